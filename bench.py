@@ -9,11 +9,16 @@ A step = forward + 4x structure loss + backward + clamp(0.5) + Adam(1e-4) [+ RCC
 reference runs between optimizer.zero_grad() and optimizer.step() (MyTrain_med.py:59-86), on synthetic data (images N(0,1),
 1-3 random ellipses per mask) with random-init weights (the reference's default init, seed 0).  Rank 0 prints ONE JSON line.
 
-Extra objects in that line:
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+    --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy (float32; fixed,
+                         seeded samples of the large arrays, 24 MB at most): loss.npy, logits.npy, weights.npy (see dump_outputs)
+    --full               everything else the benchmark measures, after the headline, as extra objects of the same line:
   roofline     — the dominant kernel family (implicit-GEMM conv forward+dgrad on MFMA): algorithmic FLOPs / measured kernel
                  time, timed with HIP events on the launch stream inside an instrumented extra step.
+  fp32, fp32fast, configs, module_surface[_verbatim], inference, dp1 — the other precisions / configurations (--no-fp32-line, --no-extras).
   cpu_baseline — the CPU oracle (oracle/pranet_oracle.py, a torch-CPU port of the same step) timed on this host's cores on a
-                 bounded sample (rank 0, N=1 only).
+                 bounded sample (rank 0, N=1 only; --no-cpu-baseline).
+  dp.exposed_comm_ms — multi-rank runs: the step with the collectives minus the same graphs without them.
 """
 import argparse, json, os, sys, time
 
@@ -299,6 +304,32 @@ def dp1_line(dev, x, m, steps=10):
     return res
 
 
+DUMP_SAMPLE = 1 << 21          # elements kept of an output larger than this (8 MB of float32)
+
+
+def dump_outputs(d, tr, loss):
+    """--dump-outputs: what the timed step (Trainer.step / replay) hands its caller after the last timed step, as float32 .npy files in `d`:
+      loss.npy    the step's loss vector [loss2, loss3, loss4, loss5, total]
+      logits.npy  Trainer.last_outs, the 8 lateral logit maps [8, N, H, W] flattened (res2net / pvt; the mutation loss keeps none)
+      weights.npy the trained weights after the optimizer step (the flat fp32 arena every model parameter is a view of)
+    An array with more than DUMP_SAMPLE elements is sampled at DUMP_SAMPLE flat indices drawn from a generator seeded per name (sorted, fixed for a
+    given shape), so that two builds run with the same arguments can be compared element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+
+    def put(name, t, seed):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(seed)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())          # (the copy to the host waits for the step)
+    put("loss", loss, 0)
+    if tr.last_outs is not None:
+        put("logits", tr.last_outs, 1)
+    put("weights", tr.flat, 2)
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -473,9 +504,12 @@ def main(argv=None):
                          "emcad = config 5 (EMCADNet dual K=9 + the 15-subset loss + AdamW, use --batch 16 --size 512)")
     ap.add_argument("--dp1", action="store_true", help="single GPU, but through the data-parallel path on a ONE-rank RCCL communicator (bucket hooks, graph "
                                                        "segments, ncclAllReduce between them): validates the RCCL plumbing where only one GPU is available")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-line", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra records of the default single-GPU run (configs 4 / 5, module surface, inference, one-rank DP)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else: the instrumented roofline / per-kernel step, the exposed "
+                                                        "all-reduce time, the fp32 lines, configs 4 / 5, module surface, inference, one-rank DP, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-fp32-line", action="store_true", help="--full without the fp32 / fp32fast lines")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra records of the single-GPU run (configs 4 / 5, module surface, inference, one-rank DP)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of a multi-rank run (nccl = RCCL; gloo only with --dry-run)")
     ap.add_argument("--dry-run", action="store_true", help="launcher + rendezvous + bucketed gradient all-reduce + the timing protocol, no model (see wire_only)")
     ap.add_argument("--launch-timeout", type=float, default=1800.0, help="seconds after which a self-launched multi-rank run is killed (status 124)")
@@ -552,11 +586,15 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t)
     loss_v = [float(v) for v in loss.float().cpu()]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, loss)
 
-    # ---- instrumented extra step: per-kernel-family HIP-event timing (not part of the timed region)
-    from pn2 import profile as prof
-    roof = prof.measure_step(tr, x, m, args.dtype, config={"model": args.model, "batch": args.batch, "size": args.size, "dtype": args.dtype})
-    # ---- data-parallel exchange: how much of the gradient all-reduce is exposed (time of a step with the collectives minus one without)
+    roof = None
+    if args.full:
+        # ---- instrumented extra step: per-kernel-family HIP-event timing (not part of the timed region)
+        from pn2 import profile as prof
+        roof = prof.measure_step(tr, x, m, args.dtype, config={"model": args.model, "batch": args.batch, "size": args.size, "dtype": args.dtype})
+    # ---- data-parallel exchange: how much of the gradient all-reduce is exposed (time of a step with the collectives minus one without; --full)
     dp = None
     if use_dist:
         def timed(fn, n=5):
@@ -566,13 +604,13 @@ def main(argv=None):
             torch.cuda.synchronize()
             return (time.perf_counter() - t0_) / n
         st_ = tr._cur
-        t_all = timed(step)
+        t_all = timed(step) if args.full else None
         def no_exchange():          # the same graphs without the collectives
             for g_ in ([g for g, _ in st_.segments] if st_.segments else [st_.graph]):
                 g_.replay()
             st_.graph_opt.replay()
         t_noex = None
-        if use_graph and st_.graph_opt is not None:
+        if args.full and use_graph and st_.graph_opt is not None:
             # the probe steps the optimizer on UNREDUCED local gradients: replicas would silently diverge - restore weights and Adam state after it
             keep = [t_.clone() for t_ in (tr.flat, tr.exp_avg, tr.exp_avg_sq, tr.bias_corr)]
             t_noex = timed(no_exchange)
@@ -600,24 +638,25 @@ def main(argv=None):
             "loss": loss_v,
             "mfma_frac_whole_step": (None if args.model == "emcad" else
                                      round(ips / world * (TRAIN_GFLOP_PER_IMG if args.model == "res2net" else 72.3) / 1e3 / (PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_F32_TFLOPS), 4)),
-            "roofline": roof["roofline"], "kernels": roof["kernels"],
         }
-        hb = out["roofline"].get("step_hbm_bytes_pmc")
-        if hb:          # the whole step against the HBM roofline: bytes of the committed PMC passes / this run's step time (the step is traffic-bound first)
-            gbs = hb / (1e-3 * out["ms_per_step"]) / 1e9
-            out["roofline"]["step_hbm"] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(gbs / 8000.0, 4), "bytes_per_step": hb,
-                                          "source": out["roofline"].get("traffic_source"), "source_commit": out["roofline"].get("traffic_commit"),
-                                          "note": "bytes: PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, eager launches) recorded at source_commit - a derived figure, stale "
-                                                  "if kernels that move data changed after that commit; time: this run"}
+        if roof is not None:
+            out["roofline"], out["kernels"] = roof["roofline"], roof["kernels"]
+            hb = out["roofline"].get("step_hbm_bytes_pmc")
+            if hb:          # the whole step against the HBM roofline: bytes of the committed PMC passes / this run's step time (the step is traffic-bound first)
+                gbs = hb / (1e-3 * out["ms_per_step"]) / 1e9
+                out["roofline"]["step_hbm"] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(gbs / 8000.0, 4), "bytes_per_step": hb,
+                                              "source": out["roofline"].get("traffic_source"), "source_commit": out["roofline"].get("traffic_commit"),
+                                              "note": "bytes: PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, eager launches) recorded at source_commit - a derived figure, stale "
+                                                      "if kernels that move data changed after that commit; time: this run"}
         # always present: how many ranks exchanged gradients (1 = a single process, no collective on the data path)
         out["dp"] = dp if dp is not None else {"backend": None, "nccl_ranks": 1, "mode": "single process, no collective on the data path"}
-        if world == 1 and not args.no_fp32_line and args.model == "res2net" and args.dtype == "bf16":
+        if args.full and world == 1 and not args.no_fp32_line and args.model == "res2net" and args.dtype == "bf16":
             tr = None
             torch.cuda.empty_cache()
             out["fp32"] = fp32_line(lambda: PraNet_V2(num_class=1).to(dev).train(), x, m)
             torch.cuda.empty_cache()
             out["fp32fast"] = fp32_line(lambda: PraNet_V2(num_class=1).to(dev).train(), x, m, mode="fp32fast")
-        if world == 1 and not args.no_extras and not args.dp1 and args.model == "res2net" and args.dtype == "bf16" and args.batch == 32 and args.size == 352:
+        if args.full and world == 1 and not args.no_extras and not args.dp1 and args.model == "res2net" and args.dtype == "bf16" and args.batch == 32 and args.size == 352:
             # the other numbers of the repository, in the driver's record (each bounded to a few seconds of GPU time; a failure is reported, not fatal)
             tr = None
             torch.cuda.empty_cache()
@@ -631,7 +670,7 @@ def main(argv=None):
             if "dp1" in out and "ms_per_step" in out["dp1"]:
                 out["dp1"]["local_ms_per_step"] = out["ms_per_step"]
                 out["dp1"]["overhead_frac"] = round(out["dp1"]["ms_per_step"] / out["ms_per_step"] - 1.0, 4)
-        if world == 1 and not args.no_cpu_baseline and args.model != "emcad":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model != "emcad":
             out["cpu_baseline"] = cpu_baseline(args.size)
         try:          # libraries that printf to the C stdout of a pipe (RCCL's version banner) are flushed first: the JSON line stays the last line of stdout
             import ctypes

@@ -72,14 +72,18 @@ def test_refuses_to_launch_ranks_under_a_profiler():
     assert r.returncode == 2 and "profiled process" in r.stderr and r.stdout.strip() == ""
 
 
-def test_gpu_count_comes_from_sysfs_not_from_hip(tmp_path):
+def test_gpu_count_comes_from_sysfs_not_from_hip(tmp_path, monkeypatch):
     import bench
+    monkeypatch.delenv("HIP_VISIBLE_DEVICES", raising=False)          # the count of the fake topology, not of the devices this process was given
+    monkeypatch.delenv("ROCR_VISIBLE_DEVICES", raising=False)
     for i, simd in enumerate((0, 256, 256, 0)):          # two CPU nodes, two GPU nodes
         d = tmp_path / str(i)
         d.mkdir()
         (d / "properties").write_text(f"cpu_cores_count {0 if simd else 64}\nsimd_count {simd}\nmem_banks_count 1\n")
     assert bench.count_gpus_sysfs(str(tmp_path)) == 2
     assert bench.count_gpus_sysfs(str(tmp_path / "missing")) in (0, None)
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "1")          # a visible-device list caps the count
+    assert bench.count_gpus_sysfs(str(tmp_path)) == 1
 
 
 def test_sigterm_to_the_launcher_takes_the_rank_group_down(tmp_path):
