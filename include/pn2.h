@@ -9,7 +9,9 @@
  *   - every pointer is a DEVICE pointer owned by the caller (PyTorch allocates; the library never frees);
  *   - activations are NHWC views: base pointer at the view's first channel, `ld` = elements between pixels;
  *   - dtype: PN2_F32 (fp32 parity path: fp32 storage, conv products and sums in double on v_mfma_f64_16x16x4_f64, one rounding per output)
- *     or PN2_BF16 (bf16 storage, v_mfma_f32_16x16x32_bf16, f32 accumulate);
+ *     or PN2_BF16 (bf16 storage, v_mfma_f32_16x16x32_bf16, f32 accumulate); the conv contraction entry points - pn2_conv_gemm, _ep, _gated, _affine,
+ *     _multi, _tile, _job_blocks, pn2_conv_wgrad, _multi, _variant, pn2_conv_tile_m and pn2_conv_stat_blocks - also take PN2_F32F ("fp32fast":
+ *     fp32 storage like PN2_F32, fp32 products and sums on v_mfma_f32_16x16x4_f32); every other entry point takes PN2_F32 for fp32fast tensors;
  *   - every call is asynchronous on `stream` (a hipStream_t); returns 0 on success, <0 for argument
  *     errors (-1 null pointer, -2 unsupported geometry/alignment, -3 unknown dtype), >0 = hipError_t;
  *   - no global state; safe to call from any thread / any stream; graph-capture safe (no sync, no malloc).
@@ -22,6 +24,7 @@ extern "C" {
 
 #define PN2_F32 0
 #define PN2_BF16 1
+#define PN2_F32F 2         /* conv contraction entry points only (see dtype above) */
 #define PN2_CONV_STATS 1   /* emit per-channel sum / sum-of-squares partials (fused BN batch statistics) */
 #define PN2_CONV_ACCUM 2   /* out += result (gradient accumulation) */
 #define PN2_CONV_SPLITK(n) ((n) << 16)   /* bf16 LDS-DMA kernels only (tuning code kernel 2 / 3): n = 2..15 workgroups share the K loop of a tile and

@@ -4,16 +4,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/pn2.h"          // PN2_F32 / PN2_BF16 / PN2_F32F
 
 typedef unsigned short bf16_t;   // storage type; arithmetic always in f32
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) double f64x4_t;
-
-#define PN2_F32 0
-#define PN2_BF16 1
-#define PN2_F32F 2          // fp32 storage like PN2_F32, contractions on the f32 matrix pipe (v_mfma_f32_16x16x4_f32, 157 TF/s) instead of the f64 one - conv GEMM / wgrad entry points only
 
 // storage type of PN2_F32F: a float under another name, so that the conv kernels (templated on the storage type) pick another MFMA form for it
 struct f32f_t { float v; };

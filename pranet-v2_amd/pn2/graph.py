@@ -10,31 +10,30 @@ import torch
 
 import weakref
 
-from .capi import F32, BF16
+from .capi import F32, BF16, F32F
 from .engine import Engine, GradQueue, PackCache, StepArena, TUNER
 
-_DT = {"bf16": BF16, "bfloat16": BF16, "fp32": F32, "float32": F32, "f32": F32}
+_DT = {"bf16": BF16, "bfloat16": BF16, "fp32": F32, "float32": F32, "f32": F32, "fp32fast": F32F, "f32fast": F32F, "fp32_fast": F32F}
+_MODE = {BF16: "bf16", F32: "fp32", F32F: "fp32fast"}
 _compute_dtype = _DT[os.environ.get("PN2_DTYPE", "bf16").lower()]
 
 
 def set_compute_dtype(name):
     """'bf16' (default: bf16 storage + MFMA, fp32 accumulate), 'fp32' (fp32 storage, conv contractions in DOUBLE on the f64 matrix pipe: the parity path) or
     'fp32fast' (fp32 storage, fp32 products and sums on the f32 matrix pipe - the reference's own arithmetic, MyTrain_med.py runs without autocast - at twice
-    the pipe rate; everything except the conv GEMM / wgrad kernels is the 'fp32' path)."""
+    the pipe rate; everything except the conv GEMM / wgrad kernels is the 'fp32' path).  Trainers and predictors built afterwards run in this mode, those
+    built before keep theirs; a module call runs in the mode current at the call, each mode on call sites of its own."""
     global _compute_dtype
-    from . import capi
-    fast = isinstance(name, str) and name.lower() in ("fp32fast", "f32fast", "fp32_fast")
-    capi.set_f32_mma(fast)
-    _compute_dtype = F32 if fast else (_DT[name.lower()] if isinstance(name, str) else name)
+    _compute_dtype = _DT[name.lower()] if isinstance(name, str) else name
 
 
 def get_compute_mode():
     """'bf16' | 'fp32' | 'fp32fast'"""
-    from . import capi
-    return "bf16" if _compute_dtype == BF16 else ("fp32fast" if capi.F32_MMA == capi.F32F else "fp32")
+    return _MODE[_compute_dtype]
 
 
 def get_compute_dtype():
+    """The mode as the engine takes it: capi.BF16, capi.F32 or capi.F32F."""
     return _compute_dtype
 
 

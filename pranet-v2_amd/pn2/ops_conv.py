@@ -6,7 +6,7 @@ import torch
 
 from . import capi
 from . import core
-from .capi import call, F32, BF16
+from .capi import call, F32, BF16, F32F
 from .core import (Act, Bnb, KSPLIT_MINK, TUNE_REPS, WGRAD_SLAB_MB, WGRAD_WGS, _LinearAsConv, _job_table, _p, _stream, _thrash, _w4, rup)
 
 KS_UNTUNED = 3 | (1 << 2) | (2 << 4) | 0x40          # tuning code: LDS-DMA 2-stage ring, 64 x 128 tile, two K groups (see ConvOps._untuned)
@@ -49,7 +49,7 @@ class ConvOps:
         self.tuner and reused under hipGraph capture).  Returns the code for pn2_conv_desc.flags bits 8..15 (0 = library heuristic).
         ep: the launch carries a BatchNorm-backward epilogue (pn2_conv_gemm_ep): the candidates are timed WITH it (its extra operand reads and
         per-tile work favour other tiles than the plain kernel), writing to scratch destinations."""
-        fast = self.dt == F32 and capi.F32_MMA == capi.F32F          # fp32fast: tiles of the register-staged kernel are tuned per shape too (64-row tiles win where
+        fast = self.mma == F32F                                      # fp32fast: tiles of the register-staged kernel are tuned per shape too (64-row tiles win where
         if self.dt != BF16 and not fast:                             # the heuristic takes 128: more workgroups per CU; 716 -> 748 images/s with 64 rows everywhere)
             return 0
         t = self.tuner
@@ -107,11 +107,11 @@ class ConvOps:
 
             def launch(code):
                 d2.flags = base | (code << 8)
-                call.pn2_conv_gemm_ep(self.dt, in_ptr, _p(wp), _p(scratch), C.byref(d2), C.byref(e2), st)
+                call.pn2_conv_gemm_ep(self.mma, in_ptr, _p(wp), _p(scratch), C.byref(d2), C.byref(e2), st)
         else:
             def launch(code):
                 d2.flags = code << 8
-                call.pn2_conv_gemm(self.dt, in_ptr, _p(wp), _p(scratch), nul, nul, C.byref(d2), st)
+                call.pn2_conv_gemm(self.mma, in_ptr, _p(wp), _p(scratch), nul, nul, C.byref(d2), st)
         # Intra-workgroup split-K (conv_dma_gemm_ks, tuning-code bit 6: two K groups of four waves) sums a tile's K loop in another fp32 order than the plain
         # kernels, which all agree bit for bit.  Whether a shape takes it is therefore a RULE of the shape, not of a timing: about one wave of tiles and a long
         # K loop (what the free tuning run of round 5 picked it for) - every call site that computes the same conv gets the same bits, and the tuner chooses
@@ -171,13 +171,13 @@ class ConvOps:
         if bm:
             b = 64 if bm == 1 else 128
             return (M + b - 1) // b
-        return call.pn2_conv_stat_blocks(M, Cout, capi.F32_MMA if self.dt == F32 else self.dt)          # (fp32fast picks its own tiles)
+        return call.pn2_conv_stat_blocks(M, Cout, self.mma)          # (fp32fast picks its own tiles)
 
     def _tune_wgrad(self, wd, dy_ptr, x_ptr, rd, nsplit, wshape):
         """-> (kernel code, pixel splits) for this wgrad shape.  Candidates: register-staged / LDS-DMA / LDS-DMA with 128 x 256 tiles x
         {1, 1/2, 1/4, 1/8} of the heuristic split count; each is timed together with the slab reduction its split count implies."""
         t = self.tuner
-        fast = self.dt == F32 and capi.F32_MMA == capi.F32F          # fp32fast: one kernel, but the pixel-split count is worth timing
+        fast = self.mma == F32F          # fp32fast: one kernel, but the pixel-split count is worth timing
         if t is None or (self.dt != BF16 and not fast):
             return 0, nsplit
         key = ("w", wd.N, wd.H, wd.W, wd.OH, wd.OW, wd.Cin_p, wd.ld_x, wd.Cout_p, wd.ld_dy, wd.KH, wd.KW, wd.stride, wd.pad_h, wd.pad_w, wd.dil_h, wd.dil_w, nsplit)
@@ -203,7 +203,7 @@ class ConvOps:
 
         def run(code, ns):
             wd.tune = code
-            call.pn2_conv_wgrad(self.dt, dy_ptr, x_ptr, _p(slab), C.byref(wd), ns, st)
+            call.pn2_conv_wgrad(self.mma, dy_ptr, x_ptr, _p(slab), C.byref(wd), ns, st)
             call.pn2_wgrad_reduce(_p(slab), _p(gw), C.byref(rd), ns, 0, st)
         for code, ns in cands:
             run(code, ns)
@@ -303,7 +303,7 @@ class ConvOps:
             cd.ld_out = out.ld
             cd.flags = (tune << 8) | capi.CONV_AFFINE | (capi.CONV_RELU6 if relu == 2 else (capi.CONV_RELU if relu else 0))
             capi.WORK.update(flops=2 * M * Cout * Cin * KH * KW, tag=":fwd", shape=f"{Cin}->{Cout} k{KH}x{KW} s{sh} d{dh} {N}x{OH}x{OW}")
-            call.pn2_conv_gemm_affine(self.dt, x.ptr, _p(wp), out.ptr, _p(scale), _p(shift), residual.ptr if residual is not None else C.c_void_p(0),
+            call.pn2_conv_gemm_affine(self.mma, x.ptr, _p(wp), out.ptr, _p(scale), _p(shift), residual.ptr if residual is not None else C.c_void_p(0),
                                       residual.ld if residual is not None else 0, C.byref(cd), st)
             return out
         tile_rows = 0
@@ -320,7 +320,7 @@ class ConvOps:
         if gate is not None:
             assert (KH, KW, sh) == (1, 1, 1) and gate.dt == F32 and gate.C == 1 and gate.M == M and bias is None, "the fused gate sits in front of a bias-free 1x1 conv"
             ksplit = 1
-            call.pn2_conv_gemm_gated(self.dt, x.ptr, _p(wp), _p(raw), _p(psum), _p(psq), C.byref(cd), gate.ptr, st)
+            call.pn2_conv_gemm_gated(self.mma, x.ptr, _p(wp), _p(raw), _p(psum), _p(psq), C.byref(cd), gate.ptr, st)
         elif ksplit > 1:
             # few output rows, long contraction (the 5x5 convs of the ra4 branch on 11x11 maps): the K loop of every tile is shared by ksplit
             # workgroups that leave fp32 partial tiles; the reduce sums them and takes the BatchNorm statistics / adds the bias
@@ -329,14 +329,14 @@ class ConvOps:
             if train_bn:
                 nblk, tile_rows = (M + 63) // 64, 0          # the reduce leaves raw moments of 64-row blocks
                 psum, psq = self.fbuf(nblk, Cout_p), self.fbuf(nblk, Cout_p)
-            call.pn2_conv_gemm(self.dt, x.ptr, _p(wp), _p(raw), _p(ws), _p(None), C.byref(cd), st)
+            call.pn2_conv_gemm(self.mma, x.ptr, _p(wp), _p(raw), _p(ws), _p(None), C.byref(cd), st)
             call.pn2_conv_splitk_reduce(self.dt, _p(ws), ksplit, M, Cout_p, _p(raw), raw_ld, _p(bvec) if fuse_bias else _p(None),
                                         _p(psum) if train_bn else _p(None), _p(psq) if train_bn else _p(None), 0, st)
         elif fuse_bias:
             cd.flags |= capi.CONV_BIAS
-            call.pn2_conv_gemm(self.dt, x.ptr, _p(wp), _p(raw), _p(bvec), _p(None), C.byref(cd), st)
+            call.pn2_conv_gemm(self.mma, x.ptr, _p(wp), _p(raw), _p(bvec), _p(None), C.byref(cd), st)
         else:
-            call.pn2_conv_gemm(self.dt, x.ptr, _p(wp), _p(raw), _p(psum), _p(psq), C.byref(cd), st)
+            call.pn2_conv_gemm(self.mma, x.ptr, _p(wp), _p(raw), _p(psum), _p(psq), C.byref(cd), st)
 
         scale = shift = mean = invstd = par = None
         bd = None
@@ -549,11 +549,11 @@ class ConvOps:
             gwt, gwa = self.pgrads.sink(w)
             # wgrad (+ slab reduce) only feeds the parameter gradient: with a gradient queue both are deferred into the table-driven launches of its flush
             if rq is not None and rq.defer_wgrad:
-                rq.add_wgrad(self.dt, draw, x.ptr, x.t, slab, wd, nsplit, flops)
+                rq.add_wgrad(self.mma, draw, x.ptr, x.t, slab, wd, nsplit, flops)
                 rq.add_reduce(slab, gwt, rd, nsplit, gwa)
             else:
                 capi.WORK.update(flops=flops, tag="", shape=shape)
-                call.pn2_conv_wgrad(self.dt, _p(draw), x.ptr, _p(slab), C.byref(wd), nsplit, st)
+                call.pn2_conv_wgrad(self.mma, _p(draw), x.ptr, _p(slab), C.byref(wd), nsplit, st)
                 if rq is None:
                     call.pn2_wgrad_reduce(_p(slab), _p(gwt), C.byref(rd), nsplit, gwa, st)
                 else:
@@ -575,7 +575,7 @@ class ConvOps:
                 dd.transposed, dd.Kp, dd.flags = 0, Kp2, 0
                 dd.flags |= self._tune_gemm(dd, _p(draw), wp2, M, Ct) << 8
                 capi.WORK.update(flops=flops, tag=":dgrad", shape=shape + " patch")
-                call.pn2_conv_gemm(self.dt, _p(draw), _p(wp2), _p(tpatch), C.c_void_p(0), C.c_void_p(0), C.byref(dd), st)
+                call.pn2_conv_gemm(self.mma, _p(draw), _p(wp2), _p(tpatch), C.c_void_p(0), C.c_void_p(0), C.byref(dd), st)
                 call.pn2_depth_to_space(self.dt, _p(tpatch), Ct, _p(gx), gx.stride(2), N, H, W, OH, OW, KH, x.Cp, gxa, st)
             elif x.requires_grad and core.SMALL_CIN_DGRAD and Cin <= 4 and sh > 1 and dh == 1 and dw == 1 and ph == pw and (x.gw == x.gwp or x.Cp == x.gwp) and gw_o == gwp_o \
                     and Cout_p == Cout and KH * KW * Cout * 16 <= 64 * 1024 and x.ld == x.Cp:
@@ -623,7 +623,7 @@ class ConvOps:
                 if ks > 1:
                     ws = self.fbuf(ks, Mx, x.Cp)
                     dd.flags = ((2 | (1 << 2) | ((3 if x.Cp > 64 else 2) << 4)) << 8) | (ks << 16)
-                    call.pn2_conv_gemm(self.dt, _p(draw), _p(wt), _p(gx), _p(ws), C.c_void_p(0), C.byref(dd), st)
+                    call.pn2_conv_gemm(self.mma, _p(draw), _p(wt), _p(gx), _p(ws), C.c_void_p(0), C.byref(dd), st)
                     call.pn2_conv_splitk_reduce(self.dt, _p(ws), ks, Mx, x.Cp, _p(gx), x.Cp, C.c_void_p(0), C.c_void_p(0), C.c_void_p(0), gxa, st)
                 elif want_ep:
                     ep = capi.ConvEp()
@@ -657,17 +657,17 @@ class ConvOps:
                         v.grad_written = True
                         x.dual_done = True
                         u._sealed = v._sealed = True
-                        call.pn2_conv_gemm_ep(self.dt, _p(draw), _p(wt), _p(gu), C.byref(dd), C.byref(ep), st)
+                        call.pn2_conv_gemm_ep(self.mma, _p(draw), _p(wt), _p(gu), C.byref(dd), C.byref(ep), st)
                     else:
                         self._fill_bnb(ep.a, x, nbx, ep, tcode)
-                        call.pn2_conv_gemm_ep(self.dt, _p(draw), _p(wt), _p(gx), C.byref(dd), C.byref(ep), st)
+                        call.pn2_conv_gemm_ep(self.mma, _p(draw), _p(wt), _p(gx), C.byref(dd), C.byref(ep), st)
                     if pool_ok and x.pool_prior is not None:
                         x.pool_prior = None
                         self._pending_pool.remove(x)
                     x._sealed = True
                 else:
                     dd.flags |= self._tune_gemm(dd, _p(draw), wt, Mx, x.Cp) << 8
-                    call.pn2_conv_gemm(self.dt, _p(draw), _p(wt), _p(gx), C.c_void_p(0), C.c_void_p(0), C.byref(dd), st)
+                    call.pn2_conv_gemm(self.mma, _p(draw), _p(wt), _p(gx), C.c_void_p(0), C.c_void_p(0), C.byref(dd), st)
 
         self.record(bwd)
         return out if y2 is None else (out, y2)
@@ -713,7 +713,7 @@ class ConvOps:
 
     def _tile_m(self, M, Cout, tune):
         bm = (tune >> 2) & 3
-        return (64 if bm == 1 else 128) if bm else call.pn2_conv_tile_m(M, Cout, capi.F32_MMA if self.dt == F32 else self.dt)
+        return (64 if bm == 1 else 128) if bm else call.pn2_conv_tile_m(M, Cout, self.mma)
 
     def _fill_bnb(self, t, act, nblk, ep=None, tcode=0):
         """Describe `act`'s BatchNorm to a dgrad epilogue target and register the partial rows it will leave."""
@@ -860,10 +860,10 @@ class ConvOps:
                         fold.add(key, bn, par, bd, off)
             out = Act(self, self.empty(N, H, W, Ct), Ct, Ct, Ct, self.dt)
             cd.flags = (tune << 8) | capi.CONV_AFFINE
-            call.pn2_conv_gemm_affine(self.dt, x.ptr, _p(wp), out.ptr, _p(par[0]), _p(par[1]), C.c_void_p(0), 0, C.byref(cd), st)
+            call.pn2_conv_gemm_affine(self.mma, x.ptr, _p(wp), out.ptr, _p(par[0]), _p(par[1]), C.c_void_p(0), 0, C.byref(cd), st)
             return [out.slice(off, off + co) for co, off in zip(couts, offs)]
         raw = self.empty(N, H, W, Ct)
-        call.pn2_conv_gemm(self.dt, x.ptr, _p(wp), _p(raw), _p(psum), _p(psq), C.byref(cd), st)
+        call.pn2_conv_gemm(self.mma, x.ptr, _p(wp), _p(raw), _p(psum), _p(psq), C.byref(cd), st)
         scale, shift = self.fbuf(Ct), self.fbuf(Ct)
         mean, invstd = (self.fbuf(Ct), self.fbuf(Ct)) if train else (None, None)
         bds = []
@@ -919,10 +919,10 @@ class ConvOps:
                 nsplit = rq.table_splits(nsplit, M, x.Cp + Ct, wd, 4 if self.dt == F32 else 2)
             slab = self.fbuf(nsplit, wd.Rp, wd.Kp) if rq is None else rq.slab(tuple(id(c.weight) for c in convs), (nsplit, wd.Rp, wd.Kp), self.dev)
             if rq is not None and rq.defer_wgrad:
-                rq.add_wgrad(self.dt, draw, x.ptr, x.t, slab, wd, nsplit, flops)
+                rq.add_wgrad(self.mma, draw, x.ptr, x.t, slab, wd, nsplit, flops)
             else:
                 capi.WORK.update(flops=flops, tag="", shape=shape)
-                call.pn2_conv_wgrad(self.dt, _p(draw), x.ptr, _p(slab), C.byref(wd), nsplit, st)
+                call.pn2_conv_wgrad(self.mma, _p(draw), x.ptr, _p(slab), C.byref(wd), nsplit, st)
             for c, co, off in zip(convs, couts, offs):
                 gwt, gwa = self.pgrads.sink(c.weight)
                 rd = self._pack_desc(c.weight, x_map, (co, co, co), False)
@@ -941,7 +941,7 @@ class ConvOps:
                 dd.transposed, dd.Kp, dd.flags = 1, Kt, (capi.CONV_ACCUM if gxa else 0)
                 dd.flags |= self._tune_gemm(dd, _p(draw), wt, M, x.Cp) << 8
                 capi.WORK.update(flops=flops, tag=":dgrad", shape=shape)
-                call.pn2_conv_gemm(self.dt, _p(draw), _p(wt), _p(gx), nul, nul, C.byref(dd), st)
+                call.pn2_conv_gemm(self.mma, _p(draw), _p(wt), _p(gx), nul, nul, C.byref(dd), st)
         self.record(bwd)
         return outs
 

@@ -9,7 +9,6 @@ import time
 import torch
 
 from . import capi
-from .capi import F32
 
 _EL = {0: 4, 1: 2}
 ACTUAL = {}     # bytes the fused DSRA tail kernels really move (next to SURVEY's algorithmic 17*S figure)
@@ -129,14 +128,12 @@ class Recorder:
                 by_ = 0
                 if _name in ("pn2_conv_gemm", "pn2_conv_gemm_ep", "pn2_conv_gemm_multi", "pn2_conv_wgrad", "pn2_conv_wgrad_multi"):
                     fl, tag, shape = capi.WORK.pop("flops", 0), capi.WORK.pop("tag", ""), capi.WORK.pop("shape", "")
-                    es = 4 if int(a[0]) == capi.F32 else 2
+                    es = 2 if int(a[0]) == capi.BF16 else 4
                     by_ = sum(_conv_bytes(s_, es) for s_ in (capi.WORK.pop("shapes", None) or [shape]))
                 else:
                     fl, tag, shape = 0, "", _shape(_name, a)
                     by_ = capi.WORK.pop("bytes", 0) if _name.endswith("_multi") else _bytes(_name, a)      # lock-step launches: summed over their jobs
                 e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                if _name in capi._MMA_FUNCS and int(a[0]) == capi.F32:          # fp32fast: the translation capi.call applies at the ABI boundary
-                    a = (capi.F32_MMA,) + tuple(a[1:])
                 e0.record()
                 rc = _fn(*a)
                 e1.record()
@@ -221,7 +218,8 @@ def _conv_class(shape):
 
 
 def measure_step(trainer, x, m, dtype, config=None):
-    peak_tf = 2500.0 if dtype == "bf16" else 157.3
+    """dtype: the caller's name for the mode (unused: the peak is that of the matrix pipe the trainer's own mode runs on)."""
+    peak_tf = 2500.0 if trainer.dtype == capi.BF16 else 157.3
     ACTUAL.clear()
     trainer.step(x, m)                       # eager warm-up (allocator, caches)
     # Keep the GPU queue full during the instrumented step: a spin kernel first, so the host runs ahead and every event marker

@@ -58,7 +58,7 @@ class Trainer:
             raise ValueError(f"unknown loss {loss!r}")
         clip = 3.0e38 if clip is None else clip
         self.lr, self.clip, self.betas, self.eps = lr, clip, betas, eps
-        self.dtype = get_compute_dtype() if dtype is None else dtype
+        self.dtype = get_compute_dtype() if dtype is None else dtype          # compute mode (BF16 / F32 / F32F), kept for the object's life
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.dp = process_group is not None and (self.world > 1 or force_dp or os.environ.get("PN2_DP_FORCE", "0") == "1")
@@ -180,7 +180,7 @@ class Trainer:
         # only with the bump arena (nothing is recycled inside a step) do the buffers of a lane outlive the deferred emission
         eng.fuse_tail = self.fuse_tail and self.loss_kind == "structure"
         if size is not None and (size != images.shape[2] or size != images.shape[3]):
-            x = eng.cast(eng.resize_to(eng.from_nchw(images, dt=F32), size, size, align_corners=True), self.dtype)
+            x = eng.cast(eng.resize_to(eng.from_nchw(images, dt=F32), size, size, align_corners=True), eng.dt)
             n_, _, h_, w_ = gts.shape
             g = Act(eng, gts.reshape(n_, h_, w_, 1).float().contiguous(), 1, 1, 1, F32, requires_grad=False)
             gts = eng.resize_to(g, size, size, align_corners=True).t

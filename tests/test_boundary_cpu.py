@@ -44,6 +44,52 @@ def test_value_helpers_run_without_gpu():
     assert call.pn2_loss_blocks(352 * 352) == 31
 
 
+def test_header_dtype_codes_match_binding():
+    from pn2 import capi
+    src = open(os.path.join(ROOT, "include", "pn2.h")).read()
+    codes = {n: int(v) for n, v in re.findall(r"#define\s+PN2_(F32F|F32|BF16)\s+(\d+)", src)}
+    assert codes == {"F32": capi.F32, "BF16": capi.BF16, "F32F": capi.F32F}
+
+
+def test_compute_mode_names_round_trip():
+    import pn2
+    from pn2 import capi, graph
+    was = graph.get_compute_dtype()
+    try:
+        for name, code in (("bf16", capi.BF16), ("fp32", capi.F32), ("fp32fast", capi.F32F)):
+            pn2.set_compute_dtype(name)
+            assert graph.get_compute_mode() == name and pn2.get_compute_dtype() == code
+            pn2.set_compute_dtype(graph.get_compute_mode())
+            assert pn2.get_compute_dtype() == code
+    finally:
+        pn2.set_compute_dtype(was)
+
+
+def test_call_passes_arguments_through_in_every_mode(monkeypatch):
+    """The dtype code a caller passes is the one the library receives, whatever the process-wide mode (no translation at the boundary)."""
+    import pn2
+    from pn2 import capi, graph
+    lib = capi.load()
+    seen = []
+    names = ("pn2_conv_gemm", "pn2_conv_wgrad", "pn2_conv_gemm_tile", "pn2_pack_weight")
+    for n in names:
+        monkeypatch.setattr(lib, n, lambda *a, _n=n: seen.append((_n, a)) or 0)
+    was = graph.get_compute_dtype()
+    try:
+        for mode in ("bf16", "fp32", "fp32fast"):
+            pn2.set_compute_dtype(mode)
+            for n in names:
+                capi.call.__dict__.pop(n, None)          # (checked wrappers are cached on the caller)
+                for dt in (capi.F32, capi.BF16, capi.F32F):
+                    seen.clear()
+                    getattr(capi.call, n)(dt, 11, 22)
+                    assert seen == [(n, (dt, 11, 22))], (mode, n, dt, seen)
+    finally:
+        for n in names:
+            capi.call.__dict__.pop(n, None)
+        pn2.set_compute_dtype(was)
+
+
 def test_argument_errors_are_reported_not_swallowed():
     from pn2 import capi
     lib = capi.load()

@@ -156,6 +156,61 @@ def test_second_forward_before_backward_falls_back_to_the_plain_pass():
     assert st.gen == n_gen
 
 
+def _same(a, b):
+    (oa, ga), (ob, gb) = a, b
+    return all(torch.equal(u, v) for u, v in zip(oa, ob)) and ga.keys() == gb.keys() and all(torch.equal(ga[k], gb[k]) for k in ga)
+
+
+def test_call_site_follows_a_change_of_compute_mode():
+    """fp32 -> fp32fast -> fp32 on one live model: every mode replays graphs captured in its own arithmetic, bit for bit what a model that only ever ran
+    in that mode computes."""
+    import pn2
+    from pn2 import graph as G
+    from oracle import weights as W
+    G.set_module_graph(True)
+    x, _ = W.synthetic_batch(2, 96, seed=7)
+    x = x.to(dev)
+    gs = [torch.randn(2, 1, 96, 96, device=dev, generator=torch.Generator(device=dev).manual_seed(i)) for i in range(8)]
+
+    def calls(model, mode, n=5):
+        """n training calls with fixed output gradients in `mode` -> (outputs, parameter gradients) of the last one"""
+        pn2.set_compute_dtype(mode)
+        for _ in range(n):
+            model.zero_grad()
+            outs = model(x)
+            torch.autograd.backward(list(outs), gs)
+        return [o.detach().clone() for o in outs], {n_: p.grad.detach().clone() for n_, p in model.named_parameters() if p.grad is not None}
+    model = _model()
+    r32 = calls(model, "fp32")
+    sites = next(iter(model.hot_parameters())).__dict__["_pn2_sites"]
+    assert len(sites) == 1 and next(iter(sites.values())).graph_f is not None          # call 5 was a replay
+    rfast = calls(model, "fp32fast")
+    assert len(sites) == 2 and all(st.graph_f is not None for st in sites.values())
+    assert _same(rfast, calls(_model(), "fp32fast"))
+    assert not any(torch.equal(u, v) for u, v in zip(rfast[0], r32[0]))           # the two modes are told apart
+    assert _same(calls(model, "fp32", 2), r32)
+
+
+def test_trainer_keeps_the_compute_mode_it_was_built_with():
+    import pn2
+    from pn2.trainer import Trainer
+    from oracle import weights as W
+    x, m = W.synthetic_batch(2, 96, seed=3)
+    x, m = x.to(dev), m.to(dev)
+
+    def run(switch):
+        pn2.set_compute_dtype("fp32fast")
+        tr = Trainer(_model(), lr=1e-4, clip=0.5)
+        if switch:
+            pn2.set_compute_dtype("fp32")
+        losses = [tr.step(x, m).clone() for _ in range(3)]
+        torch.cuda.synchronize()
+        return losses, tr.gflat.clone(), tr.last_outs.clone()
+    ref, got = run(False), run(True)
+    assert all(torch.equal(a, b) for a, b in zip(ref[0], got[0])), (ref[0], got[0])
+    assert torch.equal(ref[1], got[1]) and torch.equal(ref[2], got[2])
+
+
 def test_clip_gradient_multi_tensor_form_is_the_per_tensor_clamp():
     """utils.clip_gradient (reference utils/utils.py:7-17) clamps GPU gradients with two multi-tensor launches: same values as the reference's per-parameter loop."""
     from utils.utils import clip_gradient

@@ -39,7 +39,7 @@ def run_all(self, t, key, cd, in_ptr, wp, M, Cout, ep):
                     code = kern | (bm << 2) | (bn << 4) | ks
                     d2.flags = code << 8
                     try:
-                        call.pn2_conv_gemm(self.dt, in_ptr, _p(wp), _p(scratch), nul, nul, C.byref(d2), st)
+                        call.pn2_conv_gemm(self.mma, in_ptr, _p(wp), _p(scratch), nul, nul, C.byref(d2), st)
                     except RuntimeError:
                         continue
                     res = {}
@@ -49,7 +49,7 @@ def run_all(self, t, key, cd, in_ptr, wp, M, Cout, ep):
                             if cold:
                                 core._thrash()
                             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                            e0.record(); call.pn2_conv_gemm(self.dt, in_ptr, _p(wp), _p(scratch), nul, nul, C.byref(d2), st); e1.record()
+                            e0.record(); call.pn2_conv_gemm(self.mma, in_ptr, _p(wp), _p(scratch), nul, nul, C.byref(d2), st); e1.record()
                             evs.append((e0, e1))
                         torch.cuda.synchronize()
                         ts = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
