@@ -48,7 +48,8 @@ typedef struct pn2_conv_desc {
     int KH, KW, stride, pad_h, pad_w, dil_h, dil_w;   /* of the FORWARD convolution */
     int transposed;         /* 0 forward gather, 1 dgrad gather */
     int Kp;                 /* packed-weight row length, multiple of 128 */
-    int flags;              /* PN2_CONV_* ; bits 8..15 optional tuning code (bf16): kernel | BM<<2 | BN<<4, see pn2_conv_tile_m */
+    int flags;              /* PN2_CONV_* ; bits 8..15 optional tuning code: kernel | BM<<2 | BN<<4, see pn2_conv_tile_m.  PN2_BF16 takes
+                               all of it; PN2_F32F takes the BM / BN bits only (register-staged kernel, BN 128 clamped to 64); PN2_F32 ignores it */
 } pn2_conv_desc;
 
 typedef struct pn2_wgrad_desc {

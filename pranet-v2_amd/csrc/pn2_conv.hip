@@ -1604,6 +1604,7 @@ __device__ __forceinline__ void conv_wgrad_body(const T* __restrict__ dy, const 
 #define PN2_WCH 8
 #endif
                 constexpr int WCH = PN2_WCH;          // MFMAs per chain (x 4 pixels): 8 = the 32 pixels of a stage (4: +1.4 % step time for gradients no closer to float64 - bs32 probes: median rel-L2 1.7e-6 / 1.9e-6, reference fp32 3.3e-6)
+                static_assert((WGP / 4) % WCH == 0, "a chain must end on a stage boundary, or its partial sum is never added to acc");
 #pragma unroll
                 for (int q = 0; q < WGP / 4; ++q) {       // 4 pixels per 16x16x4 MFMA
                     float a[MT], b[NT];
@@ -2162,7 +2163,7 @@ int launch_wgrad(const void* dy, const void* x, float* slab, const pn2_wgrad_des
 }
 
 // (kernel, BM, BN) for this desc: kern 0 register-staged, 2 LDS-DMA 3-stage, 3 LDS-DMA 2-stage.  Optional per-shape tuning code in flags bits 8..15
-// (bf16 only): kernel (1 register-staged, 2 / 3 LDS-DMA) | BM (1: 64, 2: 128) << 2 | BN (1: 32, 2: 64, 3: 128) << 4
+// (bf16; fp32fast takes the BM / BN bits, fp32 none): kernel (1 register-staged, 2 / 3 LDS-DMA) | BM (1: 64, 2: 128) << 2 | BN (1: 32, 2: 64, 3: 128) << 4
 template <typename T>
 void gemm_select(const pn2_conv_desc& d, int& kern, int& bm, int& bn) {
     pick_tiles(d.N * d.OH * d.OW, d.Cout, sizeof(T) == 4, bm, bn);
@@ -2306,13 +2307,11 @@ int gemm_multi_dispatch(int dtype, int bm, int bn, int bits, const pn2_conv_job*
         }
         return -2;
     }
-    if (dtype == PN2_F32F) {
+    if (dtype == PN2_F32F) {          // (no 128-wide tiles: gemm_select and pn2_conv_gemm_tile never pick them for 4-byte types)
         if (bm == 128) {
-            if (bn == 128) return launch_gather_tab_f32<f32f_t, EP, 128, 128, 2, 2>(jobs, bstart, njobs, total, st);
             if (bn == 64) return launch_gather_tab_f32<f32f_t, EP, 128, 64, 2, 2>(jobs, bstart, njobs, total, st);
             if (bn == 32) return launch_gather_tab_f32<f32f_t, EP, 128, 32, 4, 1>(jobs, bstart, njobs, total, st);
         } else if (bm == 64) {
-            if (bn == 128) return launch_gather_tab_f32<f32f_t, EP, 64, 128, 2, 2>(jobs, bstart, njobs, total, st);
             if (bn == 64) return launch_gather_tab_f32<f32f_t, EP, 64, 64, 2, 2>(jobs, bstart, njobs, total, st);
             if (bn == 32) return launch_gather_tab_f32<f32f_t, EP, 64, 32, 4, 1>(jobs, bstart, njobs, total, st);
         }

@@ -53,7 +53,7 @@ def _model(z, fp32, calibrated):
     import pn2
     from lib.pranet import PraNet_V2
     from oracle import weights as W
-    pn2.set_compute_dtype("fp32" if fp32 else "bf16")
+    pn2.set_compute_dtype(fp32 if isinstance(fp32, str) else ("fp32" if fp32 else "bf16"))          # (a mode name: "fp32fast")
     sd = W.make_state_dict(W.manifest_pranet_v2(1), seed=0, bn3_gamma=float(z["bn3_gamma"]))
     if calibrated:
         for f in z.files:
@@ -88,7 +88,17 @@ def test_conditioned_train_fp32_literal_tolerance(z, tag):
     probe by probe: the median must be no worse than the reference's own fp32 run (floor 2e-6) - measured 3 x better - and the worst probe must stay
     in the flip-noise range (<= 2e-2; measured 1.5e-4 .. 5.3e-3 over builds whose BatchNorm statistics round differently, the reference's own worst:
     1.5e-3 / 3.6e-3).  A wrong kernel shows as O(0.1 .. 1) on the probes behind it and moves the median."""
-    model, outs, losses = _train_case(z, tag, True)
+    _train_literal(z, tag, "fp32")
+
+
+@pytest.mark.parametrize("tag", ["t96", "t352"])
+def test_conditioned_train_fp32fast_literal_tolerance(z, tag):
+    """The same literal gates in fp32fast (fp32 products and sums on the f32 matrix pipe, the conv kernels of tests/test_gpu_convkernels_fp32.py)."""
+    _train_literal(z, tag, "fp32fast")
+
+
+def _train_literal(z, tag, mode):
+    model, outs, losses = _train_case(z, tag, mode)
     s32, s64 = int(z[f"{tag}.stride32"]), int(z[f"{tag}.stride64"])
     e32 = [float((o[:, :, ::s32, ::s32] - T(z[f"{tag}.out{i}"])).abs().max()) for i, o in enumerate(outs)]
     e64 = [float((o[:, :, ::s64, ::s64].double() - T(z[f"{tag}.f64.out{i}"])).abs().max()) for i, o in enumerate(outs)]
@@ -170,3 +180,9 @@ def test_conditioned_eval_calibrated_bn(z, tag, fp32):
         for e, t in zip(ours, tb):
             assert e <= 1.3 * t, (ours, tb)              # measured 0.93 .. 1.16 x
         assert abs(dice - ref_dice) <= max(1e-3, 1.25 * d_t)
+
+
+@pytest.mark.parametrize("tag", ["e96", "e352"])
+def test_conditioned_eval_calibrated_bn_fp32fast(z, tag):
+    """test_conditioned_eval_calibrated_bn's fp32 gates in fp32fast: |logit - ref fp32| <= 1e-4 literal, uint8 within 1 level, |d meanDic| <= 1e-3."""
+    test_conditioned_eval_calibrated_bn(z, tag, "fp32fast")

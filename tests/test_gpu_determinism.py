@@ -28,11 +28,20 @@ def _need_gpu():
 def test_captured_bs32_step_replays_bit_identically_50_times():
     """bench.py's object (Trainer.capture / replay at 32 x 3 x 352 x 352, bf16, random init) with lr = 0: the weights stay put, so every replay is the same
     computation - loss, maps and the whole gradient arena must not move by a bit over 50 replays."""
+    _replays("bf16", 50)
+
+
+def test_captured_bs32_step_replays_bit_identically_fp32fast():
+    """The same in fp32fast (bench.py --dtype fp32fast): 10 replays of the ~42 ms step, bit for bit."""
+    _replays("fp32fast", 10)
+
+
+def _replays(mode, n):
     import pn2
     from pn2.trainer import Trainer
     from lib.pranet import PraNet_V2
     from oracle import weights as W
-    pn2.set_compute_dtype("bf16")
+    pn2.set_compute_dtype(mode)
     torch.manual_seed(0)
     model = PraNet_V2(num_class=1).to(dev).train()
     x, mask = W.synthetic_batch(32, 352, seed=1234)
@@ -43,7 +52,7 @@ def test_captured_bs32_step_replays_bit_identically_50_times():
     torch.cuda.synchronize()
     g0, maps0, w0 = tr.gflat.clone(), tr.last_outs.clone(), tr.flat.clone()
     assert torch.isfinite(loss0).all() and float(g0.abs().sum()) > 0
-    for i in range(50):
+    for i in range(n):
         loss = tr.replay()
         torch.cuda.synchronize()
         assert torch.equal(loss, loss0), (i, loss.tolist(), loss0.tolist())

@@ -58,15 +58,16 @@ CONVS = [  # N, Cin, Cout, k, stride, pad, dil, H, W, bn, relu
 ]
 
 
-@pytest.mark.parametrize("dtn", ["fp32", "bf16"])
+@pytest.mark.parametrize("dtn", ["fp32", "fp32fast", "bf16"])
 @pytest.mark.parametrize("cfg", CONVS)
 def test_conv_bn_act_fwd_bwd(dtn, cfg):
     from pn2 import F32, BF16
+    from pn2.capi import F32F
     from pn2.engine import Engine
     from pn2.graph import _seed_grad
     N, Cin, Cout, k, stride, pad, dil, H, Wd, bn, relu = cfg
-    dt = F32 if dtn == "fp32" else BF16
-    err, tol = (relmax, 3e-5) if dt == F32 else (rell2, 5e-2)
+    dt = {"fp32": F32, "fp32fast": F32F, "bf16": BF16}[dtn]
+    err, tol = (relmax, 3e-5) if dt != BF16 else (rell2, 5e-2)
     torch.manual_seed(1)
     conv = nn.Conv2d(Cin, Cout, k, stride, pad, dil, bias=False).to(dev)
     bnm = nn.BatchNorm2d(Cout).to(dev) if bn else None
@@ -104,7 +105,7 @@ EVAL_CONVS = [  # N, Cin, Cout, k, stride, pad, H, W, relu, residual, out_map
 ]
 
 
-@pytest.mark.parametrize("dtn", ["fp32", "bf16"])
+@pytest.mark.parametrize("dtn", ["fp32", "fp32fast", "bf16"])
 @pytest.mark.parametrize("cfg", EVAL_CONVS)
 def test_eval_conv_bn_fused_in_gemm_epilogue(dtn, cfg, monkeypatch):
     """Eval-mode conv + BatchNorm (+ ReLU / ReLU6) (+ residual) in ONE launch (pn2_conv_gemm_affine, MyTest_med.py:98-104) against the two-launch path
@@ -112,9 +113,10 @@ def test_eval_conv_bn_fused_in_gemm_epilogue(dtn, cfg, monkeypatch):
     (one rounding fewer; with a residual: the same two roundings at other places, within 1.25 x).  Covers group-padded outputs (26 channels in 32 slots), partial last tiles, stride 2, a 5x5 and the split between pre- and post-residual
     activation."""
     from pn2 import F32, BF16
+    from pn2.capi import F32F
     from pn2 import engine as E, core
     N, Cin, Cout, k, stride, pad, H, Wd, relu, use_res, omap = cfg
-    dt = F32 if dtn == "fp32" else BF16
+    dt = {"fp32": F32, "fp32fast": F32F, "bf16": BF16}[dtn]
     torch.manual_seed(2)
     conv = nn.Conv2d(Cin, Cout, k, stride, pad, bias=False).to(dev)
     bnm = nn.BatchNorm2d(Cout).to(dev).eval()
@@ -132,14 +134,14 @@ def test_eval_conv_bn_fused_in_gemm_epilogue(dtn, cfg, monkeypatch):
         torch.cuda.synchronize()
         return eng.to_nchw(y).clone(), y.t.clone()
     (y1, t1), (y0, t0) = run(True), run(False)
-    xr = x if dt == F32 else x.bfloat16().float()
-    wr = conv.weight.detach() if dt == F32 else conv.weight.detach().bfloat16().float()
+    xr = x if dt != BF16 else x.bfloat16().float()
+    wr = conv.weight.detach() if dt != BF16 else conv.weight.detach().bfloat16().float()
     ref = F.batch_norm(F.conv2d(xr.double().cpu(), wr.double().cpu(), None, stride, pad), bnm.running_mean.double().cpu(), bnm.running_var.double().cpu(),
                        bnm.weight.detach().double().cpu(), bnm.bias.detach().double().cpu(), False, 0.1, 1e-5)
     if use_res:
-        ref = ref + (res if dt == F32 else res.bfloat16().float()).double().cpu()
+        ref = ref + (res if dt != BF16 else res.bfloat16().float()).double().cpu()
     ref = F.relu6(ref) if relu == 2 else (F.relu(ref) if relu else ref)
-    if dt == F32:
+    if dt != BF16:
         assert torch.equal(t1, t0)                     # same fma on the same correctly rounded conv result
         assert relmax(y1, ref) < 3e-5
     else:
@@ -150,16 +152,17 @@ def test_eval_conv_bn_fused_in_gemm_epilogue(dtn, cfg, monkeypatch):
             assert float(t1[..., Cout:].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("dtn", ["fp32", "bf16"])
+@pytest.mark.parametrize("dtn", ["fp32", "fp32fast", "bf16"])
 def test_reverse_attention_gate_in_gemm_epilogue(dtn):
     """V1 reverse attention (PraNet_Res2Net.py:153-155): ra_conv1((1 - sigmoid(crop)).expand(C) * x_l) with a 1x1 ra_conv1 + train-mode BN.  The fused
     path scales the GEMM's accumulator rows (pn2_conv_gemm_gated) and never writes the gated copy of x_l; outputs and all four gradients (x_l, crop,
     conv weight, BN affine) against torch float64 autograd, and against the engine's own materialising path (pn2_ra_gate_fwd / _bwd)."""
     from pn2 import F32, BF16
+    from pn2.capi import F32F
     from pn2.engine import Engine, Act
     from pn2.graph import _seed_grad
-    dt = F32 if dtn == "fp32" else BF16
-    err, tol = (relmax, 5e-5) if dt == F32 else (rell2, 3e-2)
+    dt = {"fp32": F32, "fp32fast": F32F, "bf16": BF16}[dtn]
+    err, tol = (relmax, 5e-5) if dt != BF16 else (rell2, 3e-2)
     torch.manual_seed(11)
     N, H, Wd, Cin, Cout = 3, 11, 13, 136, 64
     conv = nn.Conv2d(Cin, Cout, 1, bias=False).to(dev); bnm = nn.BatchNorm2d(Cout).to(dev)
@@ -192,16 +195,16 @@ def test_reverse_attention_gate_in_gemm_epilogue(dtn):
     for i_, (g_, r_) in enumerate(zip(grads, ref)):
         if float(r_.abs().max()) > 1e-9:
             assert err(g_, r_) < tol, (i_, err(g_, r_))
-    assert relmax(bnm.running_var, br.running_var) < (1e-5 if dt == F32 else 2e-2)
+    assert relmax(bnm.running_var, br.running_var) < (1e-5 if dt != BF16 else 2e-2)
     bnm.running_mean.copy_(rm0); bnm.running_var.copy_(rv0)
     out0, grads0 = run(False)
-    assert err(out, out0) < (1e-5 if dt == F32 else 2e-2)
+    assert err(out, out0) < (1e-5 if dt != BF16 else 2e-2)
     for g_, g0 in zip(grads, grads0):
         if float(g0.abs().max()) > 1e-9:
-            assert err(g_, g0) < (2e-5 if dt == F32 else 3e-2)
+            assert err(g_, g0) < (2e-5 if dt != BF16 else 3e-2)
 
 
-@pytest.mark.parametrize("dtn", ["fp32", "bf16"])
+@pytest.mark.parametrize("dtn", ["fp32", "fp32fast", "bf16"])
 @pytest.mark.parametrize("case", ["chain", "residual", "big_mean"])
 def test_bn_backward_statistics_in_dgrad_epilogue(dtn, case, monkeypatch):
     """conv -> BN -> ReLU -> conv -> BN [-> + residual -> ReLU -> conv]: with x_last=True the second (third) conv's dgrad GEMM takes the
@@ -209,11 +212,12 @@ def test_bn_backward_statistics_in_dgrad_epilogue(dtn, case, monkeypatch):
     torch float64 autograd, and - in fp32 - as the engine's own reduce-pass path.  big_mean: |mean| >> sigma channels (the Chan-merged
     forward statistics must not cancel)."""
     from pn2 import F32, BF16, engine, core
+    from pn2.capi import F32F
     from pn2.engine import Engine
     from pn2.graph import _seed_grad
     from pn2 import capi
-    dt = F32 if dtn == "fp32" else BF16
-    err, tol = (relmax, 5e-5) if dt == F32 else (rell2, 1e-1)         # bf16: three BatchNorm layers deep
+    dt = {"fp32": F32, "fp32fast": F32F, "bf16": BF16}[dtn]
+    err, tol = (relmax, 5e-5) if dt != BF16 else (rell2, 1e-1)         # bf16: three BatchNorm layers deep
     torch.manual_seed(5)
     N, H, Wd, C0, C1, C2 = 3, 13, 17, 24, 40, 56
     c1 = nn.Conv2d(C0, C1, 3, 1, 1, bias=False).to(dev); b1 = nn.BatchNorm2d(C1).to(dev)
@@ -275,7 +279,7 @@ def test_bn_backward_statistics_in_dgrad_epilogue(dtn, case, monkeypatch):
     assert n0 == 0
     for g_, r_, f_ in zip(grads, grads0, ref):
         if float(f_.abs().max()) > 1e-9:
-            if dt == F32:
+            if dt != BF16:
                 assert relmax(g_, r_) < (2e-5 if case != "big_mean" else 2e-3)
             else:
                 assert rell2(g_, r_) < 3e-2
@@ -493,7 +497,7 @@ def _fixture_model(fp32=True):
     import pn2
     from lib.pranet import PraNet_V2
     from oracle import weights as W
-    pn2.set_compute_dtype("fp32" if fp32 else "bf16")
+    pn2.set_compute_dtype(fp32 if isinstance(fp32, str) else ("fp32" if fp32 else "bf16"))          # (or a mode name: "fp32fast")
     model = PraNet_V2(num_class=1)
     model.load_state_dict(W.make_state_dict(W.manifest_pranet_v2(1), seed=0), strict=True)
     return model.to(dev).train()
@@ -893,7 +897,7 @@ def test_lr_schedule_reaches_captured_graph():
     assert torch.equal(tr.flat, p2)
 
 
-@pytest.mark.parametrize("fp32", [False, True])
+@pytest.mark.parametrize("fp32", [False, True, "fp32fast"])
 def test_table_driven_launches_match_single_launches(fp32, monkeypatch):
     """pn2_conv_wgrad_multi / pn2_wgrad_reduce_multi over the step arena == one pn2_conv_wgrad + pn2_wgrad_reduce per conv, bit for bit."""
     from pn2 import core
@@ -917,7 +921,7 @@ def test_table_driven_launches_match_single_launches(fp32, monkeypatch):
         assert torch.equal(res[0][0], other[0]) and torch.equal(res[0][1], other[1])
 
 
-@pytest.mark.parametrize("fp32", [False, True])
+@pytest.mark.parametrize("fp32", [False, True, "fp32fast"])
 @pytest.mark.parametrize("size", [96, 224])
 def test_lockstep_launches_match_plain_launches(fp32, size, monkeypatch):
     """Engine.lockstep (pn2/lockstep.py): the three RFB modules and their branch tails, and the three parallel 3x3 convs of every Res2Net stage
@@ -1226,7 +1230,7 @@ def test_predictor_graphs_survive_a_growing_job_table():
     del junk
 
 
-@pytest.mark.parametrize("fp32", [False, True])
+@pytest.mark.parametrize("fp32", [False, True, "fp32fast"])
 def test_stem_bn_relu_maxpool_as_one_op(fp32, monkeypatch):
     """conv_bn_act(pool=True): the stem's bn1 -> ReLU -> MaxPool2d(3, 2, 1) (Res2Net_v1b.py:137-139) without the full-resolution BatchNorm output.  Forward
     (pn2_bn_relu_maxpool_fwd): pooled activation and argmax bytes straight from the raw conv output - every value formed as the separate normalise and pool passes form
@@ -1251,7 +1255,7 @@ def test_stem_bn_relu_maxpool_as_one_op(fp32, monkeypatch):
             assert torch.equal(res["sep"][0], res[name][0]) and torch.equal(res["sep"][2], res[name][2]), name
         assert torch.equal(res["sep"][1], res["fwd"][1]), float((res["sep"][1] - res["fwd"][1]).abs().max())
         rel = float((res["sep"][1] - res["quad"][1]).norm() / res["sep"][1].norm())
-        print(f"\nstem pool quad backward vs separate ops, {'fp32' if fp32 else 'bf16'} {size}^2: gradient rel-L2 {rel:.2e}")
+        print(f"\nstem pool quad backward vs separate ops, {fp32 if isinstance(fp32, str) else ('fp32' if fp32 else 'bf16')} {size}^2: gradient rel-L2 {rel:.2e}")
         # bf16: a handful of dz roundings flip with the last bit of the stem's coefficients and the net amplifies them: 5e-8 ... 8e-5 observed over runs of the same
         # code (which flips occur depends on the tiles / pixel splits the tuner timed fastest in that process); the bf16 gradient noise itself is ~1e-2
         assert rel <= (2e-7 if fp32 else 1e-3), rel
