@@ -11,7 +11,11 @@
  *   - dtype: PN2_F32 (fp32 parity path: fp32 storage, conv products and sums in double on v_mfma_f64_16x16x4_f64, one rounding per output)
  *     or PN2_BF16 (bf16 storage, v_mfma_f32_16x16x32_bf16, f32 accumulate); the conv contraction entry points - pn2_conv_gemm, _ep, _gated, _affine,
  *     _multi, _tile, _job_blocks, pn2_conv_wgrad, _multi, _variant, pn2_conv_tile_m and pn2_conv_stat_blocks - also take PN2_F32F ("fp32fast":
- *     fp32 storage like PN2_F32, fp32 products and sums on v_mfma_f32_16x16x4_f32); every other entry point takes PN2_F32 for fp32fast tensors;
+ *     fp32 storage like PN2_F32, fp32 products and sums on v_mfma_f32_16x16x4_f32) and PN2_F32X3 ("fp32x3": fp32 storage, every operand split into
+ *     three bf16 terms x = h + m + l when it is staged into LDS, six of the nine cross products - hh, hm, mh, hl, lh, mm - on v_mfma_f32_16x16x32_bf16,
+ *     exact products, fp32 sums; the three dropped terms are of fp32 rounding size).  fp32x3 edge cases: a NaN operand gives NaN; an infinite operand
+ *     gives NaN (inf - inf appears in the split); |x| above the largest bf16 rounds h to inf, and the result is NaN too.  Every other entry point takes
+ *     PN2_F32 for fp32fast / fp32x3 tensors and returns -3 for PN2_F32F / PN2_F32X3;
  *   - every call is asynchronous on `stream` (a hipStream_t); returns 0 on success, <0 for argument
  *     errors (-1 null pointer, -2 unsupported geometry/alignment, -3 unknown dtype), >0 = hipError_t;
  *   - no global state; safe to call from any thread / any stream; graph-capture safe (no sync, no malloc).
@@ -25,6 +29,7 @@ extern "C" {
 #define PN2_F32 0
 #define PN2_BF16 1
 #define PN2_F32F 2         /* conv contraction entry points only (see dtype above) */
+#define PN2_F32X3 3        /* conv contraction entry points only (see dtype above) */
 #define PN2_CONV_STATS 1   /* emit per-channel sum / sum-of-squares partials (fused BN batch statistics) */
 #define PN2_CONV_ACCUM 2   /* out += result (gradient accumulation) */
 #define PN2_CONV_SPLITK(n) ((n) << 16)   /* bf16 LDS-DMA kernels only (tuning code kernel 2 / 3): n = 2..15 workgroups share the K loop of a tile and
@@ -49,7 +54,7 @@ typedef struct pn2_conv_desc {
     int transposed;         /* 0 forward gather, 1 dgrad gather */
     int Kp;                 /* packed-weight row length, multiple of 128 */
     int flags;              /* PN2_CONV_* ; bits 8..15 optional tuning code: kernel | BM<<2 | BN<<4, see pn2_conv_tile_m.  PN2_BF16 takes
-                               all of it; PN2_F32F takes the BM / BN bits only (register-staged kernel, BN 128 clamped to 64); PN2_F32 ignores it */
+                               all of it; PN2_F32F and PN2_F32X3 take the BM / BN bits only (register-staged kernel, BN 128 clamped to 64); PN2_F32 ignores it */
 } pn2_conv_desc;
 
 typedef struct pn2_wgrad_desc {

@@ -4,7 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/pn2.h"          // PN2_F32 / PN2_BF16 / PN2_F32F
+#include "../../include/pn2.h"          // PN2_F32 / PN2_BF16 / PN2_F32F / PN2_F32X3
 
 typedef unsigned short bf16_t;   // storage type; arithmetic always in f32
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
@@ -14,6 +14,8 @@ typedef __attribute__((ext_vector_type(4))) double f64x4_t;
 
 // storage type of PN2_F32F: a float under another name, so that the conv kernels (templated on the storage type) pick another MFMA form for it
 struct f32f_t { float v; };
+// storage type of PN2_F32X3: fp32 storage again; the conv kernels split the operands into bf16 terms (MMA<f32x3_t> in pn2_conv.hip)
+struct f32x3_t { float v; };
 
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((unsigned)h) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {           // round-to-nearest-even, gfx950 hardware convert
@@ -40,6 +42,11 @@ template <> struct TT<f32f_t> : TT<float> {
     static constexpr int DT = PN2_F32F;
     __device__ static __forceinline__ float ld(const f32f_t* p) { return p->v; }
     __device__ static __forceinline__ void st(f32f_t* p, float v) { p->v = v; }
+};
+template <> struct TT<f32x3_t> : TT<float> {
+    static constexpr int DT = PN2_F32X3;
+    __device__ static __forceinline__ float ld(const f32x3_t* p) { return p->v; }
+    __device__ static __forceinline__ void st(f32x3_t* p, float v) { p->v = v; }
 };
 template <> struct TT<bf16_t> {
     static constexpr int VEC = 8;

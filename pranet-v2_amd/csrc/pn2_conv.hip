@@ -128,6 +128,64 @@ template <> struct MMA<f32f_t> {
             for (int j = 0; j < NT; ++j) acc[i][j] += t[i][j];
     }
 };
+// PN2_F32X3 ("fp32x3"): fp32 storage and fp32-grade contractions on the bf16 matrix pipe.  Every operand is split ONCE PER WORKGROUP, where the gather kernel
+// moves it from registers into LDS (split3 below), into bf16 terms x = h + m + l (exact for finite normal x; |m| <= 2^-8 |x|, |l| <= 2^-16 |x|); the LDS stage
+// holds an [h(4) m(4)] plane in the fp32 tile's place and swizzle (same 16-byte reads) and an l(4) plane of 8-byte slots.  A and B share the (lane group, slot)
+// -> k mapping, so the eight bf16 slots of a lane carry two terms of the same four k-values, and three v_mfma_f32_16x16x32_bf16 per 16-deep sub-step take six
+// of the nine cross products: [h m].[h m] = hh + mm, [h m].[m h] = hm + mh, [h l].[l h] = hl + lh (ml, lm, ll: ~2 * 2^-24 |a||b| together, dropped).  bf16 x bf16
+// products are exact in fp32; like MMA<f32f_t>, the three MFMAs of a sub-step start from C = 0 and meet the accumulator in a round-to-nearest add.
+template <> struct MMA<f32x3_t> {
+    static constexpr int BK = 16 * KSUB;
+    static constexpr bool F64ROWS = false, DEEP = true;
+    typedef f32x4_t acc_t;
+    __device__ static __forceinline__ int arow(int l15) { return l15; }
+    __device__ static __forceinline__ f32x4_t mfma(const uint4& a, const uint4& b, const f32x4_t& c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+    }
+    // a = [h(4) m(4)] and la = l(4) of an A fragment, b / lb of a B fragment; k-major over the MT x NT blocks (independent chains back to back, see MMA<f32f_t>)
+    template <int MT, int NT> __device__ static __forceinline__ void run_block(acc_t (&acc)[MT][NT], const uint4 (&a)[MT], const uint2 (&la)[MT], const uint4 (&b)[NT], const uint2 (&lb)[NT]) {
+        uint4 ahl[MT], bmh[NT], blh[NT];
+#pragma unroll
+        for (int i = 0; i < MT; ++i) ahl[i] = make_uint4(a[i].x, a[i].y, la[i].x, la[i].y);          // [h l]
+#pragma unroll
+        for (int j = 0; j < NT; ++j) { bmh[j] = make_uint4(b[j].z, b[j].w, b[j].x, b[j].y); blh[j] = make_uint4(lb[j].x, lb[j].y, b[j].x, b[j].y); }      // [m h], [l h]
+        f32x4_t t[MT][NT];
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) t[i][j] = mfma(a[i], b[j], f32x4_t{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) t[i][j] = mfma(a[i], bmh[j], t[i][j]);
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) t[i][j] = mfma(ahl[i], blh[j], t[i][j]);
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[i][j] += t[i][j];
+    }
+};
+template <typename T> constexpr bool X3 = false;          // PN2_F32X3 instantiations: split operands in LDS
+template <> constexpr bool X3<f32x3_t> = true;
+template <typename T> constexpr int lo_row = 0;           // bytes per LDS row of the gather kernels' l plane
+template <> constexpr int lo_row<f32x3_t> = 64;
+
+// four fp32 values -> bf16 terms: hm = [h0..h3 m0..m3], lo = [l0..l3] (packed pairs, element 0 in the low half).  h = bf16(x), r = x - h (exact), m = bf16(r),
+// l = bf16(r - m) (exact): x == h + m + l for finite normal x.  NaN stays NaN; inf, and |x| above the largest bf16 (h = inf), give NaN terms (inf - inf).
+__device__ __forceinline__ void split3(const uint4& v, uint4& hm, uint2& lo) {
+    const float x0 = __uint_as_float(v.x), x1 = __uint_as_float(v.y), x2 = __uint_as_float(v.z), x3 = __uint_as_float(v.w);
+    const unsigned h01 = TT<bf16_t>::cvt2(x0, x1), h23 = TT<bf16_t>::cvt2(x2, x3);
+    const float r0 = x0 - __uint_as_float(h01 << 16), r1 = x1 - __uint_as_float(h01 & 0xffff0000u);
+    const float r2 = x2 - __uint_as_float(h23 << 16), r3 = x3 - __uint_as_float(h23 & 0xffff0000u);
+    const unsigned m01 = TT<bf16_t>::cvt2(r0, r1), m23 = TT<bf16_t>::cvt2(r2, r3);
+    const float s0 = r0 - __uint_as_float(m01 << 16), s1 = r1 - __uint_as_float(m01 & 0xffff0000u);
+    const float s2 = r2 - __uint_as_float(m23 << 16), s3 = r3 - __uint_as_float(m23 & 0xffff0000u);
+    hm = make_uint4(h01, h23, m01, m23);
+    lo = make_uint2(TT<bf16_t>::cvt2(s0, s1), TT<bf16_t>::cvt2(s2, s3));
+}
 
 
 // 16 channels x 32 rows of a row-major bf16 tile in LDS as an MFMA operand (lane: channel l15, k-slots (g, e) <-> row (e>>2)*16 + g*4 + (e&3)):
@@ -969,6 +1027,18 @@ __device__ __forceinline__ void conv_epilogue(f32x4_t (&acc)[MT][NT], char* smem
     }
 }
 
+// fp32x3 stage layout of the gather kernels: [h m] rows exactly where the fp32 rows are (RS bytes, 16-byte slot kv ^ (row & 7)), then the l plane of all
+// BM + BN rows, 64 bytes per row, 8-byte slot kv ^ (((row >> 2) & 3) << 1) - the sixteen rows x two lane groups of a half-wave read distinct bank pairs
+__device__ __forceinline__ int x3_lo_off(int row, int slot) { return row * 64 + ((slot ^ (((row >> 2) & 3) << 1)) << 3); }
+// split one staged vector (this thread's k-slot tid & 7) and write its [h m] part to row `row` of the A or B rows at `hm_rows`, its l part to row `lrow` of the l plane
+__device__ __forceinline__ void x3_store(char* hm_rows, int row, char* lo, int lrow, const u32x4_t_& v) {
+    uint4 hm; uint2 l;
+    split3(__builtin_bit_cast(uint4, v), hm, l);
+    const int kv = threadIdx.x & 7;
+    *reinterpret_cast<uint4*>(hm_rows + row * RS + ((kv ^ (row & 7)) << 4)) = hm;
+    *reinterpret_cast<uint2*>(lo + x3_lo_off(lrow, kv)) = l;
+}
+
 // ------------------------------------------------------------------------------------------------
 // forward / dgrad gather-GEMM
 // ------------------------------------------------------------------------------------------------
@@ -977,7 +1047,8 @@ __device__ __forceinline__ void conv_gather_body(const T* __restrict__ in, const
                                                  float* __restrict__ psum, float* __restrict__ psq, const pn2_conv_desc& d, const pn2_conv_ep& ep, int lbid, int lgrid) {
     constexpr int VEC = TT<T>::VEC, BK = MMA<T>::BK;
     constexpr int WTM = BM / WM, WTN = BN / WN, MT = WTM / 16, NT = WTN / 16;
-    constexpr int STAGE = (BM + BN) * RS;
+    constexpr int LR = lo_row<T>;                  // fp32x3: an l plane of LR-byte rows behind the [h m] rows (A then B)
+    constexpr int STAGE = (BM + BN) * (RS + LR);
     constexpr int NA = BM / 32, NB = BN / 32;     // 16-byte vectors per thread per step (8 vectors per 128-byte row)
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -1029,7 +1100,11 @@ __device__ __forceinline__ void conv_gather_body(const T* __restrict__ in, const
     // the weight-panel vectors by literal index: with two register sets (DEEP) hipcc left an `unroll`-ed loop over RB_[i] as a loop and the arrays in scratch
 #define PN2_U4(N_, M_, X_, Y_) do { if constexpr ((N_) > 0) { M_(0, X_, Y_); } if constexpr ((N_) > 1) { M_(1, X_, Y_); } if constexpr ((N_) > 2) { M_(2, X_, Y_); } if constexpr ((N_) > 3) { M_(3, X_, Y_); } } while (0)
 #define PN2_GLOAD_B(i_, RB_, step_) RB_[i_] = *reinterpret_cast<const u32x4_t_*>(bptr + (size_t)(32 * (i_)) * d.Kp + (size_t)(step_) * BK)
-#define PN2_LSTORE_B(i_, RB_, Bs_) *reinterpret_cast<u32x4_t_*>(Bs_ + ((tid >> 3) + 32 * (i_)) * RS + wslot) = RB_[i_]
+#define PN2_LSTORE_B(i_, RB_, Bs_)                                                                                     \
+    do {                                                                                                               \
+        if constexpr (X3<T>) x3_store(Bs_, (tid >> 3) + 32 * (i_), Bs_ + BN * RS, BM + (tid >> 3) + 32 * (i_), RB_[i_]); \
+        else *reinterpret_cast<u32x4_t_*>(Bs_ + ((tid >> 3) + 32 * (i_)) * RS + wslot) = RB_[i_];                      \
+    } while (0)
 #define PN2_GLOAD(step_, RA_, RB_, AM_)                                                                                \
     do {                                                                                                               \
         AM_ = 0;                                                                                                       \
@@ -1063,7 +1138,8 @@ __device__ __forceinline__ void conv_gather_body(const T* __restrict__ in, const
         char* Bs_ = As_ + BM * RS;                                                                                     \
         _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                                               \
             const u32x4_t_ v_ = (AM_ >> i) & 1u ? RA_[i] : u32x4_t_{0u, 0u, 0u, 0u};                                   \
-            *reinterpret_cast<u32x4_t_*>(As_ + ((tid >> 3) + 32 * i) * RS + wslot) = v_;                               \
+            if constexpr (X3<T>) x3_store(As_, (tid >> 3) + 32 * i, As_ + (BM + BN) * RS, (tid >> 3) + 32 * i, v_);          \
+            else *reinterpret_cast<u32x4_t_*>(As_ + ((tid >> 3) + 32 * i) * RS + wslot) = v_;                          \
         }                                                                                                              \
         PN2_U4(NB, PN2_LSTORE_B, RB_, Bs_);                                                                            \
     } while (0)
@@ -1075,7 +1151,15 @@ __device__ __forceinline__ void conv_gather_body(const T* __restrict__ in, const
             uint4 a[MT], b[NT];                                                                                        \
             _Pragma("unroll") for (int i = 0; i < MT; ++i) a[i] = *reinterpret_cast<const uint4*>(As + (wm * WTM + i * 16 + l15a) * RS + (((ks * 4 + g) ^ (l15a & 7)) << 4)); \
             _Pragma("unroll") for (int j = 0; j < NT; ++j) b[j] = *reinterpret_cast<const uint4*>(Bs + (wn * WTN + j * 16 + l15) * RS + (((ks * 4 + g) ^ (l15 & 7)) << 4));  \
-            MMA<T>::template run_block<MT, NT>(acc, a, b);                                                             \
+            if constexpr (X3<T>) {                                                                                     \
+                const char* Ls = As + (BM + BN) * RS;                                                                  \
+                uint2 la[MT], lb[NT];                                                                                  \
+                _Pragma("unroll") for (int i = 0; i < MT; ++i) la[i] = *reinterpret_cast<const uint2*>(Ls + x3_lo_off(wm * WTM + i * 16 + l15, ks * 4 + g)); \
+                _Pragma("unroll") for (int j = 0; j < NT; ++j) lb[j] = *reinterpret_cast<const uint2*>(Ls + x3_lo_off(BM + wn * WTN + j * 16 + l15, ks * 4 + g)); \
+                MMA<T>::template run_block<MT, NT>(acc, a, la, b, lb);                                                 \
+            } else {                                                                                                   \
+                MMA<T>::template run_block<MT, NT>(acc, a, b);                                                         \
+            }                                                                                                          \
         }                                                                                                              \
     } while (0)
 
@@ -1475,6 +1559,22 @@ template <> struct WG<float> {
     static constexpr int NFRAG = 2;  // two uint4 = 8 pixels-slots per lane per 32-pixel step
 };
 template <> struct WG<f32f_t> : WG<float> {};
+// fp32x3: h / m / l bf16 planes [pixel][channel] per operand (split at the LDS store), read like bf16 with ds_read_b64_tr_b16 - 4 pixels per read,
+// so a 16-pixel sub-step is three MFMAs (MMA<f32x3_t>) instead of four 4-pixel f32 MFMAs
+template <> struct WG<f32x3_t> {
+    static constexpr int PAD = 32;   // of a bf16 plane row (as WG<bf16_t>)
+    static constexpr int NFRAG = 1;
+};
+// LDS bytes of one wgrad stage (WGP pixel rows of both operands)
+template <typename T> constexpr int wg_stage_bytes(int bmc, int bnk) {
+    return X3<T> ? 3 * WGP * (bmc * 2 + WG<T>::PAD + bnk * 2 + WG<T>::PAD) : WGP * (bmc * (int)sizeof(T) + WG<T>::PAD + bnk * (int)sizeof(T) + WG<T>::PAD);
+}
+// one 4-pixel x 16-channel bf16 fragment (lane: channel l15, slot e <-> pixel g*4 + e): the first half of tr_frag_bf16
+__device__ __forceinline__ uint2 tr4_bf16(const char* tile, int rs, int chan0, int lane) {
+    const int g = lane >> 4, i = lane & 15;
+    const char* p = tile + (g * 4 + (i >> 2)) * rs + (chan0 + (i & 3) * 4) * 2;
+    return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t_ __attribute__((address_space(3)))*)(p)));
+}
 
 template <typename T, int BMC, int BNK, int WM, int WN, bool PW>
 __device__ __forceinline__ void conv_wgrad_body(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ slab, const pn2_wgrad_desc& d, int nsplit, int bloc) {
@@ -1482,8 +1582,10 @@ __device__ __forceinline__ void conv_wgrad_body(const T* __restrict__ dy, const 
     // at a multiple of 8 so that bloc % 8 is still the XCD the block runs on)
     constexpr int VEC = TT<T>::VEC;
     constexpr int WTM = BMC / WM, WTN = BNK / WN, MT = WTM / 16, NT = WTN / 16;
-    constexpr int RSY = BMC * (int)sizeof(T) + WG<T>::PAD, RSX = BNK * (int)sizeof(T) + WG<T>::PAD;
-    constexpr int STAGE = WGP * (RSY + RSX);
+    constexpr int ES = X3<T> ? 2 : (int)sizeof(T), NPL = X3<T> ? 3 : 1;          // bytes per element of an LDS row, planes per operand (fp32x3: h, m, l in bf16)
+    constexpr int RSY = BMC * ES + WG<T>::PAD, RSX = BNK * ES + WG<T>::PAD;
+    constexpr int STAGE = NPL * WGP * (RSY + RSX);
+    static_assert(STAGE == wg_stage_bytes<T>(BMC, BNK), "launch and kernel disagree on the stage size");
     constexpr int VPRY = BMC / VEC, VPRX = BNK / VEC;
     constexpr int NY = (WGP * VPRY + 255) / 256, NX = (WGP * VPRX + 255) / 256;
     constexpr int RSTEPY = 256 / VPRY > WGP ? WGP : 256 / VPRY;   // rows covered per pass
@@ -1565,7 +1667,22 @@ __device__ __forceinline__ void conv_wgrad_body(const T* __restrict__ dy, const 
     };
     auto lstore = [&](int stage) {
         char* Ys = smem + stage * STAGE;
-        char* Xs = Ys + WGP * RSY;
+        char* Xs = Ys + NPL * WGP * RSY;
+        if constexpr (X3<T>) {          // the split, once per element and workgroup: h / m / l planes, four channels (8 bytes) per thread and plane
+            auto put = [](char* p, int plane, const uint4& v) {
+                uint4 hm; uint2 lo;
+                split3(v, hm, lo);
+                *reinterpret_cast<uint2*>(p) = make_uint2(hm.x, hm.y);
+                *reinterpret_cast<uint2*>(p + plane) = make_uint2(hm.z, hm.w);
+                *reinterpret_cast<uint2*>(p + 2 * plane) = lo;
+            };
+#pragma unroll
+            for (int i = 0; i < NY; ++i)
+                if (y_active) put(Ys + (yrow + i * RSTEPY) * RSY + ycv * 8, WGP * RSY, (ymask >> i) & 1u ? ry[i] : make_uint4(0, 0, 0, 0));
+#pragma unroll
+            for (int i = 0; i < NX; ++i) put(Xs + (xrow + i * RSTEPX) * RSX + xkv * 8, WGP * RSX, (xmask >> i) & 1u ? rx[i] : make_uint4(0, 0, 0, 0));
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < NY; ++i)
             if (y_active) *reinterpret_cast<uint4*>(Ys + (yrow + i * RSTEPY) * RSY + ycv * 16) = (ymask >> i) & 1u ? ry[i] : make_uint4(0, 0, 0, 0);
@@ -1587,8 +1704,46 @@ __device__ __forceinline__ void conv_wgrad_body(const T* __restrict__ dy, const 
             const int cur = (step - s_begin) & 1;
             gload(step + 1, step + 1 < s_end);      // branch-free prefetch: the last one is dead (all lanes masked, address clamped)
             const char* Ys = smem + cur * STAGE;
-            const char* Xs = Ys + WGP * RSY;
-            if constexpr (sizeof(T) == 2) {
+            const char* Xs = Ys + NPL * WGP * RSY;
+            if constexpr (X3<T>) {
+                // 16 pixels per sub-step (lane: 4 pixels g*4..g*4+3 per read), three MFMAs per block (MMA<f32x3_t>); one chain per 32-pixel stage from C = 0,
+                // added to acc round-to-nearest at the stage's end (as fp32fast's WCH = 8 chains)
+                f32x4_t part[MT][NT];
+#pragma unroll
+                for (int q = 0; q < WGP / 16; ++q) {
+                    uint4 a[MT], ahl[MT], b[NT], bmh[NT], blh[NT];
+#pragma unroll
+                    for (int i = 0; i < MT; ++i) {
+                        const char* t = Ys + q * 16 * RSY;
+                        const int c0 = wm * WTM + i * 16;
+                        const uint2 h = tr4_bf16(t, RSY, c0, lane), m = tr4_bf16(t + WGP * RSY, RSY, c0, lane), l = tr4_bf16(t + 2 * WGP * RSY, RSY, c0, lane);
+                        a[i] = make_uint4(h.x, h.y, m.x, m.y); ahl[i] = make_uint4(h.x, h.y, l.x, l.y);
+                    }
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) {
+                        const char* t = Xs + q * 16 * RSX;
+                        const int c0 = wn * WTN + j * 16;
+                        const uint2 h = tr4_bf16(t, RSX, c0, lane), m = tr4_bf16(t + WGP * RSX, RSX, c0, lane), l = tr4_bf16(t + 2 * WGP * RSX, RSX, c0, lane);
+                        b[j] = make_uint4(h.x, h.y, m.x, m.y); bmh[j] = make_uint4(m.x, m.y, h.x, h.y); blh[j] = make_uint4(l.x, l.y, h.x, h.y);
+                    }
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) part[i][j] = MMA<f32x3_t>::mfma(a[i], b[j], q == 0 ? f32x4_t{0.f, 0.f, 0.f, 0.f} : part[i][j]);
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) part[i][j] = MMA<f32x3_t>::mfma(a[i], bmh[j], part[i][j]);
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) part[i][j] = MMA<f32x3_t>::mfma(ahl[i], blh[j], part[i][j]);
+                }
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) acc[i][j] += part[i][j];
+            } else if constexpr (sizeof(T) == 2) {
                 uint4 a[MT], b[NT];
 #pragma unroll
                 for (int i = 0; i < MT; ++i) a[i] = WG<bf16_t>::frag(Ys, RSY, wm * WTM + i * 16, lane);
@@ -2053,7 +2208,7 @@ template <typename T, int BM, int BN, int WM, int WN, bool EP>
 int launch_gemm(const void* in, const void* wp, void* out, float* psum, float* psq, const pn2_conv_desc& d, const pn2_conv_ep& ep, hipStream_t st) {
     const int M = d.N * d.OH * d.OW;
     const int grid = ((M + BM - 1) / BM) * ((d.Cout + BN - 1) / BN);
-    constexpr int main_b = 2 * (BM + BN) * RS, epi_b = BM * (BN * (int)sizeof(T) + 16) + 3 * WM * BN * 4;
+    constexpr int main_b = 2 * (BM + BN) * (RS + lo_row<T>), epi_b = BM * (BN * (int)sizeof(T) + 16) + 3 * WM * BN * 4;
     constexpr bool E2 = EP && sizeof(T) == 2 && ep2_tile(BM, BN);
     constexpr int ep_b = (EP && !E2) ? ep_lds_bytes(TT<T>::VEC) : 0;
     constexpr int lds0 = (main_b > epi_b ? main_b : epi_b) > ep_b ? (main_b > epi_b ? main_b : epi_b) : ep_b;
@@ -2153,9 +2308,17 @@ inline void pick_tiles(int M, int cout, bool f32, int& bm, int& bn) {
 template <typename T, int BMC, int WM, int WN>
 int launch_wgrad(const void* dy, const void* x, float* slab, const pn2_wgrad_desc& d, int nsplit, hipStream_t st) {
     constexpr int BNK = 128;
-    constexpr int lds = 2 * WGP * (BMC * (int)sizeof(T) + WG<T>::PAD + BNK * (int)sizeof(T) + WG<T>::PAD);
+    constexpr int lds = 2 * wg_stage_bytes<T>(BMC, BNK);
     dim3 grid(8 * ((nsplit + 7) / 8) * (d.Rp / BMC) * (d.Kp / BNK));
     const bool pw = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0;
+    if constexpr (X3<T>) {          // (fp32x3: 74-111 KB, above the default 64 KB cap)
+        static bool done = false;
+        if (!done) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad<T, BMC, BNK, WM, WN, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad<T, BMC, BNK, WM, WN, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            done = true;
+        }
+    }
     if (pw) hipLaunchKernelGGL((conv_wgrad<T, BMC, BNK, WM, WN, true>), grid, dim3(256), lds, st, (const T*)dy, (const T*)x, slab, d, nsplit);
     else hipLaunchKernelGGL((conv_wgrad<T, BMC, BNK, WM, WN, false>), grid, dim3(256), lds, st, (const T*)dy, (const T*)x, slab, d, nsplit);
     PN2_CHECK_LAUNCH();
@@ -2167,7 +2330,7 @@ int launch_wgrad(const void* dy, const void* x, float* slab, const pn2_wgrad_des
 template <typename T>
 void gemm_select(const pn2_conv_desc& d, int& kern, int& bm, int& bn) {
     pick_tiles(d.N * d.OH * d.OW, d.Cout, sizeof(T) == 4, bm, bn);
-    const int tune = (sizeof(T) == 2 || !MMA<T>::F64ROWS) ? (d.flags >> 8) & 0xff : 0;          // (fp32fast takes the tile bits of a tuning code; its kernel is always the register-staged one)
+    const int tune = (sizeof(T) == 2 || !MMA<T>::F64ROWS) ? (d.flags >> 8) & 0xff : 0;          // (fp32fast / fp32x3 take the tile bits of a tuning code; their kernel is always the register-staged one)
     const int tk_ = dma_extent_ok(d) ? (tune & 3) : 1, tbm = (tune >> 2) & 3, tbn = (tune >> 4) & 3;     // > 2 GB operand: register-staged kernel (64-bit addresses)
     if (tbm) bm = tbm == 1 ? 64 : 128;
     if (tbn) bn = tbn == 1 ? 32 : (tbn == 2 ? 64 : 128);
@@ -2265,7 +2428,7 @@ int launch_dma_tab_ks2(const pn2_conv_job* jobs, const int* bstart, int njobs, i
 }
 template <typename T, bool EP, int BM, int BN, int WM, int WN>
 int launch_gather_tab_f32(const pn2_conv_job* jobs, const int* bstart, int njobs, int total, hipStream_t st) {
-    constexpr int main_b = 2 * (BM + BN) * RS, epi_b = BM * (BN * 4 + 16) + 3 * WM * BN * 4, ep_b = EP ? ep_lds_bytes(4) : 0;
+    constexpr int main_b = 2 * (BM + BN) * (RS + lo_row<T>), epi_b = BM * (BN * 4 + 16) + 3 * WM * BN * 4, ep_b = EP ? ep_lds_bytes(4) : 0;
     constexpr int lds = (main_b > epi_b ? main_b : epi_b) > ep_b ? (main_b > epi_b ? main_b : epi_b) : ep_b;
     static bool done = false;
     if (!done) {
@@ -2314,6 +2477,16 @@ int gemm_multi_dispatch(int dtype, int bm, int bn, int bits, const pn2_conv_job*
         } else if (bm == 64) {
             if (bn == 64) return launch_gather_tab_f32<f32f_t, EP, 64, 64, 2, 2>(jobs, bstart, njobs, total, st);
             if (bn == 32) return launch_gather_tab_f32<f32f_t, EP, 64, 32, 4, 1>(jobs, bstart, njobs, total, st);
+        }
+        return -2;
+    }
+    if (dtype == PN2_F32X3) {         // (no 128-wide tiles either)
+        if (bm == 128) {
+            if (bn == 64) return launch_gather_tab_f32<f32x3_t, EP, 128, 64, 2, 2>(jobs, bstart, njobs, total, st);
+            if (bn == 32) return launch_gather_tab_f32<f32x3_t, EP, 128, 32, 4, 1>(jobs, bstart, njobs, total, st);
+        } else if (bm == 64) {
+            if (bn == 64) return launch_gather_tab_f32<f32x3_t, EP, 64, 64, 2, 2>(jobs, bstart, njobs, total, st);
+            if (bn == 32) return launch_gather_tab_f32<f32x3_t, EP, 64, 32, 4, 1>(jobs, bstart, njobs, total, st);
         }
         return -2;
     }
@@ -2388,7 +2561,15 @@ int wgrad_dispatch(const void* dy, const void* x, float* slab, const pn2_wgrad_d
 template <typename T, int BMC, int WM, int WN>
 int launch_wgrad_tab(bool pw, const pn2_wgrad_job* jobs, const int* bstart, int njobs, int total, hipStream_t st) {
     constexpr int BNK = 128;
-    constexpr int lds = 2 * WGP * (BMC * (int)sizeof(T) + WG<T>::PAD + BNK * (int)sizeof(T) + WG<T>::PAD);
+    constexpr int lds = 2 * wg_stage_bytes<T>(BMC, BNK);
+    if constexpr (X3<T>) {
+        static bool done = false;
+        if (!done) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tab<T, BMC, BNK, WM, WN, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tab<T, BMC, BNK, WM, WN, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            done = true;
+        }
+    }
     if (pw) hipLaunchKernelGGL((conv_wgrad_tab<T, BMC, BNK, WM, WN, true>), dim3(total), dim3(256), lds, st, jobs, bstart, njobs);
     else hipLaunchKernelGGL((conv_wgrad_tab<T, BMC, BNK, WM, WN, false>), dim3(total), dim3(256), lds, st, jobs, bstart, njobs);
     PN2_CHECK_LAUNCH();
@@ -2625,6 +2806,7 @@ static int conv_gemm_impl(int dtype, const void* in, const void* wp, void* out, 
     if (dtype == PN2_BF16) return use_ep ? gemm_dispatch<bf16_t, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<bf16_t, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
     if (dtype == PN2_F32) return use_ep ? gemm_dispatch<float, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<float, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
     if (dtype == PN2_F32F) return use_ep ? gemm_dispatch<f32f_t, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<f32f_t, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
+    if (dtype == PN2_F32X3) return use_ep ? gemm_dispatch<f32x3_t, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<f32x3_t, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
     return -3;
 }
 
@@ -2676,6 +2858,7 @@ int pn2_conv_gemm_affine(int dtype, const void* in, const void* wp, void* out, c
     if (dtype == PN2_BF16) return gemm_dispatch<bf16_t, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
     if (dtype == PN2_F32) return gemm_dispatch<float, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
     if (dtype == PN2_F32F) return gemm_dispatch<f32f_t, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
+    if (dtype == PN2_F32X3) return gemm_dispatch<f32x3_t, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
     return -3;
 }
 
@@ -2720,6 +2903,7 @@ int pn2_conv_gemm_tile(int dtype, const pn2_conv_desc* d) {
     if (dtype == PN2_BF16) { gemm_select<bf16_t>(*d, kern, bm, bn); if (!dma_extent_ok(*d)) return -2; }      // (a register-staged choice joins the table on the LDS-DMA kernel: same bits)
     else if (dtype == PN2_F32) gemm_select<float>(*d, kern, bm, bn);
     else if (dtype == PN2_F32F) gemm_select<f32f_t>(*d, kern, bm, bn);
+    else if (dtype == PN2_F32X3) gemm_select<f32x3_t>(*d, kern, bm, bn);
     else return -3;
     if (ksb) {
         if (dtype != PN2_BF16 || bn < 64 || (bm == 128 && bn == 128)) return -2;
@@ -2758,12 +2942,13 @@ int pn2_conv_wgrad(int dtype, const void* dy, const void* x, float* slab, const 
     if (dtype == PN2_BF16) return wgrad_dispatch<bf16_t>(dy, x, slab, *d, nsplit, (hipStream_t)stream);
     if (dtype == PN2_F32) return wgrad_dispatch<float>(dy, x, slab, *d, nsplit, (hipStream_t)stream);
     if (dtype == PN2_F32F) return wgrad_dispatch<f32f_t>(dy, x, slab, *d, nsplit, (hipStream_t)stream);
+    if (dtype == PN2_F32X3) return wgrad_dispatch<f32x3_t>(dy, x, slab, *d, nsplit, (hipStream_t)stream);
     return -3;
 }
 
 int pn2_conv_wgrad_variant(int dtype, const pn2_wgrad_desc* d) {
     if (!d) return -1;
-    return dtype == PN2_BF16 ? wgrad_variant<bf16_t>(*d) : ((dtype == PN2_F32 || dtype == PN2_F32F) ? wgrad_variant<float>(*d) : -3);
+    return dtype == PN2_BF16 ? wgrad_variant<bf16_t>(*d) : ((dtype == PN2_F32 || dtype == PN2_F32F || dtype == PN2_F32X3) ? wgrad_variant<float>(*d) : -3);
 }
 
 int pn2_conv_wgrad_blocks(const pn2_wgrad_desc* d, int nsplit) {
@@ -2778,6 +2963,7 @@ int pn2_conv_wgrad_multi(int dtype, int variant, const pn2_wgrad_job* jobs_dev, 
     if (dtype == PN2_BF16) return wgrad_multi_dispatch<bf16_t>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream);
     if (dtype == PN2_F32) return wgrad_multi_dispatch<float>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream);
     if (dtype == PN2_F32F) return wgrad_multi_dispatch<f32f_t>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream);
+    if (dtype == PN2_F32X3) return wgrad_multi_dispatch<f32x3_t>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream);
     return -3;
 }
 

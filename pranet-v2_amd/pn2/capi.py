@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("PN2_LIB") or os.path.join(os.path.dirname(_HERE), "cs
 F32, BF16 = 0, 1
 F32F = 2          # PN2_F32F ("fp32fast"): fp32 storage like F32, conv contractions on the f32 matrix pipe (v_mfma_f32_16x16x4_f32) instead of the f64 one;
                   # accepted by the conv GEMM / wgrad entry points only (include/pn2.h) - the engine passes it there as Engine.mma
+F32X3 = 3         # PN2_F32X3 ("fp32x3"): fp32 storage like F32, conv operands split into three bf16 terms, six cross products on the bf16 matrix pipe
+                  # (v_mfma_f32_16x16x32_bf16), fp32-grade contractions; the same entry points as F32F take it
 CONV_STATS, CONV_ACCUM, CONV_BIAS = 1, 2, 4
 CONV_AFFINE, CONV_RELU, CONV_RELU6 = 16, 32, 64
 

@@ -12,7 +12,7 @@ import torch
 
 from . import capi
 from . import core
-from .capi import call, F32, BF16, F32F
+from .capi import call, F32, BF16, F32F, F32X3
 from .core import *            # noqa: F401,F403
 from .core import _p, _stream, _job_table, _thrash, _w4, _LinearAsConv, _PERMS, _THRASH      # noqa: F401
 from .ops_conv import ConvOps
@@ -32,8 +32,8 @@ class Engine(ConvOps, EncoderOps, SpatialOps):
         if not torch.cuda.is_available():
             raise RuntimeError("pranet-v2_amd runs on MI355X only: no GPU visible and there is no CPU fallback")
         capi.load()
-        self.mma = dtype                                # compute mode = dtype code of the conv GEMM / wgrad entry points (BF16, F32 or F32F)
-        self.dt = F32 if dtype == F32F else dtype      # storage dtype of activations and of every other launch (fp32fast stores fp32)
+        self.mma = dtype                                # compute mode = dtype code of the conv GEMM / wgrad entry points (BF16, F32, F32F or F32X3)
+        self.dt = F32 if dtype in (F32F, F32X3) else dtype      # storage dtype of activations and of every other launch (fp32fast / fp32x3 store fp32)
         self.tdt = TORCH_DT[self.dt]
         self.training = training
         self.need_grad = need_grad      # decided by the caller (grad mode is off inside autograd.Function.forward)

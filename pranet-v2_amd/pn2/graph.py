@@ -10,30 +10,32 @@ import torch
 
 import weakref
 
-from .capi import F32, BF16, F32F
+from .capi import F32, BF16, F32F, F32X3
 from .engine import Engine, GradQueue, PackCache, StepArena, TUNER
 
-_DT = {"bf16": BF16, "bfloat16": BF16, "fp32": F32, "float32": F32, "f32": F32, "fp32fast": F32F, "f32fast": F32F, "fp32_fast": F32F}
-_MODE = {BF16: "bf16", F32: "fp32", F32F: "fp32fast"}
+_DT = {"bf16": BF16, "bfloat16": BF16, "fp32": F32, "float32": F32, "f32": F32, "fp32fast": F32F, "f32fast": F32F, "fp32_fast": F32F,
+       "fp32x3": F32X3, "f32x3": F32X3}
+_MODE = {BF16: "bf16", F32: "fp32", F32F: "fp32fast", F32X3: "fp32x3"}
 _compute_dtype = _DT[os.environ.get("PN2_DTYPE", "bf16").lower()]
 
 
 def set_compute_dtype(name):
     """'bf16' (default: bf16 storage + MFMA, fp32 accumulate), 'fp32' (fp32 storage, conv contractions in DOUBLE on the f64 matrix pipe: the parity path) or
     'fp32fast' (fp32 storage, fp32 products and sums on the f32 matrix pipe - the reference's own arithmetic, MyTrain_med.py runs without autocast - at twice
-    the pipe rate; everything except the conv GEMM / wgrad kernels is the 'fp32' path).  Trainers and predictors built afterwards run in this mode, those
+    the pipe rate; everything except the conv GEMM / wgrad kernels is the 'fp32' path) or 'fp32x3' (as 'fp32fast', but the conv operands are split into three
+    bf16 terms and six of their cross products run on the bf16 matrix pipe: fp32-grade contractions at a third of fp32fast's matrix cycles).  Trainers and predictors built afterwards run in this mode, those
     built before keep theirs; a module call runs in the mode current at the call, each mode on call sites of its own."""
     global _compute_dtype
     _compute_dtype = _DT[name.lower()] if isinstance(name, str) else name
 
 
 def get_compute_mode():
-    """'bf16' | 'fp32' | 'fp32fast'"""
+    """'bf16' | 'fp32' | 'fp32fast' | 'fp32x3'"""
     return _MODE[_compute_dtype]
 
 
 def get_compute_dtype():
-    """The mode as the engine takes it: capi.BF16, capi.F32 or capi.F32F."""
+    """The mode as the engine takes it: capi.BF16, capi.F32, capi.F32F or capi.F32X3."""
     return _compute_dtype
 
 

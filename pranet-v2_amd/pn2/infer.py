@@ -17,7 +17,7 @@ class Predictor:
 
     def __init__(self, model, dtype=None):
         self.model = model
-        self.dtype = get_compute_dtype() if dtype is None else dtype          # compute mode (BF16 / F32 / F32F), kept for the object's life
+        self.dtype = get_compute_dtype() if dtype is None else dtype          # compute mode (BF16 / F32 / F32F / F32X3), kept for the object's life
         self.pack_cache = PackCache()
         self.bn_fold = BnFoldCache()    # folded BatchNorm rows of every layer: one table-driven launch per forward (inside the graph: the live statistics are used)
         self._states = {}               # input shape -> captured forward (insertion order = LRU order)

@@ -6,10 +6,11 @@ import torch
 
 from . import capi
 from . import core
-from .capi import call, F32, BF16, F32F
+from .capi import call, F32, BF16, F32F, F32X3
 from .core import (Act, Bnb, KSPLIT_MINK, TUNE_REPS, WGRAD_SLAB_MB, WGRAD_WGS, _LinearAsConv, _job_table, _p, _stream, _thrash, _w4, rup)
 
 KS_UNTUNED = 3 | (1 << 2) | (2 << 4) | 0x40          # tuning code: LDS-DMA 2-stage ring, 64 x 128 tile, two K groups (see ConvOps._untuned)
+_MMA_KEY = {F32F: "f32f", F32X3: "f32x3"}           # tuner-key suffix of the fp32-storage modes whose register-staged tiles are tuned per shape
 
 
 class ConvOps:
@@ -49,7 +50,7 @@ class ConvOps:
         self.tuner and reused under hipGraph capture).  Returns the code for pn2_conv_desc.flags bits 8..15 (0 = library heuristic).
         ep: the launch carries a BatchNorm-backward epilogue (pn2_conv_gemm_ep): the candidates are timed WITH it (its extra operand reads and
         per-tile work favour other tiles than the plain kernel), writing to scratch destinations."""
-        fast = self.mma == F32F                                      # fp32fast: tiles of the register-staged kernel are tuned per shape too (64-row tiles win where
+        fast = self.mma in (F32F, F32X3)                             # fp32fast / fp32x3: tiles of the register-staged kernel are tuned per shape too (64-row tiles win where
         if self.dt != BF16 and not fast:                             # the heuristic takes 128: more workgroups per CU; 716 -> 748 images/s with 64 rows everywhere)
             return 0
         t = self.tuner
@@ -59,7 +60,7 @@ class ConvOps:
         if ep is not None:
             key = key + ("ep", ep.a.mode, ep.b.mode, 1 if ep.b.out else 0, cd.flags & capi.CONV_ACCUM) + (("pool",) if ep.pool else ())
         if fast:
-            key = key + ("f32f",)
+            key = key + (_MMA_KEY[self.mma],)
         if key in t:
             if core.TUNE_LOG is not None:
                 core.TUNE_LOG.append((key, t[key], "hit"))
@@ -177,12 +178,12 @@ class ConvOps:
         """-> (kernel code, pixel splits) for this wgrad shape.  Candidates: register-staged / LDS-DMA / LDS-DMA with 128 x 256 tiles x
         {1, 1/2, 1/4, 1/8} of the heuristic split count; each is timed together with the slab reduction its split count implies."""
         t = self.tuner
-        fast = self.mma == F32F          # fp32fast: one kernel, but the pixel-split count is worth timing
+        fast = self.mma in (F32F, F32X3)          # fp32fast / fp32x3: one kernel, but the pixel-split count is worth timing
         if t is None or (self.dt != BF16 and not fast):
             return 0, nsplit
         key = ("w", wd.N, wd.H, wd.W, wd.OH, wd.OW, wd.Cin_p, wd.ld_x, wd.Cout_p, wd.ld_dy, wd.KH, wd.KW, wd.stride, wd.pad_h, wd.pad_w, wd.dil_h, wd.dil_w, nsplit)
         if fast:
-            key = key + ("f32f",)
+            key = key + (_MMA_KEY[self.mma],)
         if key in t:
             return t[key]
         if torch.cuda.is_current_stream_capturing():

@@ -219,7 +219,7 @@ def _conv_class(shape):
 
 def measure_step(trainer, x, m, dtype, config=None):
     """dtype: the caller's name for the mode (unused: the peak is that of the matrix pipe the trainer's own mode runs on)."""
-    peak_tf = 2500.0 if trainer.dtype == capi.BF16 else 157.3
+    peak_tf = 2500.0 if trainer.dtype == capi.BF16 else (2500.0 / 6 if trainer.dtype == capi.F32X3 else 157.3)      # fp32x3: three bf16 MFMAs per 16-deep step
     ACTUAL.clear()
     trainer.step(x, m)                       # eager warm-up (allocator, caches)
     # Keep the GPU queue full during the instrumented step: a spin kernel first, so the host runs ahead and every event marker

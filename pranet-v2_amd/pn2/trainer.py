@@ -58,7 +58,7 @@ class Trainer:
             raise ValueError(f"unknown loss {loss!r}")
         clip = 3.0e38 if clip is None else clip
         self.lr, self.clip, self.betas, self.eps = lr, clip, betas, eps
-        self.dtype = get_compute_dtype() if dtype is None else dtype          # compute mode (BF16 / F32 / F32F), kept for the object's life
+        self.dtype = get_compute_dtype() if dtype is None else dtype          # compute mode (BF16 / F32 / F32F / F32X3), kept for the object's life
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.dp = process_group is not None and (self.world > 1 or force_dp or os.environ.get("PN2_DP_FORCE", "0") == "1")

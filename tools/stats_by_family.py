@@ -13,6 +13,8 @@ for r in rows:
     k = m.group(1) if m else n[:40]
     if "f32f_t" in n:
         k += "<f32f>"
+    elif "f32x3_t" in n:
+        k += "<f32x3>"
     elif "<float" in n:
         k += "<float>"
     agg[k] += int(r["TotalDurationNs"]); calls[k] += int(r["Calls"])
