@@ -409,16 +409,19 @@ int pn2_gelu_bwd(int dt, const void* dy, const void* z, void* dz, long long n, v
  * (the pn2_gelu_bwd pass fused in; dz_out then feeds the flip=1 data-gradient launch). */
 int pn2_dwconv3x3_wgrad_blocks(int dt, int N, int H, int W, int C);
 int pn2_dwconv3x3_wgrad(int dt, const void* dz, const void* x, float* partial, int nblk, int N, int H, int W, int C, const void* zpre, void* dz_out, void* stream);
-/* Spatial-reduction attention (Attention.forward pvtv2.py:90-111), head_dim 64, Nkv <= 256:
- * q [B][Nq][heads*64] ; kv [B][Nkv][2*heads*64] (k then v, heads inner, as the reference's reshape(B,-1,2,heads,hd)) ;
- * out = softmax(q k^T * scale) v, heads concatenated ; lse [B][heads][Nq] fp32 saved for the backward.
+/* Spatial-reduction attention (Attention.forward pvtv2.py:90-111), head_dim hd = 32 (pvt_v2_b0) or 64 (b1..b5), 1 <= Nkv <= 256; any other
+ * head_dim or Nkv returns -2:
+ * q [B][Nq][heads*hd] ; kv [B][Nkv][2*heads*hd] (k then v, heads inner, as the reference's reshape(B,-1,2,heads,hd)) ;
+ * out [B][Nq][heads*hd] = softmax(q k^T * scale) v, heads concatenated ; lse [B][heads][Nq] fp32 saved for the backward.
+ * Rows may be wider than heads*hd (ld_* >= the row); the bf16 MFMA kernels need every ld a multiple of 8, other views take the scalar kernels
+ * (their bf16 backward returns -2 where its 256-query chunks outnumber pn2_attn_bwd_blocks).
  * Backward: dq, dkv written (not accumulated); `partial` is scratch (see pn2_attn_bwd_blocks). */
 /* DropPath (stochastic depth, pvtv2.py:125,148-149): y[n] = x[n] * scale[n] (+ res[n]: the residual add of Block.forward :148-149 in the same pass),
  * scale[n] = bernoulli(keep)/keep drawn by the caller; with res == NULL it is its own adjoint */
 int pn2_scale_samples(int dt, const void* x, void* y, const float* scale, const void* res, int N, long long per_sample, void* stream);
 int pn2_attn_fwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads, int head_dim,
                  float scale, void* stream);
-int pn2_attn_bwd_blocks(int dt, int B, int heads, int Nq);   /* partial slots per (b, head): partial holds [B][heads][slots][2][roundup(Nkv,64)][64] fp32 */
+int pn2_attn_bwd_blocks(int dt, int B, int heads, int Nq);   /* partial slots per (b, head): partial holds [B][heads][slots][2][roundup(Nkv,64)][hd] fp32 */
 /* out = the forward result (delta = rowsum(dO * out) lets the bf16 MFMA path treat key ranges independently); delta: [B][heads][Nq] fp32 scratch */
 int pn2_attn_bwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, const void* out, int ld_o, const void* dout, int ld_do, const float* lse, void* dq, int ld_dq,
                  void* dkv, int ld_dkv, float* partial, float* delta, int B, int Nq, int Nkv, int heads, int head_dim, float scale, void* stream);

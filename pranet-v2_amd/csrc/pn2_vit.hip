@@ -2,7 +2,7 @@
 //   LayerNorm forward / backward            nn.LayerNorm at pvtv2.py:71,119,126,169,224-247 (eps 1e-5 / 1e-6)
 //   column sums                             bias gradients of nn.Linear / biased nn.Conv2d (:19,22,62-65,70,167)
 //   depth-wise 3x3 conv (+bias, +GELU)      DWConv :363-374 followed by nn.GELU in Mlp.forward :42-49
-//   spatial-reduction attention             Attention.forward :90-111 (head_dim 64, <= 256 reduced key/value tokens)
+//   spatial-reduction attention             Attention.forward :90-111 (head_dim 32 or 64, <= 256 reduced key/value tokens)
 // Tokens [B, N, C] of the reference are NHWC pixels here (N = H*W), so no transposes are needed anywhere.
 // The Linear layers themselves run on the implicit-GEMM conv kernels (1x1) of pn2_conv.hip.
 // All kernels are deterministic (fixed-order reductions, no floating-point atomics).
@@ -751,22 +751,24 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_row_k(const T* __restrict
 }
 
 // ------------------------------------------------------------------------------------------ spatial-reduction attention
-// q   [B][Nq][heads*64]                      (Attention.q)
-// kv  [B][Nkv][2*heads*64]: k of head h at columns h*64.., v at heads*64 + h*64..   (Attention.kv reshaped (B,-1,2,heads,64), :98-101)
-// out [B][Nq][heads*64]  = softmax(q k^T * scale) v   with heads concatenated (:107)
-// One block = 4 waves = 4 queries in flight for one (b, head); K^T, K, V^T, V of that head live in LDS (<= 256 keys).  Lane d of a wave
-// owns dimension d of q / out; lane l owns keys l, l+64, ... for the score / softmax part.
+// HD = head_dim, 32 (pvt_v2_b0) or 64 (b1..b5):
+// q   [B][Nq][heads*HD]                      (Attention.q)
+// kv  [B][Nkv][2*heads*HD]: k of head h at columns h*HD.., v at heads*HD + h*HD..   (Attention.kv reshaped (B,-1,2,heads,HD), :98-101)
+// out [B][Nq][heads*HD]  = softmax(q k^T * scale) v   with heads concatenated (:107)
+// One block = 4 waves = 4 queries in flight for one (b, head); K^T, K, V^T, V of that head live in LDS (<= 256 keys).  Lane d < HD of a wave
+// owns dimension d of q / out (at HD = 32 the upper half-wave idles in the dimension walks); lane l owns keys l, l+64, ... for the score /
+// softmax part.
 constexpr int AT_MAXK = 4;       // keys per lane -> Nkv <= 256
 
-template <typename T>
+template <typename T, int HD>
 __device__ __forceinline__ void attn_stage_kv(const T* __restrict__ kv, int ld_kv, int Nkv, int NP, int heads, int h, float* Kt, float* Vt) {
-    // Kt/Vt: [64 dims][NP + 1]: the odd row stride makes both walks conflict-free — lanes over keys (row d, consecutive l) and lanes
+    // Kt/Vt: [HD dims][NP + 1]: the odd row stride makes both walks conflict-free — lanes over keys (row d, consecutive l) and lanes
     // over dims (column l, stride NP + 1); pad keys hold zeros
     const int RS = NP + 1;
-    for (int i = threadIdx.x; i < NP * 64; i += 256) {
-        const int l = i >> 6, d = i & 63;
+    for (int i = threadIdx.x; i < NP * HD; i += 256) {
+        const int l = i / HD, d = i % HD;
         float k = 0.f, v = 0.f;
-        if (l < Nkv) { k = TT<T>::ld(kv + (size_t)l * ld_kv + h * 64 + d); v = TT<T>::ld(kv + (size_t)l * ld_kv + heads * 64 + h * 64 + d); }
+        if (l < Nkv) { k = TT<T>::ld(kv + (size_t)l * ld_kv + h * HD + d); v = TT<T>::ld(kv + (size_t)l * ld_kv + heads * HD + h * HD + d); }
         Kt[d * RS + l] = k;
         Vt[d * RS + l] = v;
     }
@@ -776,14 +778,15 @@ __device__ __forceinline__ float rdlane(float v, int lane) { return __int_as_flo
 
 constexpr int AT_QB = 4;         // queries a wave works on at once: every K / V value read from LDS is used AT_QB times
 
-template <typename T, int NK>
+template <typename T, int NK, int HD>
 __global__ __launch_bounds__(256) void attn_fwd_k(const T* __restrict__ q, int ld_q, const T* __restrict__ kv, int ld_kv, T* __restrict__ out, int ld_o,
                                                   float* __restrict__ lse, int Nq, int Nkv, int heads, float scale, int q_per_blk) {
     extern __shared__ float lds[];
     constexpr int NP = NK * 64, RS = NP + 1;
-    float* Kt = lds; float* Vt = lds + 64 * RS;
+    float* Kt = lds; float* Vt = lds + HD * RS;
     const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    attn_stage_kv<T>(kv + (size_t)b * Nkv * ld_kv, ld_kv, Nkv, NP, heads, h, Kt, Vt);
+    const int dl = lane & (HD - 1);                                      // dimension of this lane in the dimension walks (lane < HD stores)
+    attn_stage_kv<T, HD>(kv + (size_t)b * Nkv * ld_kv, ld_kv, Nkv, NP, heads, h, Kt, Vt);
     __syncthreads();
     const int q0 = blockIdx.x * q_per_blk;
     int q1 = q0 + q_per_blk; if (q1 > Nq) q1 = Nq;
@@ -792,12 +795,12 @@ __global__ __launch_bounds__(256) void attn_fwd_k(const T* __restrict__ q, int l
 #pragma unroll
         for (int i = 0; i < AT_QB; ++i) {
             const int qi = qb + i < q1 ? qb + i : q1 - 1;
-            qd[i] = TT<T>::ld(q + ((size_t)b * Nq + qi) * ld_q + h * 64 + lane) * scale;
+            qd[i] = TT<T>::ld(q + ((size_t)b * Nq + qi) * ld_q + h * HD + dl) * scale;
 #pragma unroll
             for (int k = 0; k < NK; ++k) s[i][k] = 0.f;
         }
 #pragma unroll
-        for (int d = 0; d < 64; ++d) {
+        for (int d = 0; d < HD; ++d) {
             float kk[NK];
 #pragma unroll
             for (int k = 0; k < NK; ++k) kk[k] = Kt[d * RS + k * 64 + lane];
@@ -826,34 +829,35 @@ __global__ __launch_bounds__(256) void attn_fwd_k(const T* __restrict__ q, int l
         for (int k = 0; k < NK; ++k) {
 #pragma unroll
             for (int l = 0; l < 64; ++l) {
-                const float vv = Vt[lane * RS + k * 64 + l];
+                const float vv = Vt[dl * RS + k * 64 + l];
 #pragma unroll
                 for (int i = 0; i < AT_QB; ++i) o_[i] += rdlane(s[i][k], l) * vv;
             }
         }
 #pragma unroll
         for (int i = 0; i < AT_QB; ++i)
-            if (qb + i < q1) TT<T>::st(out + ((size_t)b * Nq + qb + i) * ld_o + h * 64 + lane, o_[i] * inv[i]);
+            if (qb + i < q1 && lane < HD) TT<T>::st(out + ((size_t)b * Nq + qb + i) * ld_o + h * HD + lane, o_[i] * inv[i]);
     }
 }
 
 // backward.  A block owns a chunk of queries of one (b, head).  Per group of 4 x QB queries (QB per wave): phase A recomputes
 // p = exp(s - lse), dP = dO V^T, dS = p (dP - sum p dP) and dq = scale dS K exactly like the forward walks K / V; P, dS, q, dO of the
 // group go to LDS tiles.  Phase B: every wave owns NP/4 keys and accumulates dK[l][d] += dS[q][l] q[q][d], dV[l][d] += P[q][l] dO[q][d]
-// in registers (lane = d, broadcast LDS reads).  Block partials [2][NP][64] are summed over the query chunks by attn_bwd_kv_reduce_k.
+// in registers (lane = d, broadcast LDS reads).  Block partials [2][NP][HD] are summed over the query chunks by attn_bwd_kv_reduce_k.
 constexpr int AT_QCHUNK = 256;
 
-template <typename T, int NK, int QB>
+template <typename T, int NK, int QB, int HD>
 __global__ __launch_bounds__(256) void attn_bwd_k(const T* __restrict__ q, int ld_q, const T* __restrict__ kv, int ld_kv, const T* __restrict__ dout, int ld_do,
                                                   const float* __restrict__ lse, T* __restrict__ dq, int ld_dq, float* __restrict__ part,
                                                   int Nq, int Nkv, int heads, float scale) {
     extern __shared__ float lds[];
     constexpr int NP = NK * 64, RS = NP + 1, KPW = NP / 4;
-    float* Kt = lds; float* Vt = Kt + 64 * RS;
+    float* Kt = lds; float* Vt = Kt + HD * RS;
     constexpr int GQ = 4 * QB;          // queries per group
-    float* Pt = Vt + 64 * RS; float* dSt = Pt + GQ * NP; float* qt = dSt + GQ * NP; float* dot = qt + GQ * 64;
+    float* Pt = Vt + HD * RS; float* dSt = Pt + GQ * NP; float* qt = dSt + GQ * NP; float* dot = qt + GQ * HD;
     const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    attn_stage_kv<T>(kv + (size_t)b * Nkv * ld_kv, ld_kv, Nkv, NP, heads, h, Kt, Vt);
+    const int dl = lane & (HD - 1);                                      // as in attn_fwd_k: lanes >= HD compute a copy of lane - HD and store nothing
+    attn_stage_kv<T, HD>(kv + (size_t)b * Nkv * ld_kv, ld_kv, Nkv, NP, heads, h, Kt, Vt);
     __syncthreads();
     const int q0 = blockIdx.x * AT_QCHUNK;
     int q1 = q0 + AT_QCHUNK; if (q1 > Nq) q1 = Nq;
@@ -868,14 +872,14 @@ __global__ __launch_bounds__(256) void attn_bwd_k(const T* __restrict__ q, int l
             const bool ok = qb + i < q1;
             const int qi = ok ? qb + i : q1 - 1;
             const size_t qo = (size_t)b * Nq + qi;
-            qd[i] = ok ? TT<T>::ld(q + qo * ld_q + h * 64 + lane) * scale : 0.f;
-            dod[i] = ok ? TT<T>::ld(dout + qo * ld_do + h * 64 + lane) : 0.f;
+            qd[i] = ok && lane < HD ? TT<T>::ld(q + qo * ld_q + h * HD + lane) * scale : 0.f;
+            dod[i] = ok && lane < HD ? TT<T>::ld(dout + qo * ld_do + h * HD + lane) : 0.f;
             L[i] = lse[((size_t)b * heads + h) * Nq + qi];
 #pragma unroll
             for (int k = 0; k < NK; ++k) { s[i][k] = 0.f; dp[i][k] = 0.f; }
         }
 #pragma unroll
-        for (int d = 0; d < 64; ++d) {
+        for (int d = 0; d < HD; ++d) {
             float kk[NK], vv[NK];
 #pragma unroll
             for (int k = 0; k < NK; ++k) { kk[k] = Kt[d * RS + k * 64 + lane]; vv[k] = Vt[d * RS + k * 64 + lane]; }
@@ -900,48 +904,51 @@ __global__ __launch_bounds__(256) void attn_bwd_k(const T* __restrict__ q, int l
                 dp[i][k] = s[i][k] * (dp[i][k] - delta);          // dS
                 Pt[row * NP + k * 64 + lane] = s[i][k]; dSt[row * NP + k * 64 + lane] = dp[i][k];
             }
-            qt[row * 64 + lane] = qd[i]; dot[row * 64 + lane] = dod[i];
+            if (lane < HD) { qt[row * HD + lane] = qd[i]; dot[row * HD + lane] = dod[i]; }
             dqd[i] = 0.f;
         }
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
 #pragma unroll
             for (int l = 0; l < 64; ++l) {
-                const float kk = Kt[lane * RS + k * 64 + l];
+                const float kk = Kt[dl * RS + k * 64 + l];
 #pragma unroll
                 for (int i = 0; i < QB; ++i) dqd[i] += rdlane(dp[i][k], l) * kk;
             }
         }
 #pragma unroll
         for (int i = 0; i < QB; ++i)
-            if (qb + i < q1) TT<T>::st(dq + ((size_t)b * Nq + qb + i) * ld_dq + h * 64 + lane, dqd[i] * scale);
+            if (qb + i < q1 && lane < HD) TT<T>::st(dq + ((size_t)b * Nq + qb + i) * ld_dq + h * HD + lane, dqd[i] * scale);
         __syncthreads();
         // phase B: this wave's keys [wid*KPW, +KPW), all queries of the group
         for (int r = 0; r < GQ; ++r) {
-            const float qv = qt[r * 64 + lane], gv = dot[r * 64 + lane];
+            const float qv = qt[r * HD + dl], gv = dot[r * HD + dl];
             const float* pr = Pt + r * NP + wid * KPW; const float* dr = dSt + r * NP + wid * KPW;
 #pragma unroll
             for (int j = 0; j < KPW; ++j) { ak[j] += dr[j] * qv; av[j] += pr[j] * gv; }
         }
         __syncthreads();
     }
-    float* dst = part + ((((size_t)b * heads + h) * gridDim.x + blockIdx.x) * 2) * NP * 64;
+    float* dst = part + ((((size_t)b * heads + h) * gridDim.x + blockIdx.x) * 2) * NP * HD;
+    if (lane < HD) {
 #pragma unroll
-    for (int j = 0; j < KPW; ++j) {
-        dst[(size_t)(wid * KPW + j) * 64 + lane] = ak[j];                 // qd carried the softmax scale already
-        dst[(size_t)NP * 64 + (size_t)(wid * KPW + j) * 64 + lane] = av[j];
+        for (int j = 0; j < KPW; ++j) {
+            dst[(size_t)(wid * KPW + j) * HD + lane] = ak[j];             // qd carried the softmax scale already
+            dst[(size_t)NP * HD + (size_t)(wid * KPW + j) * HD + lane] = av[j];
+        }
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(64) void attn_bwd_kv_reduce_k(const float* __restrict__ part, T* __restrict__ dkv, int ld_dkv, int Nkv, int NP, int heads, int nqb) {
+// one block of HD threads per (key, head, b): partial [B][heads][nqb][2][NP][HD]
+template <typename T, int HD>
+__global__ __launch_bounds__(HD) void attn_bwd_kv_reduce_k(const float* __restrict__ part, T* __restrict__ dkv, int ld_dkv, int Nkv, int NP, int heads, int nqb) {
     const int l = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
-    const float* p = part + (((size_t)b * heads + h) * nqb * 2) * NP * 64 + (size_t)l * 64 + d;
+    const float* p = part + (((size_t)b * heads + h) * nqb * 2) * NP * HD + (size_t)l * HD + d;
     float sk = 0.f, sv = 0.f;
-    for (int c = 0; c < nqb; ++c) { sk += p[(size_t)c * 2 * NP * 64]; sv += p[(size_t)c * 2 * NP * 64 + (size_t)NP * 64]; }
+    for (int c = 0; c < nqb; ++c) { sk += p[(size_t)c * 2 * NP * HD]; sv += p[(size_t)c * 2 * NP * HD + (size_t)NP * HD]; }
     T* dst = dkv + ((size_t)b * Nkv + l) * ld_dkv;
-    TT<T>::st(dst + h * 64 + d, sk);
-    TT<T>::st(dst + heads * 64 + h * 64 + d, sv);
+    TT<T>::st(dst + h * HD + d, sk);
+    TT<T>::st(dst + heads * HD + h * HD + d, sv);
 }
 
 // ------------------------------------------------------------------------------------------ bf16 MFMA attention
@@ -955,16 +962,26 @@ __device__ __forceinline__ f32x4v mfma16(const uint4& a, const uint4& b, f32x4v 
 
 // Fragment (A[i][k] or B[k][i], i = lane & 15) of a 16-wide column block of a ROW-MAJOR LDS tile [k][col] whose rows are the contraction index,
 // through the transposing LDS read: k-slot (g, j) <-> tile row (j >> 2) * 16 + g * 4 + (j & 3).  The other operand of the MFMA has to walk the
-// contraction in the same order (perm_frag).  Conflict-free when the row stride is an odd multiple of 32 bytes (ATR = 80 elements).
+// contraction in the same order (perm_frag).  Conflict-free when the row stride is an odd multiple of 32 bytes: ATR = 80 elements for 64-wide
+// rows (head_dim 64, and the 64-query tiles of the backward), 48 for 32-wide rows (head_dim 32).
 constexpr int ATR = 80;
+template <int HD> constexpr int at_tr() { static_assert(HD == 32 || HD == 64, "head_dim 32 or 64"); return HD == 64 ? ATR : 48; }
+template <int R = ATR>
 __device__ __forceinline__ uint4 tr_frag(const bf16_t* tile, int col0, int lane) {
     const int g = lane >> 4, i = lane & 15;
-    unsigned a = (unsigned)(size_t)(reinterpret_cast<const char*>(tile) + (g * 4 + (i >> 2)) * (ATR * 2) + (col0 + (i & 3) * 4) * 2);
+    unsigned a = (unsigned)(size_t)(reinterpret_cast<const char*>(tile) + (g * 4 + (i >> 2)) * (R * 2) + (col0 + (i & 3) * 4) * 2);
     asm volatile("" : "+v"(a));            // keep the tile offset out of the instruction's immediate field
     const s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(a));
-    const s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(a + 16 * ATR * 2));
+    const s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(a + 16 * R * 2));
     const uint2 lo = __builtin_bit_cast(uint2, v0), hi = __builtin_bit_cast(uint2, v1);
     return make_uint4(lo.x, lo.y, hi.x, hi.y);
+}
+// f2bf of a value that may come straight from v_exp_f32: gfx950 needs one wait state between a transcendental's result and a VALU that reads it,
+// and the compiler's hazard recognizer does not look inside inline asm (f2bf's convert), so the pad is part of the asm
+__device__ __forceinline__ bf16_t f2bf_trans(float f) {
+    unsigned r;
+    asm("s_nop 0\n\tv_cvt_pk_bf16_f32 %0, %1, %1" : "=v"(r) : "v"(f));
+    return (bf16_t)r;
 }
 // the matching fragment of an operand stored with the contraction index contiguous: row[k0 + g*4 .. +3] and row[k0 + 16 + g*4 .. +3]
 __device__ __forceinline__ uint4 perm_frag(const bf16_t* row, int k0, int g) {
@@ -974,23 +991,24 @@ __device__ __forceinline__ uint4 perm_frag(const bf16_t* row, int k0, int g) {
 
 // Forward.  A block = 8 waves = 128 queries per step; K and V rows of the (b, head) are staged once (16-byte copies, no transposes) and the block
 // walks query tiles blockIdx.x, blockIdx.x + gridDim.x, ...  (the K/V staging of the one-tile-per-block version cost more than its MFMAs).
-template <int NK>
+// HD = 32: S = Q K^T is one MFMA per 16 x 16 tile (the whole contraction is one A fragment) and O = P V has 2 column blocks instead of 4.
+template <int NK, int HD>
 __global__ __launch_bounds__(512) void attn_fwd_mfma_k(const bf16_t* __restrict__ q, int ld_q, const bf16_t* __restrict__ kv, int ld_kv, bf16_t* __restrict__ out, int ld_o,
                                                        float* __restrict__ lse, int Nq, int Nkv, int heads, float scale) {
-    constexpr int NP = NK * 64, NT = NP / 16, KR = 72, PR = NP + 8;
+    constexpr int NP = NK * 64, NT = NP / 16, KR = HD + 8, VR = at_tr<HD>(), PR = NP + 8, ND = HD / 16, CH = HD / 8;
     extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
     bf16_t* Ks = smem;                    // [NP][KR]   key rows                   -> B operand of S = Q K^T (lane = key, 16 bytes of d)
-    bf16_t* Vs = Ks + NP * KR;            // [NP][ATR]  value rows                 -> B operand of O = P V through tr_frag (contraction = keys)
-    bf16_t* Ps = Vs + NP * ATR;           // [8 waves][16][PR] probabilities       -> A operand of O = P V (perm_frag)
+    bf16_t* Vs = Ks + NP * KR;            // [NP][VR]   value rows                 -> B operand of O = P V through tr_frag (contraction = keys)
+    bf16_t* Ps = Vs + NP * VR;            // [8 waves][16][PR] probabilities       -> A operand of O = P V (perm_frag)
     const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
     const bf16_t* kvb = kv + (size_t)b * Nkv * ld_kv;
-    for (int i = threadIdx.x; i < NP * 8; i += 512) {
-        const int key = i >> 3, ch = i & 7;
+    for (int i = threadIdx.x; i < NP * CH; i += 512) {
+        const int key = i / CH, ch = i % CH;
         uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
-        if (key < Nkv) { kk = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + h * 64 + ch * 8);
-                         vv = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + heads * 64 + h * 64 + ch * 8); }
+        if (key < Nkv) { kk = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + h * HD + ch * 8);
+                         vv = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + heads * HD + h * HD + ch * 8); }
         *reinterpret_cast<uint4*>(Ks + key * KR + ch * 8) = kk;
-        *reinterpret_cast<uint4*>(Vs + key * ATR + ch * 8) = vv;
+        *reinterpret_cast<uint4*>(Vs + key * VR + ch * 8) = vv;
     }
     __syncthreads();
     bf16_t* pw = Ps + wid * 16 * PR;
@@ -998,15 +1016,17 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma_k(const bf16_t* __restrict_
     for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
         const int q0 = tile * 128 + wid * 16;
         const int qa = min(q0 + l15, Nq - 1);                             // A-operand row of this lane
-        const bf16_t* qp = q + ((size_t)b * Nq + qa) * ld_q + h * 64 + g * 8;
-        const uint4 aq0 = *reinterpret_cast<const uint4*>(qp), aq1 = *reinterpret_cast<const uint4*>(qp + 32);
+        const bf16_t* qp = q + ((size_t)b * Nq + qa) * ld_q + h * HD + g * 8;
+        uint4 aq[HD / 32];
+#pragma unroll
+        for (int kc = 0; kc < HD / 32; ++kc) aq[kc] = *reinterpret_cast<const uint4*>(qp + kc * 32);
         f32x4v s[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const bf16_t* kp = Ks + (nt * 16 + l15) * KR + g * 8;
             f32x4v c = {0.f, 0.f, 0.f, 0.f};
-            c = mfma16(aq0, *reinterpret_cast<const uint4*>(kp), c);
-            c = mfma16(aq1, *reinterpret_cast<const uint4*>(kp + 32), c);
+#pragma unroll
+            for (int kc = 0; kc < HD / 32; ++kc) c = mfma16(aq[kc], *reinterpret_cast<const uint4*>(kp + kc * 32), c);
             s[nt] = c;
         }
         float mx[4], sum[4];
@@ -1025,25 +1045,25 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma_k(const bf16_t* __restrict_
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) pw[(g * 4 + r) * PR + nt * 16 + l15] = f2bf(s[nt][r]);
+            for (int r = 0; r < 4; ++r) pw[(g * 4 + r) * PR + nt * 16 + l15] = f2bf_trans(s[nt][r]);
         __syncthreads();                                                  // (every wave walks the same number of tiles)
-        f32x4v o[4];
+        f32x4v o[ND];
 #pragma unroll
-        for (int nd = 0; nd < 4; ++nd) o[nd] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        for (int nd = 0; nd < ND; ++nd) o[nd] = f32x4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < NP / 32; ++ks) {
             const uint4 ap = perm_frag(pw + l15 * PR, ks * 32, g);
 #pragma unroll
-            for (int nd = 0; nd < 4; ++nd) o[nd] = mfma16(ap, tr_frag(Vs + ks * 32 * ATR, nd * 16, lane), o[nd]);
+            for (int nd = 0; nd < ND; ++nd) o[nd] = mfma16(ap, tr_frag<VR>(Vs + ks * 32 * VR, nd * 16, lane), o[nd]);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int qi = q0 + g * 4 + r;
             if (qi < Nq) {
                 const float inv = 1.f / sum[r];
-                bf16_t* op = out + ((size_t)b * Nq + qi) * ld_o + h * 64 + l15;
+                bf16_t* op = out + ((size_t)b * Nq + qi) * ld_o + h * HD + l15;
 #pragma unroll
-                for (int nd = 0; nd < 4; ++nd) op[nd * 16] = f2bf(o[nd][r] * inv);
+                for (int nd = 0; nd < ND; ++nd) op[nd * 16] = f2bf(o[nd][r] * inv);
                 if (l15 == 0) lse[((size_t)b * heads + h) * Nq + qi] = mx[r] + __logf(sum[r]);
             }
         }
@@ -1051,63 +1071,64 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma_k(const bf16_t* __restrict_
     }
 }
 
-// delta[b][h][q] = sum_d dO[q][h*64 + d] * O[q][h*64 + d]   (= sum_keys P dP: lets the backward treat key ranges independently)
-template <typename T>
+// delta[b][h][q] = sum_d dO[q][h*HD + d] * O[q][h*HD + d]   (= sum_keys P dP: lets the backward treat key ranges independently)
+template <typename T, int HD>
 __global__ __launch_bounds__(256) void attn_delta_k(const T* __restrict__ dout, int ld_do, const T* __restrict__ o, int ld_o, float* __restrict__ delta, int B, int Nq, int heads) {
     const int lane = threadIdx.x & 63;
     const size_t item = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), total = (size_t)B * Nq * heads;
     if (item >= total) return;
     const int h = (int)(item % heads); const size_t bq = item / heads;          // bq = b * Nq + q
-    float v = TT<T>::ld(dout + bq * ld_do + h * 64 + lane) * TT<T>::ld(o + bq * ld_o + h * 64 + lane);
+    float v = lane < HD ? TT<T>::ld(dout + bq * ld_do + h * HD + lane) * TT<T>::ld(o + bq * ld_o + h * HD + lane) : 0.f;
     v = wave_sum(v);
     if (lane == 0) { const size_t b = bq / Nq, qi = bq % Nq; delta[(b * heads + h) * Nq + qi] = v; }
 }
 
 // backward for the keys [key0, key0 + NKB*64) of one (b, head); the block walks 64-query tiles blockIdx.x, blockIdx.x + gridDim.x, ...:
 //   S = Q K^T, dP = dO V^T (MFMA) -> P = exp(S scale - lse), dS = P (dP - delta) scale
-//   dQ (+)= dS K ; dK += dS^T Q, dV += P^T dO accumulate in registers over the tiles of the block and leave as ONE fp32 partial [2][NPT][64]
+//   dQ (+)= dS K ; dK += dS^T Q, dV += P^T dO accumulate in registers over the tiles of the block and leave as ONE fp32 partial [2][NPT][HD]
 //   per block (summed by attn_bwd_kv_reduce_k).  K, V, Q and dO tiles are staged row-major with 16-byte copies; every product whose contraction
 //   runs over tile rows (keys for dQ, queries for dK / dV) reads its B operand with the transposing LDS read (tr_frag), so nothing is transposed.
-template <int NKB>
+//   HD = 32: S and dP are one MFMA per tile, dQ / dK / dV have 2 column blocks instead of 4.
+template <int NKB, int HD>
 __global__ __launch_bounds__(256) void attn_bwd_mfma_k(const bf16_t* __restrict__ q, int ld_q, const bf16_t* __restrict__ kv, int ld_kv, const bf16_t* __restrict__ dout, int ld_do,
                                                        const float* __restrict__ lse, const float* __restrict__ delta, bf16_t* __restrict__ dq, int ld_dq, float* __restrict__ part,
                                                        int Nq, int Nkv, int heads, float scale, int key0, int NPT, int dq_acc) {
-    constexpr int NP = NKB * 64, NT = NP / 16, KR = 72, TR = NP + 8, NKT = NT / 4;
+    constexpr int NP = NKB * 64, NT = NP / 16, KR = 72, TR = NP + 8, NKT = NT / 4, DR = at_tr<HD>(), VR = HD + 8, ND = HD / 16, CH = HD / 8, CHS = HD == 64 ? 3 : 2, KC = HD / 32;
     extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
-    bf16_t* Ks = smem;                    // [NP][ATR] K rows: B of S = Q K^T (16-byte reads) and of dQ = dS K (tr_frag, contraction = keys)
-    bf16_t* Vs = Ks + NP * ATR;           // [NP][KR]  V rows: B of dP = dO V^T
-    bf16_t* Qs = Vs + NP * KR;            // [64][ATR] Q tile  [q][d]: A of S, B of dK (tr_frag, contraction = queries)
-    bf16_t* Gs = Qs + 64 * ATR;           // [64][ATR] dO tile [q][d]: A of dP, B of dV
-    bf16_t* Sa = Gs + 64 * ATR;           // [4][16][TR] dS, A layout per wave (perm_frag over keys)
+    bf16_t* Ks = smem;                    // [NP][DR]  K rows: B of S = Q K^T (16-byte reads) and of dQ = dS K (tr_frag, contraction = keys)
+    bf16_t* Vs = Ks + NP * DR;            // [NP][VR]  V rows: B of dP = dO V^T
+    bf16_t* Qs = Vs + NP * VR;            // [64][DR]  Q tile  [q][d]: A of S, B of dK (tr_frag, contraction = queries)
+    bf16_t* Gs = Qs + 64 * DR;            // [64][DR]  dO tile [q][d]: A of dP, B of dV
+    bf16_t* Sa = Gs + 64 * DR;            // [4][16][TR] dS, A layout per wave (perm_frag over keys)
     bf16_t* St = Sa + 64 * TR;            // [NP][KR]  dS transposed [key][q]  (perm_frag over queries)
     bf16_t* Pt = St + NP * KR;            // [NP][KR]  P transposed  [key][q]
     const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
     const bf16_t* kvb = kv + (size_t)b * Nkv * ld_kv;
-    for (int i = threadIdx.x; i < NP * 8; i += 256) {
-        const int kl = i >> 3, ch = i & 7, key = key0 + kl;
+    for (int i = threadIdx.x; i < NP * CH; i += 256) {
+        const int kl = i >> CHS, ch = i & (CH - 1), key = key0 + kl;
         uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
-        if (key < Nkv) { kk = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + h * 64 + ch * 8);
-                         vv = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + heads * 64 + h * 64 + ch * 8); }
-        *reinterpret_cast<uint4*>(Ks + kl * ATR + ch * 8) = kk;
-        *reinterpret_cast<uint4*>(Vs + kl * KR + ch * 8) = vv;
+        if (key < Nkv) { kk = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + h * HD + ch * 8);
+                         vv = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + heads * HD + h * HD + ch * 8); }
+        *reinterpret_cast<uint4*>(Ks + kl * DR + ch * 8) = kk;
+        *reinterpret_cast<uint4*>(Vs + kl * VR + ch * 8) = vv;
     }
-    f32x4v ak[NKT][4], av[NKT][4];
+    f32x4v ak[NKT][ND], av[NKT][ND];
 #pragma unroll
     for (int i = 0; i < NKT; ++i)
 #pragma unroll
-        for (int nd = 0; nd < 4; ++nd) { ak[i][nd] = f32x4v{0.f, 0.f, 0.f, 0.f}; av[i][nd] = ak[i][nd]; }
+        for (int nd = 0; nd < ND; ++nd) { ak[i][nd] = f32x4v{0.f, 0.f, 0.f, 0.f}; av[i][nd] = ak[i][nd]; }
     bf16_t* sa = Sa + wid * 16 * TR;
     const int ntile = (Nq + 63) / 64;
     for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
         const int qt0 = tile * 64;
         __syncthreads();                                                  // the previous tile's readers of Qs / Gs / St / Pt are done (and K / V are in)
-        for (int i = threadIdx.x; i < 64 * 8; i += 256) {
-            const int ql = i >> 3, ch = i & 7, qi = qt0 + ql;
+        for (int i = threadIdx.x; i < 64 * CH; i += 256) {
+            const int ql = i >> CHS, ch = i & (CH - 1), qi = qt0 + ql;
             uint4 qq = make_uint4(0, 0, 0, 0), gg = qq;
-            if (qi < Nq) { qq = *reinterpret_cast<const uint4*>(q + ((size_t)b * Nq + qi) * ld_q + h * 64 + ch * 8);
-                           gg = *reinterpret_cast<const uint4*>(dout + ((size_t)b * Nq + qi) * ld_do + h * 64 + ch * 8); }
-            *reinterpret_cast<uint4*>(Qs + ql * ATR + ch * 8) = qq;
-            *reinterpret_cast<uint4*>(Gs + ql * ATR + ch * 8) = gg;
+            if (qi < Nq) { qq = *reinterpret_cast<const uint4*>(q + ((size_t)b * Nq + qi) * ld_q + h * HD + ch * 8);
+                           gg = *reinterpret_cast<const uint4*>(dout + ((size_t)b * Nq + qi) * ld_do + h * HD + ch * 8); }
+            *reinterpret_cast<uint4*>(Qs + ql * DR + ch * 8) = qq;
+            *reinterpret_cast<uint4*>(Gs + ql * DR + ch * 8) = gg;
         }
         const int q0 = qt0 + wid * 16;
         float L[4], D[4]; bool rok[4];
@@ -1119,22 +1140,27 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_k(const bf16_t* __restrict_
             L[r] = lse[li]; D[r] = delta[li];
         }
         __syncthreads();
-        const bf16_t* qrow = Qs + (wid * 16 + l15) * ATR + g * 8; const bf16_t* grow = Gs + (wid * 16 + l15) * ATR + g * 8;
-        const uint4 aq0 = *reinterpret_cast<const uint4*>(qrow), aq1 = *reinterpret_cast<const uint4*>(qrow + 32);
-        const uint4 ag0 = *reinterpret_cast<const uint4*>(grow), ag1 = *reinterpret_cast<const uint4*>(grow + 32);
+        const bf16_t* qrow = Qs + (wid * 16 + l15) * DR + g * 8; const bf16_t* grow = Gs + (wid * 16 + l15) * DR + g * 8;
+        uint4 aq[KC], ag[KC];
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc) aq[kc] = *reinterpret_cast<const uint4*>(qrow + kc * 32);
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc) ag[kc] = *reinterpret_cast<const uint4*>(grow + kc * 32);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const bf16_t* kp = Ks + (nt * 16 + l15) * ATR + g * 8; const bf16_t* vp = Vs + (nt * 16 + l15) * KR + g * 8;
+            const bf16_t* kp = Ks + (nt * 16 + l15) * DR + g * 8; const bf16_t* vp = Vs + (nt * 16 + l15) * VR + g * 8;
             f32x4v s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-            s = mfma16(aq0, *reinterpret_cast<const uint4*>(kp), s); s = mfma16(aq1, *reinterpret_cast<const uint4*>(kp + 32), s);
-            dp = mfma16(ag0, *reinterpret_cast<const uint4*>(vp), dp); dp = mfma16(ag1, *reinterpret_cast<const uint4*>(vp + 32), dp);
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc) s = mfma16(aq[kc], *reinterpret_cast<const uint4*>(kp + kc * 32), s);
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc) dp = mfma16(ag[kc], *reinterpret_cast<const uint4*>(vp + kc * 32), dp);
             const bool kok = key0 + nt * 16 + l15 < Nkv;
             bf16_t pb[4], sb[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float p = (kok && rok[r]) ? __expf(s[r] * scale - L[r]) : 0.f;
                 const float ds = p * (dp[r] - D[r]) * scale;
-                pb[r] = f2bf(p); sb[r] = f2bf(ds);
+                pb[r] = f2bf_trans(p); sb[r] = f2bf(ds);
                 sa[(g * 4 + r) * TR + nt * 16 + l15] = sb[r];
             }
             // transposed tiles [key][query]: 4 consecutive queries of this lane -> one 8-byte store each
@@ -1143,22 +1169,22 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_k(const bf16_t* __restrict_
             *reinterpret_cast<uint2*>(Pt + key * KR + qc) = make_uint2((unsigned)pb[0] | ((unsigned)pb[1] << 16), (unsigned)pb[2] | ((unsigned)pb[3] << 16));
         }
         __syncthreads();
-        // dQ = dS K  (this wave's 16 queries x 64 dims, contraction over the keys of this range)
-        f32x4v dqa[4];
+        // dQ = dS K  (this wave's 16 queries x HD dims, contraction over the keys of this range)
+        f32x4v dqa[ND];
 #pragma unroll
-        for (int nd = 0; nd < 4; ++nd) dqa[nd] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        for (int nd = 0; nd < ND; ++nd) dqa[nd] = f32x4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < NP / 32; ++ks) {
             const uint4 a = perm_frag(sa + l15 * TR, ks * 32, g);
 #pragma unroll
-            for (int nd = 0; nd < 4; ++nd) dqa[nd] = mfma16(a, tr_frag(Ks + ks * 32 * ATR, nd * 16, lane), dqa[nd]);
+            for (int nd = 0; nd < ND; ++nd) dqa[nd] = mfma16(a, tr_frag<DR>(Ks + ks * 32 * DR, nd * 16, lane), dqa[nd]);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (rok[r]) {
-                bf16_t* dp_ = dq + ((size_t)b * Nq + q0 + g * 4 + r) * ld_dq + h * 64 + l15;
+                bf16_t* dp_ = dq + ((size_t)b * Nq + q0 + g * 4 + r) * ld_dq + h * HD + l15;
 #pragma unroll
-                for (int nd = 0; nd < 4; ++nd) dp_[nd * 16] = f2bf(dq_acc ? bf2f(dp_[nd * 16]) + dqa[nd][r] : dqa[nd][r]);
+                for (int nd = 0; nd < ND; ++nd) dp_[nd * 16] = f2bf(dq_acc ? bf2f(dp_[nd * 16]) + dqa[nd][r] : dqa[nd][r]);
             }
         }
         // dK += dS^T Q, dV += P^T dO : this wave's key tiles (kt = wid, wid + 4, ...), contraction over the 64 queries of the tile
@@ -1170,22 +1196,22 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_k(const bf16_t* __restrict_
                 const uint4 as = perm_frag(St + (kt * 16 + l15) * KR, ks * 32, g);
                 const uint4 ap = perm_frag(Pt + (kt * 16 + l15) * KR, ks * 32, g);
 #pragma unroll
-                for (int nd = 0; nd < 4; ++nd) {
-                    ak[i][nd] = mfma16(as, tr_frag(Qs + ks * 32 * ATR, nd * 16, lane), ak[i][nd]);
-                    av[i][nd] = mfma16(ap, tr_frag(Gs + ks * 32 * ATR, nd * 16, lane), av[i][nd]);
+                for (int nd = 0; nd < ND; ++nd) {
+                    ak[i][nd] = mfma16(as, tr_frag<DR>(Qs + ks * 32 * DR, nd * 16, lane), ak[i][nd]);
+                    av[i][nd] = mfma16(ap, tr_frag<DR>(Gs + ks * 32 * DR, nd * 16, lane), av[i][nd]);
                 }
             }
         }
     }
-    float* dst = part + ((((size_t)b * heads + h) * gridDim.x + blockIdx.x) * 2) * (size_t)NPT * 64;
+    float* dst = part + ((((size_t)b * heads + h) * gridDim.x + blockIdx.x) * 2) * (size_t)NPT * HD;
 #pragma unroll
     for (int i = 0; i < NKT; ++i) {
         const int kt = wid + 4 * i;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const size_t row = (size_t)(key0 + kt * 16 + g * 4 + r) * 64 + l15;
+            const size_t row = (size_t)(key0 + kt * 16 + g * 4 + r) * HD + l15;
 #pragma unroll
-            for (int nd = 0; nd < 4; ++nd) { dst[row + nd * 16] = ak[i][nd][r]; dst[(size_t)NPT * 64 + row + nd * 16] = av[i][nd][r]; }
+            for (int nd = 0; nd < ND; ++nd) { dst[row + nd * 16] = ak[i][nd][r]; dst[(size_t)NPT * HD + row + nd * 16] = av[i][nd][r]; }
         }
     }
 }
@@ -1449,7 +1475,7 @@ int pn2_dwconv3x3_wgrad(int dt, const void* dz, const void* x, float* partial, i
     return 0;
 }
 
-static int attn_geom(int Nkv, int heads, int head_dim) { return (head_dim == 64 && Nkv >= 1 && Nkv <= 64 * AT_MAXK && heads >= 1) ? 0 : -2; }
+static int attn_geom(int Nkv, int heads, int head_dim) { return ((head_dim == 32 || head_dim == 64) && Nkv >= 1 && Nkv <= 64 * AT_MAXK && heads >= 1) ? 0 : -2; }
 
 // persistent attention blocks per launch: the blocks of one (b, head) share its K / V and walk the query tiles between them
 static int attn_target_blocks() { return 512; }
@@ -1460,28 +1486,28 @@ static int attn_bwd_gx(int B, int heads, int Nq) {
     return gx > ntile ? ntile : (gx < 1 ? 1 : gx);
 }
 
-int pn2_attn_fwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads, int head_dim,
-                 float scale, void* stream) {
-    if (!q || !kv || !out || !lse) return -1;
-    if (int rc = attn_geom(Nkv, heads, head_dim)) return rc;
+}  // extern "C"
+
+template <int HD>
+static int attn_fwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads,
+                         float scale, hipStream_t st) {
     const int NK = (Nkv + 63) / 64, NP = NK * 64;
-    const size_t lds = (size_t)2 * 64 * (NP + 1) * 4;
+    const size_t lds = (size_t)2 * HD * (NP + 1) * 4;
     const int qpb = 64;
     const dim3 grid((Nq + qpb - 1) / qpb, heads, B);
-    hipStream_t st = (hipStream_t)stream;
-#define PN2_ATTN_FWD(NKV) { if (lds > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_k<T, NKV>), \
+#define PN2_ATTN_FWD(NKV) { if (lds > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_k<T, NKV, HD>), \
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; } } \
-        hipLaunchKernelGGL((attn_fwd_k<T, NKV>), grid, dim3(256), lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (T*)out, ld_o, lse, Nq, Nkv, heads, scale, qpb); }
+        hipLaunchKernelGGL((attn_fwd_k<T, NKV, HD>), grid, dim3(256), lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (T*)out, ld_o, lse, Nq, Nkv, heads, scale, qpb); }
     constexpr bool use_mfma = true;
     if (dt == PN2_BF16 && use_mfma && (ld_q % 8) == 0 && (ld_kv % 8) == 0 && (ld_o % 8) == 0) {
         const int NPK = NK == 3 ? 256 : NP;                        // 129..192 keys run the 256-key instantiation (zero-padded keys are masked)
-        const size_t lm = ((size_t)NPK * 72 + (size_t)NPK * ATR + 8 * 16 * (NPK + 8)) * 2;
+        const size_t lm = ((size_t)NPK * (HD + 8) + (size_t)NPK * at_tr<HD>() + 8 * 16 * (NPK + 8)) * 2;
         const int ntile = (Nq + 127) / 128;
         int gx = (attn_target_blocks() + B * heads - 1) / (B * heads); if (gx > ntile) gx = ntile; if (gx < 1) gx = 1;
         const dim3 gm(gx, heads, B);
-#define PN2_ATTN_FWD_M(NKV) { if (lm > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_mfma_k<NKV>), \
+#define PN2_ATTN_FWD_M(NKV) { if (lm > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_mfma_k<NKV, HD>), \
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); done = true; } } \
-        hipLaunchKernelGGL((attn_fwd_mfma_k<NKV>), gm, dim3(512), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (bf16_t*)out, ld_o, lse, Nq, Nkv, heads, scale); }
+        hipLaunchKernelGGL((attn_fwd_mfma_k<NKV, HD>), gm, dim3(512), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (bf16_t*)out, ld_o, lse, Nq, Nkv, heads, scale); }
         if (NK == 1) PN2_ATTN_FWD_M(1) else if (NK == 2) PN2_ATTN_FWD_M(2) else PN2_ATTN_FWD_M(4)
 #undef PN2_ATTN_FWD_M
         PN2_CHECK_LAUNCH();
@@ -1498,6 +1524,64 @@ static bool attn_use_mfma(int dt, int ld_a, int ld_b) {
     return on && dt == PN2_BF16 && (ld_a % 8) == 0 && (ld_b % 8) == 0;
 }
 
+template <int HD>
+static int attn_bwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld_kv, const void* out, int ld_o, const void* dout, int ld_do, const float* lse, void* dq, int ld_dq,
+                         void* dkv, int ld_dkv, float* partial, float* delta, int B, int Nq, int Nkv, int heads, float scale, hipStream_t st) {
+    const int NK = (Nkv + 63) / 64, NP = NK * 64;
+    if (attn_use_mfma(dt, ld_q, ld_kv) && (ld_do % 8) == 0 && (ld_dq % 8) == 0) {
+        const int nqt = attn_bwd_gx(B, heads, Nq);                   // persistent blocks (= partial slots) per (b, head)
+        hipLaunchKernelGGL((attn_delta_k<bf16_t, HD>), dim3((unsigned)(((size_t)B * Nq * heads + 3) / 4)), dim3(256), 0, st, (const bf16_t*)dout, ld_do, (const bf16_t*)out, ld_o, delta, B, Nq, heads);
+        const dim3 grid(nqt, heads, B);
+        // 128 keys per launch at both head dims: at HD = 32 a 256-key block would need 161 KiB of LDS (its dS / P transposes are 64 queries wide
+        // whatever HD is), one KiB over the CU's 160
+        for (int key0 = 0; key0 < NP; key0 += 128) {
+            const int nkb = NP - key0 >= 128 ? 2 : 1;
+            const int np = nkb * 64;
+            const size_t lm = ((size_t)np * at_tr<HD>() + (size_t)np * (HD + 8) + 2 * 64 * at_tr<HD>() + 64 * (np + 8) + 2 * (size_t)np * 72) * 2;
+            if (nkb == 2) {
+                static bool done = false;
+                if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_k<2, HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); done = true; }
+                hipLaunchKernelGGL((attn_bwd_mfma_k<2, HD>), grid, dim3(256), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta, (bf16_t*)dq, ld_dq,
+                                   partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0);
+            } else {
+                static bool done1 = false;
+                if (!done1) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_k<1, HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); done1 = true; }
+                hipLaunchKernelGGL((attn_bwd_mfma_k<1, HD>), grid, dim3(256), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta, (bf16_t*)dq, ld_dq,
+                                   partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0);
+            }
+        }
+        hipLaunchKernelGGL((attn_bwd_kv_reduce_k<bf16_t, HD>), dim3(Nkv, heads, B), dim3(HD), 0, st, partial, (bf16_t*)dkv, ld_dkv, Nkv, NP, heads, nqt);
+        PN2_CHECK_LAUNCH();
+        return 0;
+    }
+    const int nqb = (Nq + AT_QCHUNK - 1) / AT_QCHUNK;
+    // a bf16 view that the MFMA kernels cannot take: its partial has pn2_attn_bwd_blocks(bf16) = attn_bwd_gx slots, fewer than nqb for many (b, head)
+    if (dt == PN2_BF16 && nqb > attn_bwd_gx(B, heads, Nq)) return -2;
+    const int QB = NK == 4 ? 2 : AT_QB;                 // 256 keys: smaller query groups so that K, V and the tiles fit the 160 KiB of LDS
+    const size_t lds = ((size_t)2 * HD * (NP + 1) + 2 * 4 * QB * NP + 2 * 4 * QB * HD) * 4;
+    const dim3 grid(nqb, heads, B);
+#define PN2_ATTN_BWD(NKV, QBV) { if (lds > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_k<T, NKV, QBV, HD>), \
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; } } \
+        hipLaunchKernelGGL((attn_bwd_k<T, NKV, QBV, HD>), grid, dim3(256), lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (const T*)dout, ld_do, lse, (T*)dq, ld_dq, \
+                           partial, Nq, Nkv, heads, scale); }
+    VIT_DISPATCH(dt, {
+        if (NK == 1) PN2_ATTN_BWD(1, AT_QB) else if (NK == 2) PN2_ATTN_BWD(2, AT_QB) else if (NK == 3) PN2_ATTN_BWD(3, AT_QB) else PN2_ATTN_BWD(4, 2)
+        hipLaunchKernelGGL((attn_bwd_kv_reduce_k<T, HD>), dim3(Nkv, heads, B), dim3(HD), 0, st, partial, (T*)dkv, ld_dkv, Nkv, NP, heads, nqb); })
+#undef PN2_ATTN_BWD
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" {
+
+int pn2_attn_fwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads, int head_dim,
+                 float scale, void* stream) {
+    if (!q || !kv || !out || !lse) return -1;
+    if (int rc = attn_geom(Nkv, heads, head_dim)) return rc;
+    return head_dim == 32 ? attn_fwd_impl<32>(dt, q, ld_q, kv, ld_kv, out, ld_o, lse, B, Nq, Nkv, heads, scale, (hipStream_t)stream)
+                          : attn_fwd_impl<64>(dt, q, ld_q, kv, ld_kv, out, ld_o, lse, B, Nq, Nkv, heads, scale, (hipStream_t)stream);
+}
+
 int pn2_attn_bwd_blocks(int dt, int B, int heads, int Nq) {
     if (Nq < 1 || B < 1 || heads < 1) return -1;
     return dt == PN2_BF16 ? attn_bwd_gx(B, heads, Nq) : (Nq + AT_QCHUNK - 1) / AT_QCHUNK;
@@ -1507,46 +1591,8 @@ int pn2_attn_bwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, con
                  void* dkv, int ld_dkv, float* partial, float* delta, int B, int Nq, int Nkv, int heads, int head_dim, float scale, void* stream) {
     if (!q || !kv || !out || !dout || !lse || !dq || !dkv || !partial || !delta) return -1;
     if (int rc = attn_geom(Nkv, heads, head_dim)) return rc;
-    const int NK = (Nkv + 63) / 64, NP = NK * 64;
-    hipStream_t st = (hipStream_t)stream;
-    if (attn_use_mfma(dt, ld_q, ld_kv) && (ld_do % 8) == 0 && (ld_dq % 8) == 0) {
-        const int nqt = attn_bwd_gx(B, heads, Nq);                   // persistent blocks (= partial slots) per (b, head)
-        hipLaunchKernelGGL(attn_delta_k<bf16_t>, dim3((unsigned)(((size_t)B * Nq * heads + 3) / 4)), dim3(256), 0, st, (const bf16_t*)dout, ld_do, (const bf16_t*)out, ld_o, delta, B, Nq, heads);
-        const dim3 grid(nqt, heads, B);
-        for (int key0 = 0; key0 < NP; key0 += 128) {
-            const int nkb = NP - key0 >= 128 ? 2 : 1;
-            const int np = nkb * 64;
-            const size_t lm = ((size_t)np * ATR + (size_t)np * 72 + 2 * 64 * ATR + 64 * (np + 8) + 2 * (size_t)np * 72) * 2;
-            if (nkb == 2) {
-                static bool done = false;
-                if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_k<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); done = true; }
-                hipLaunchKernelGGL(attn_bwd_mfma_k<2>, grid, dim3(256), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta, (bf16_t*)dq, ld_dq,
-                                   partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0);
-            } else {
-                static bool done1 = false;
-                if (!done1) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_k<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); done1 = true; }
-                hipLaunchKernelGGL(attn_bwd_mfma_k<1>, grid, dim3(256), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta, (bf16_t*)dq, ld_dq,
-                                   partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0);
-            }
-        }
-        hipLaunchKernelGGL(attn_bwd_kv_reduce_k<bf16_t>, dim3(Nkv, heads, B), dim3(64), 0, st, partial, (bf16_t*)dkv, ld_dkv, Nkv, NP, heads, nqt);
-        PN2_CHECK_LAUNCH();
-        return 0;
-    }
-    const int nqb = (Nq + AT_QCHUNK - 1) / AT_QCHUNK;
-    const int QB = NK == 4 ? 2 : AT_QB;                 // 256 keys: smaller query groups so that K, V and the tiles fit the 160 KiB of LDS
-    const size_t lds = ((size_t)2 * 64 * (NP + 1) + 2 * 4 * QB * NP + 2 * 4 * QB * 64) * 4;
-    const dim3 grid(nqb, heads, B);
-#define PN2_ATTN_BWD(NKV, QBV) { if (lds > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_k<T, NKV, QBV>), \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; } } \
-        hipLaunchKernelGGL((attn_bwd_k<T, NKV, QBV>), grid, dim3(256), lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (const T*)dout, ld_do, lse, (T*)dq, ld_dq, \
-                           partial, Nq, Nkv, heads, scale); }
-    VIT_DISPATCH(dt, {
-        if (NK == 1) PN2_ATTN_BWD(1, AT_QB) else if (NK == 2) PN2_ATTN_BWD(2, AT_QB) else if (NK == 3) PN2_ATTN_BWD(3, AT_QB) else PN2_ATTN_BWD(4, 2)
-        hipLaunchKernelGGL(attn_bwd_kv_reduce_k<T>, dim3(Nkv, heads, B), dim3(64), 0, st, partial, (T*)dkv, ld_dkv, Nkv, NP, heads, nqb); })
-#undef PN2_ATTN_BWD
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return head_dim == 32 ? attn_bwd_impl<32>(dt, q, ld_q, kv, ld_kv, out, ld_o, dout, ld_do, lse, dq, ld_dq, dkv, ld_dkv, partial, delta, B, Nq, Nkv, heads, scale, (hipStream_t)stream)
+                          : attn_bwd_impl<64>(dt, q, ld_q, kv, ld_kv, out, ld_o, dout, ld_do, lse, dq, ld_dq, dkv, ld_dkv, partial, delta, B, Nq, Nkv, heads, scale, (hipStream_t)stream);
 }
 
 int pn2_scale_samples(int dt, const void* x, void* y, const float* scale, const void* res, int N, long long per_sample, void* stream) {

@@ -17,11 +17,11 @@ class EMCADNet(nn.Module):
         if not self.dual:
             raise NotImplementedError("only the dual-supervision EMCADNet (dual=True, the PraNet-V2 configuration) is built")
         self.conv = nn.Sequential(nn.Conv2d(1, 3, kernel_size=1), nn.BatchNorm2d(3), nn.ReLU(inplace=True))
-        if encoder not in ('pvt_v2_b1', 'pvt_v2_b2', 'pvt_v2_b3', 'pvt_v2_b4', 'pvt_v2_b5'):
-            raise NotImplementedError(f"encoder {encoder}: only the head_dim-64 PVTv2 encoders are built")
+        if encoder not in ('pvt_v2_b0', 'pvt_v2_b1', 'pvt_v2_b2', 'pvt_v2_b3', 'pvt_v2_b4', 'pvt_v2_b5'):
+            raise NotImplementedError(f"encoder {encoder}: only the PVTv2 encoders are built")
         self.backbone = getattr(pvtv2, encoder)()
         path = f'./pretrained_pth/pvt/{encoder}.pth'
-        channels = [512, 320, 128, 64]
+        channels = [256, 160, 64, 32] if encoder == 'pvt_v2_b0' else [512, 320, 128, 64]     # networks.py:25-28
         if pretrain is True and (os.path.exists(path) or os.environ.get('PN2_NO_PRETRAINED', '0') != '1'):
             save_model = torch.load(path)
             model_dict = self.backbone.state_dict()

@@ -203,7 +203,7 @@ def _variant(name, embed_dims, num_heads, mlp_ratios, depths, sr_ratios=(8, 4, 2
     return _V
 
 
-# pvtv2.py:378-436.  The attention kernel is built for head_dim 64, which b1..b5 use; b0 (head_dim 32) constructs but cannot run.
+# pvtv2.py:378-436.  The attention kernels take head_dim 64 (b1..b5) and 32 (b0, every stage).
 pvt_v2_b0 = _variant("pvt_v2_b0", (32, 64, 160, 256), (1, 2, 5, 8), (8, 8, 4, 4), (2, 2, 2, 2))
 pvt_v2_b1 = _variant("pvt_v2_b1", (64, 128, 320, 512), (1, 2, 5, 8), (8, 8, 4, 4), (2, 2, 2, 2))
 pvt_v2_b2 = _variant("pvt_v2_b2", (64, 128, 320, 512), (1, 2, 5, 8), (8, 8, 4, 4), (3, 4, 6, 3))

@@ -1,5 +1,9 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the spatial-reduction attention kernels on the PVTv2-B2 shapes of configs 4 (352^2) and 5 (512^2), bs=16, bf16."""
+"""Micro-benchmark of the spatial-reduction attention kernels, bf16.  Usage: attn_micro.py [head_dim]
+head_dim 64 (default): the PVTv2-B2 shapes of configs 4 (352^2) and 5 (512^2), bs=16.
+head_dim 32: the PVTv2-B0 shapes (16 x 512^2, 16 x 352^2, 6 x 224^2), each also run at head_dim 64 on the same (B, Nq, Nkv, heads), with two floors:
+the HBM bytes of q / kv / out / lse (forward) and q / kv / out / dO / lse / dq / dkv (backward) at 8 TB/s, and the exp count (B heads Nq Nkv, twice
+in the backward, which recomputes P) at one v_exp_f32 per lane per 4 cycles: 256 CUs x 4 SIMDs x 16 lanes/clk x 2.4 GHz."""
 import ctypes as C
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,33 +25,60 @@ def timeit(fn, reps=20):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-def bench(B, Nq, Nkv, heads):
+HBM, EXP = 8e12, 256 * 4 * 16 * 2.4e9
+
+
+def bench(B, Nq, Nkv, heads, hd=64, floors=False):
     dev = "cuda"; st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    Cc = heads * 64
+    Cc = heads * hd
     q = torch.randn(B, Nq, Cc, device=dev).bfloat16(); kv = torch.randn(B, Nkv, 2 * Cc, device=dev).bfloat16()
     o = torch.empty_like(q); do = torch.randn_like(q); dq = torch.empty_like(q); dkv = torch.empty_like(kv)
     lse = torch.empty(B, heads, Nq, device=dev); delta = torch.empty(B, heads, Nq, device=dev)
     nb = call.pn2_attn_bwd_blocks(BF16, B, heads, Nq)
-    part = torch.empty(B, heads, nb, 2, (Nkv + 63) // 64 * 64, 64, device=dev)
-    sc = 0.125
-    t_f = timeit(lambda: call.pn2_attn_fwd(BF16, P(q), Cc, P(kv), 2 * Cc, P(o), Cc, P(lse), B, Nq, Nkv, heads, 64, sc, st))
-    t_b = timeit(lambda: call.pn2_attn_bwd(BF16, P(q), Cc, P(kv), 2 * Cc, P(o), Cc, P(do), Cc, P(lse), P(dq), Cc, P(dkv), 2 * Cc, P(part), P(delta), B, Nq, Nkv, heads, 64, sc, st))
-    fl = 4.0 * B * heads * Nq * Nkv * 64
+    part = torch.empty(B, heads, nb, 2, (Nkv + 63) // 64 * 64, hd, device=dev)
+    sc = hd ** -0.5
+    t_f = timeit(lambda: call.pn2_attn_fwd(BF16, P(q), Cc, P(kv), 2 * Cc, P(o), Cc, P(lse), B, Nq, Nkv, heads, hd, sc, st))
+    t_b = timeit(lambda: call.pn2_attn_bwd(BF16, P(q), Cc, P(kv), 2 * Cc, P(o), Cc, P(do), Cc, P(lse), P(dq), Cc, P(dkv), 2 * Cc, P(part), P(delta), B, Nq, Nkv, heads, hd, sc, st))
+    fl = 4.0 * B * heads * Nq * Nkv * hd
     # numerics against torch (fp32 math on the bf16-rounded inputs), first two samples
     nb_ = min(B, 2)
-    qq = q[:nb_].float().reshape(nb_, Nq, heads, 64).permute(0, 2, 1, 3).requires_grad_(True)
-    kk = kv[:nb_].float().reshape(nb_, Nkv, 2, heads, 64).permute(2, 0, 3, 1, 4).detach().requires_grad_(True)
+    qq = q[:nb_].float().reshape(nb_, Nq, heads, hd).permute(0, 2, 1, 3).requires_grad_(True)
+    kk = kv[:nb_].float().reshape(nb_, Nkv, 2, heads, hd).permute(2, 0, 3, 1, 4).detach().requires_grad_(True)
     r = ((qq @ kk[0].transpose(-2, -1)) * sc).softmax(-1) @ kk[1]
-    r.backward(do[:nb_].float().reshape(nb_, Nq, heads, 64).permute(0, 2, 1, 3))
+    r.backward(do[:nb_].float().reshape(nb_, Nq, heads, hd).permute(0, 2, 1, 3))
     ro = r.permute(0, 2, 1, 3).reshape(nb_, Nq, Cc)
     rel = lambda a, b: float((a.float() - b).norm() / b.norm())
     e_o = rel(o[:nb_], ro)
     e_q = rel(dq[:nb_], qq.grad.permute(0, 2, 1, 3).reshape(nb_, Nq, Cc))
     e_kv = rel(dkv[:nb_], kk.grad.permute(1, 3, 0, 2, 4).reshape(nb_, Nkv, 2 * Cc))
-    print(f"B{B} Nq{Nq:6d} Nkv{Nkv:4d} h{heads}: fwd {t_f:7.1f} us {fl/t_f/1e6:6.1f} TF/s | bwd(slots {nb:3d}) {t_b:7.1f} us {2.5*fl/t_b/1e6:6.1f} TF/s | rel err o {e_o:.1e} dq {e_q:.1e} dkv {e_kv:.1e}")
+    line = (f"B{B} Nq{Nq:6d} Nkv{Nkv:4d} h{heads}" + (f" hd{hd}" if floors else "") + f": fwd {t_f:7.1f} us {fl/t_f/1e6:6.1f} TF/s | bwd(slots {nb:3d}) {t_b:7.1f} us "
+            f"{2.5*fl/t_b/1e6:6.1f} TF/s | rel err o {e_o:.1e} dq {e_q:.1e} dkv {e_kv:.1e}")
+    if floors:
+        lse_b = 4 * B * heads * Nq
+        hf = (3 * q.numel() * 2 + kv.numel() * 2 + lse_b) / HBM * 1e6                       # q, kv, out, lse
+        hb = (5 * q.numel() * 2 + 2 * kv.numel() * 2 + 2 * lse_b) / HBM * 1e6                # q, kv, out, dO, lse, delta, dq, dkv
+        ex = B * heads * Nq * Nkv / EXP * 1e6
+        line += f" | floors fwd HBM {hf:6.1f} exp {ex:6.1f} us, bwd HBM {hb:6.1f} exp {2 * ex:6.1f} us"
+    print(line)
+    return t_f, t_b
+
+
+B0_SHAPES = [(16, 16384, 256, 1), (16, 4096, 256, 2), (16, 1024, 256, 5), (16, 256, 256, 8),       # 16 x 512^2
+             (16, 7744, 121, 1), (16, 1936, 121, 2), (16, 484, 121, 5), (16, 121, 121, 8),         # 16 x 352^2
+             (6, 3136, 49, 1), (6, 784, 49, 2), (6, 196, 49, 5), (6, 49, 49, 8)]                   # 6 x 224^2
 
 
 if __name__ == "__main__":
+    hd = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+    if hd == 32:
+        tot = [0.0] * 4
+        for shp in B0_SHAPES:
+            f32_, b32_ = bench(*shp, hd=32, floors=True)
+            f64_, b64_ = bench(*shp, hd=64, floors=True)
+            print(f"    hd32 / hd64: fwd {f32_ / f64_:.2f}  bwd {b32_ / b64_:.2f}")
+            tot = [a + b for a, b in zip(tot, (f32_, b32_, f64_, b64_))]
+        print(f"sum over the b0 shapes: hd32 fwd {tot[0]:.1f} bwd {tot[1]:.1f} us, hd64 fwd {tot[2]:.1f} bwd {tot[3]:.1f} us")
+        sys.exit(0)
     for shp in [(16, 7744, 121, 1), (16, 1936, 121, 2), (16, 484, 121, 5), (16, 121, 121, 8),
                 (16, 16384, 256, 1), (16, 4096, 256, 2), (16, 1024, 256, 5), (16, 256, 256, 8), (2, 256, 196, 2), (2, 256, 160, 2), (2, 200, 250, 1)]:
         bench(*shp)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """BASELINE config 5 on one GPU: EMCADNet(dual, K=9, pvt_v2_b2) forward + the reference trainer's 15-subset loss (torch ops, as trainer.py:106-140
-runs them) + backward + optimizer step through the nn.Module surface.  Usage: emcad_bench.py [batch] [size] [steps]"""
+runs them) + backward + optimizer step through the nn.Module surface.  Usage: [EMCAD_ENCODER=pvt_v2_b0] emcad_bench.py [batch] [size] [steps]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "pranet-v2_amd"))
@@ -16,7 +16,9 @@ size = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 pn2.set_compute_dtype("bf16")
 torch.manual_seed(0)
-model = EMCADNet(num_classes=9, kernel_sizes=[1, 3, 5], expansion_factor=2, activation="relu6", encoder="pvt_v2_b2", pretrain=False, dual=True).cuda().train()
+ENCODER = os.environ.get("EMCAD_ENCODER", "pvt_v2_b2")     # config 5 is pvt_v2_b2; pvt_v2_b0 is the small encoder (head_dim 32)
+ENC = "" if ENCODER == "pvt_v2_b2" else f" {ENCODER}"
+model = EMCADNet(num_classes=9, kernel_sizes=[1, 3, 5], expansion_factor=2, activation="relu6", encoder=ENCODER, pretrain=False, dual=True).cuda().train()
 GRAPH = os.environ.get("EMCAD_GRAPH", "0") == "1"          # replay the whole step (forward, loss, backward, AdamW) from one hipGraph
 opt = torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=1e-4, capturable=GRAPH)
 x = torch.randn(bs, 1, size, size, device="cuda")
@@ -48,13 +50,13 @@ if TRAINER:
     for _ in range(steps):
         l = tr.step(x, (label, bg))
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
-    print(f"EMCADNet dual K=9 bs={bs} {size}x{size} bf16 (Trainer, eager): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l[0]):.3f}")
+    print(f"EMCADNet dual K=9{ENC} bs={bs} {size}x{size} bf16 (Trainer, eager): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l[0]):.3f}")
     tr.capture(x, (label, bg), warmup=2)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(steps):
         l = tr.replay()
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
-    print(f"EMCADNet dual K=9 bs={bs} {size}x{size} bf16 (Trainer, hipGraph replay): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l[0]):.3f}")
+    print(f"EMCADNet dual K=9{ENC} bs={bs} {size}x{size} bf16 (Trainer, hipGraph replay): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l[0]):.3f}")
     with Recorder() as rec:
         tr.step(x, (label, bg))
     agg = rec.summary()
@@ -100,7 +102,7 @@ for _ in range(steps):
     r = run()
     l = l if GRAPH else r
 torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
-print(f"EMCADNet dual K=9 bs={bs} {size}x{size} bf16 ({'fused pn2.loss.mutation_loss' if FUSED else 'torch loss'}{', hipGraph replay' if GRAPH else ''}): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l.detach()):.3f}")
+print(f"EMCADNet dual K=9{ENC} bs={bs} {size}x{size} bf16 ({'fused pn2.loss.mutation_loss' if FUSED else 'torch loss'}{', hipGraph replay' if GRAPH else ''}): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l.detach()):.3f}")
 if GRAPH:
     sys.exit(0)
 with Recorder() as rec:
