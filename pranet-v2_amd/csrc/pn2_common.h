@@ -127,3 +127,18 @@ __device__ __forceinline__ void bl_range(int i, float r, int ac, int On, int& lo
 }
 
 #define PN2_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+// opt kernel K in to more than the default 64 KiB of dynamic LDS, once: the flag lives in a template keyed on the kernel, so every instantiation has exactly one
+template <auto K>
+inline void pn2_lds_opt_in(int lds_cap) {
+    static bool done = false;
+    if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap); done = true; }
+}
+// launch kernel K with `lds` bytes of dynamic LDS; lds_cap: the most this instantiation is ever launched with.  Returns 0 or the launch error.
+template <auto K, typename... A>
+inline int pn2_launch(dim3 grid, dim3 block, size_t lds, int lds_cap, hipStream_t st, const A&... args) {
+    if (lds_cap > 64 * 1024) pn2_lds_opt_in<K>(lds_cap);
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}

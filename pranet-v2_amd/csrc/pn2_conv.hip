@@ -2190,104 +2190,86 @@ inline int reduce_blocks(const pn2_pack_desc& p) {
     return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
 
+// descriptor fields above the PN2_CONV_* bits: d.flags bits 8..15 hold the optional per-shape tuning code (gemm_select), bits 16..19 the external split-K count
+constexpr int TUNE_KS2 = 0x40, TUNE_KS4 = 0x80;          // tuning code: intra-workgroup split-K over two / four K groups
+constexpr int TILE_KS2 = 0x100;          // bit 8 of a table's bm (pn2_conv_gemm_tile): the two-K-group table kernel
+inline int conv_tune(const pn2_conv_desc& d) { return (d.flags >> 8) & 0xff; }
+inline int conv_ksplit(const pn2_conv_desc& d) { return (d.flags >> 16) & 15; }
+inline bool conv_desc_ok(const pn2_conv_desc& d) {
+    return !(d.Cin_p % 8 || d.ld_in % 8 || d.Kp % 128 || (d.stride != 1 && d.stride != 2 && d.stride != 4 && d.stride != 8));
+}
+// 1 x 1, stride 1, no padding (pn2_conv_desc and pn2_wgrad_desc): the PW instantiations skip the tap / pixel decode
+template <typename D> inline bool is_pointwise(const D& d) { return d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0; }
+inline int conv_grid(const pn2_conv_desc& d, int bm, int bn) { return ((d.N * d.OH * d.OW + bm - 1) / bm) * ((d.Cout + bn - 1) / bn); }
+
 // dynamic LDS of the bf16 BatchNorm-backward epilogue for this launch (C tile + the operand tiles it needs)
 template <int BM, int BN>
-inline int ep2_lds_for(const pn2_conv_desc& d, const pn2_conv_ep& ep) {
+inline int ep2_lds(const pn2_conv_desc& d, const pn2_conv_ep& ep) {
     bool stat_a, y_a, acc, stat_b;
     ep2_needs(d, ep, stat_a, y_a, acc, stat_b);
     return ep2_layout<BM, BN>(stat_a, y_a, acc, stat_b, ep2_stat_c(ep)).total;
 }
 // table launches: the caller says what the jobs need (bits 1..4 of `ep`: statistics a, mask-from-activation a, +=, statistics b); no bits = everything
 template <int BM, int BN>
-inline int ep2_lds_bits(int bits) {
+inline int ep2_lds(int bits) {
     if (!(bits & 15)) bits = 15;
     return ep2_layout<BM, BN>(bits & 1, bits & 2, bits & 4, bits & 8).total;
 }
+// dynamic LDS (bytes) of the conv GEMM kernels for storage type T and one tile: the main loop's buffers and what the epilogues lay over them
+template <typename T, int BM, int BN, int WM>
+struct ConvLds {
+    static constexpr int stage = (BM + BN) * 128;                                           // one stage of a DMA ring
+    static constexpr int gather = 2 * (BM + BN) * (RS + lo_row<T>);                         // both operand buffers of the gather kernels
+    static constexpr int epi = BM * (BN * (int)sizeof(T) + 16) + 3 * WM * BN * 4;           // C tile + statistics rows
+    static constexpr int xch(int ks) { return (ks - 1) * BM * BN * 4; }                     // split-K: fp32 partial tiles handed between the K groups
+    static constexpr bool E2 = sizeof(T) == 2 && ep2_tile(BM, BN);                          // the ep2 layout serves this tile's statistics epilogue
+    // bytes of a launch whose main loop and plain epilogue need `lds`: with a statistics epilogue (EP) its ep2 layout (need: the descriptor and ep, or
+    // the bits of a table), else at least ep_lds_bytes
+    template <bool EP, typename... Need>
+    static int with_ep(int lds, const Need&... need) {
+        if constexpr (EP && E2) { const int e2 = ep2_lds<BM, BN>(need...); return e2 > lds ? e2 : lds; }
+        else if constexpr (EP) return lds < ep_lds_bytes(TT<T>::VEC) ? ep_lds_bytes(TT<T>::VEC) : lds;
+        else return lds;
+    }
+};
+constexpr int LDS_MAX = 160 * 1024;          // of a CU
+constexpr int imax(int a, int b) { return a > b ? a : b; }
 
 template <typename T, int BM, int BN, int WM, int WN, bool EP>
 int launch_gemm(const void* in, const void* wp, void* out, float* psum, float* psq, const pn2_conv_desc& d, const pn2_conv_ep& ep, hipStream_t st) {
-    const int M = d.N * d.OH * d.OW;
-    const int grid = ((M + BM - 1) / BM) * ((d.Cout + BN - 1) / BN);
-    constexpr int main_b = 2 * (BM + BN) * (RS + lo_row<T>), epi_b = BM * (BN * (int)sizeof(T) + 16) + 3 * WM * BN * 4;
-    constexpr bool E2 = EP && sizeof(T) == 2 && ep2_tile(BM, BN);
-    constexpr int ep_b = (EP && !E2) ? ep_lds_bytes(TT<T>::VEC) : 0;
-    constexpr int lds0 = (main_b > epi_b ? main_b : epi_b) > ep_b ? (main_b > epi_b ? main_b : epi_b) : ep_b;
-    int lds = lds0;
-    if (E2) { const int e2 = ep2_lds_for<BM, BN>(d, ep); if (e2 > lds) lds = e2; }
-    if (lds > 160 * 1024) return -4;
-    const bool pw = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0;
-    if (lds0 > 64 * 1024 || E2) {      // opt in to more than 64 KiB of dynamic LDS once per instantiation
-        static bool done = false;
-        if (!done) {
-            const int cap = E2 ? 160 * 1024 : lds0;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gather_gemm<T, BM, BN, WM, WN, true, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gather_gemm<T, BM, BN, WM, WN, false, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-            done = true;
-        }
-    }
-    if (pw) hipLaunchKernelGGL((conv_gather_gemm<T, BM, BN, WM, WN, true, EP>), dim3(grid), dim3(256), lds, st, (const T*)in, (const T*)wp, (T*)out, psum, psq, d, ep);
-    else hipLaunchKernelGGL((conv_gather_gemm<T, BM, BN, WM, WN, false, EP>), dim3(grid), dim3(256), lds, st, (const T*)in, (const T*)wp, (T*)out, psum, psq, d, ep);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    using L = ConvLds<T, BM, BN, WM>;
+    const int lds = L::template with_ep<EP>(imax(L::gather, L::epi), d, ep);
+    if (lds > LDS_MAX) return -4;
+    const int cap = EP && L::E2 ? LDS_MAX : lds;          // (without the ep2 layout lds is a constant of the instantiation)
+    const dim3 grid(conv_grid(d, BM, BN));
+    if (is_pointwise(d)) return pn2_launch<conv_gather_gemm<T, BM, BN, WM, WN, true, EP>>(grid, dim3(256), lds, cap, st, (const T*)in, (const T*)wp, (T*)out, psum, psq, d, ep);
+    return pn2_launch<conv_gather_gemm<T, BM, BN, WM, WN, false, EP>>(grid, dim3(256), lds, cap, st, (const T*)in, (const T*)wp, (T*)out, psum, psq, d, ep);
 }
 
 template <bool EP, int BM, int BN, int WM, int WN, int NS = 3>
 int launch_dma(const void* in, const void* wp, void* out, float* psum, float* psq, const pn2_conv_desc& d, const pn2_conv_ep& ep, hipStream_t st) {
-    const int M = d.N * d.OH * d.OW;
-    const int grid = ((M + BM - 1) / BM) * ((d.Cout + BN - 1) / BN);
-    constexpr int stage_b = (BM + BN) * 128, max_b = NS * stage_b, epi_b = BM * (BN * 2 + 16) + 3 * WM * BN * 4;
+    using L = ConvLds<bf16_t, BM, BN, WM>;
     // short-K convs (1-2 K-steps) only touch 1-2 ring slots: ask for less LDS so that more workgroups share a CU
     const int ksteps = (d.KH * d.KW * d.Cin_p + 63) / 64;
-    const int main_b = (ksteps < NS ? ksteps : NS) * stage_b;
-    int lds = main_b > epi_b ? main_b : epi_b;
-    constexpr bool E2 = EP && ep2_tile(BM, BN);
-    if (E2) { const int e2 = ep2_lds_for<BM, BN>(d, ep); if (e2 > lds) lds = e2; }
-    else if (EP && lds < ep_lds_bytes(8)) lds = ep_lds_bytes(8);
-    if (lds > 160 * 1024) return -4;
-    const bool pw = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0;
-    if (max_b > 64 * 1024 || epi_b > 64 * 1024 || E2) {
-        static bool done = false;
-        if (!done) {
-            const int cap = E2 ? 160 * 1024 : (max_b > epi_b ? max_b : epi_b);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_gemm<BM, BN, WM, WN, true, NS, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_gemm<BM, BN, WM, WN, false, NS, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-            done = true;
-        }
-    }
-    const int ksplit = (d.flags >> 16) & 15;
-    const dim3 g3(grid, ksplit > 1 ? ksplit : 1);
-    if (pw) hipLaunchKernelGGL((conv_dma_gemm<BM, BN, WM, WN, true, NS, EP>), g3, dim3(256), lds, st, (const bf16_t*)in, (const bf16_t*)wp, (bf16_t*)out, psum, psq, d, ep);
-    else hipLaunchKernelGGL((conv_dma_gemm<BM, BN, WM, WN, false, NS, EP>), g3, dim3(256), lds, st, (const bf16_t*)in, (const bf16_t*)wp, (bf16_t*)out, psum, psq, d, ep);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const int lds = L::template with_ep<EP>(imax((ksteps < NS ? ksteps : NS) * L::stage, L::epi), d, ep);
+    if (lds > LDS_MAX) return -4;
+    constexpr int cap = EP && L::E2 ? LDS_MAX : imax(NS * L::stage, L::epi);
+    const int ksplit = conv_ksplit(d);
+    const dim3 grid(conv_grid(d, BM, BN), ksplit > 1 ? ksplit : 1);
+    if (is_pointwise(d)) return pn2_launch<conv_dma_gemm<BM, BN, WM, WN, true, NS, EP>>(grid, dim3(256), lds, cap, st, (const bf16_t*)in, (const bf16_t*)wp, (bf16_t*)out, psum, psq, d, ep);
+    return pn2_launch<conv_dma_gemm<BM, BN, WM, WN, false, NS, EP>>(grid, dim3(256), lds, cap, st, (const bf16_t*)in, (const bf16_t*)wp, (bf16_t*)out, psum, psq, d, ep);
 }
 
 // intra-workgroup split-K launch (conv_dma_gemm_ks): KS rings, 256 * KS threads; -4 when the rings / the exchange area / the epilogue do not fit 160 KB
 template <bool EP, int BM, int BN, int WM, int WN, int NS, int KS>
 int launch_dma_ks(const void* in, const void* wp, void* out, float* psum, float* psq, const pn2_conv_desc& d, const pn2_conv_ep& ep, hipStream_t st) {
-    const int M = d.N * d.OH * d.OW;
-    const int grid = ((M + BM - 1) / BM) * ((d.Cout + BN - 1) / BN);
-    constexpr int stage_b = (BM + BN) * 128, main_b = KS * NS * stage_b, epi_b = BM * (BN * 2 + 16) + 3 * WM * BN * 4, xch_b = (KS - 1) * BM * BN * 4;
-    static_assert(main_b <= 160 * 1024 && xch_b <= 160 * 1024, "tile does not fit");
-    int lds = main_b > epi_b ? main_b : epi_b;
-    if (xch_b > lds) lds = xch_b;
-    constexpr bool E2 = EP && ep2_tile(BM, BN);
-    if (E2) { const int e2 = ep2_lds_for<BM, BN>(d, ep); if (e2 > lds) lds = e2; }
-    else if (EP && lds < ep_lds_bytes(8)) lds = ep_lds_bytes(8);
-    if (lds > 160 * 1024 || ((d.flags >> 16) & 15) > 1) return -4;
-    const bool pw = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0;
-    {
-        static bool done = false;
-        if (!done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_gemm_ks<BM, BN, WM, WN, true, NS, EP, KS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_gemm_ks<BM, BN, WM, WN, false, NS, EP, KS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            done = true;
-        }
-    }
-    if (pw) hipLaunchKernelGGL((conv_dma_gemm_ks<BM, BN, WM, WN, true, NS, EP, KS>), dim3(grid), dim3(256 * KS), lds, st, (const bf16_t*)in, (const bf16_t*)wp, (bf16_t*)out, psum, psq, d, ep);
-    else hipLaunchKernelGGL((conv_dma_gemm_ks<BM, BN, WM, WN, false, NS, EP, KS>), dim3(grid), dim3(256 * KS), lds, st, (const bf16_t*)in, (const bf16_t*)wp, (bf16_t*)out, psum, psq, d, ep);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    using L = ConvLds<bf16_t, BM, BN, WM>;
+    static_assert(KS * NS * L::stage <= LDS_MAX && L::xch(KS) <= LDS_MAX, "tile does not fit");
+    const int lds = L::template with_ep<EP>(imax(imax(KS * NS * L::stage, L::epi), L::xch(KS)), d, ep);
+    if (lds > LDS_MAX || conv_ksplit(d) > 1) return -4;
+    const dim3 grid(conv_grid(d, BM, BN));
+    if (is_pointwise(d)) return pn2_launch<conv_dma_gemm_ks<BM, BN, WM, WN, true, NS, EP, KS>>(grid, dim3(256 * KS), lds, LDS_MAX, st, (const bf16_t*)in, (const bf16_t*)wp, (bf16_t*)out, psum, psq, d, ep);
+    return pn2_launch<conv_dma_gemm_ks<BM, BN, WM, WN, false, NS, EP, KS>>(grid, dim3(256 * KS), lds, LDS_MAX, st, (const bf16_t*)in, (const bf16_t*)wp, (bf16_t*)out, psum, psq, d, ep);
 }
 
 // the LDS-DMA kernel addresses the activation operand with 32-bit byte offsets behind a buffer descriptor (conv_dma_body): its extent must stay below 2 GB
@@ -2305,24 +2287,45 @@ inline void pick_tiles(int M, int cout, bool f32, int& bm, int& bn) {
     if (blocks() < 160 && bn == 64 && cout > 32) bn = 32;
 }
 
+// compile-time tile handed to a with_tile / with_wgrad_tile visitor, and the storage type handed to a with_dtype visitor
+template <int BM_, int BN_, int WM_, int WN_> struct Tile { static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_; };
+template <typename T> struct Ty { using type = T; };
+// the built conv GEMM tiles (BM x BN, WM x WN waves): f(Tile) for (bm, bn), -2 for any other pair
+template <typename F>
+int with_tile(int bm, int bn, F f) {
+    if (bm == 128 && bn == 128) return f(Tile<128, 128, 2, 2>{});
+    if (bm == 128 && bn == 64) return f(Tile<128, 64, 2, 2>{});
+    if (bm == 128 && bn == 32) return f(Tile<128, 32, 4, 1>{});
+    if (bm == 64 && bn == 128) return f(Tile<64, 128, 2, 2>{});
+    if (bm == 64 && bn == 64) return f(Tile<64, 64, 2, 2>{});
+    if (bm == 64 && bn == 32) return f(Tile<64, 32, 4, 1>{});
+    return -2;
+}
+// the built wgrad output-channel tiles (Tile::BM = BMC; the contraction tile BNK is the kernel's own business)
+template <typename F>
+int with_wgrad_tile(int bmc, F f) {
+    if (bmc == 128) return f(Tile<128, 0, 2, 2>{});
+    if (bmc == 64) return f(Tile<64, 0, 2, 2>{});
+    if (bmc == 32) return f(Tile<32, 0, 1, 4>{});
+    return -2;
+}
+// storage type of a PN2_* dtype code: f(Ty<T>), -3 for an unknown code
+template <typename F>
+int with_dtype(int dtype, F f) {
+    if (dtype == PN2_BF16) return f(Ty<bf16_t>{});
+    if (dtype == PN2_F32) return f(Ty<float>{});
+    if (dtype == PN2_F32F) return f(Ty<f32f_t>{});
+    if (dtype == PN2_F32X3) return f(Ty<f32x3_t>{});
+    return -3;
+}
+
 template <typename T, int BMC, int WM, int WN>
 int launch_wgrad(const void* dy, const void* x, float* slab, const pn2_wgrad_desc& d, int nsplit, hipStream_t st) {
     constexpr int BNK = 128;
-    constexpr int lds = 2 * wg_stage_bytes<T>(BMC, BNK);
-    dim3 grid(8 * ((nsplit + 7) / 8) * (d.Rp / BMC) * (d.Kp / BNK));
-    const bool pw = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0;
-    if constexpr (X3<T>) {          // (fp32x3: 74-111 KB, above the default 64 KB cap)
-        static bool done = false;
-        if (!done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad<T, BMC, BNK, WM, WN, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad<T, BMC, BNK, WM, WN, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            done = true;
-        }
-    }
-    if (pw) hipLaunchKernelGGL((conv_wgrad<T, BMC, BNK, WM, WN, true>), grid, dim3(256), lds, st, (const T*)dy, (const T*)x, slab, d, nsplit);
-    else hipLaunchKernelGGL((conv_wgrad<T, BMC, BNK, WM, WN, false>), grid, dim3(256), lds, st, (const T*)dy, (const T*)x, slab, d, nsplit);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    constexpr int lds = 2 * wg_stage_bytes<T>(BMC, BNK), cap = X3<T> ? lds : 0;          // (fp32x3: 74-111 KB, above the default 64 KB cap)
+    const dim3 grid(8 * ((nsplit + 7) / 8) * (d.Rp / BMC) * (d.Kp / BNK));
+    if (is_pointwise(d)) return pn2_launch<conv_wgrad<T, BMC, BNK, WM, WN, true>>(grid, dim3(256), lds, cap, st, (const T*)dy, (const T*)x, slab, d, nsplit);
+    return pn2_launch<conv_wgrad<T, BMC, BNK, WM, WN, false>>(grid, dim3(256), lds, cap, st, (const T*)dy, (const T*)x, slab, d, nsplit);
 }
 
 // (kernel, BM, BN) for this desc: kern 0 register-staged, 2 LDS-DMA 3-stage, 3 LDS-DMA 2-stage.  Optional per-shape tuning code in flags bits 8..15
@@ -2330,7 +2333,7 @@ int launch_wgrad(const void* dy, const void* x, float* slab, const pn2_wgrad_des
 template <typename T>
 void gemm_select(const pn2_conv_desc& d, int& kern, int& bm, int& bn) {
     pick_tiles(d.N * d.OH * d.OW, d.Cout, sizeof(T) == 4, bm, bn);
-    const int tune = (sizeof(T) == 2 || !MMA<T>::F64ROWS) ? (d.flags >> 8) & 0xff : 0;          // (fp32fast / fp32x3 take the tile bits of a tuning code; their kernel is always the register-staged one)
+    const int tune = (sizeof(T) == 2 || !MMA<T>::F64ROWS) ? conv_tune(d) : 0;          // (fp32fast / fp32x3 take the tile bits of a tuning code; their kernel is always the register-staged one)
     const int tk_ = dma_extent_ok(d) ? (tune & 3) : 1, tbm = (tune >> 2) & 3, tbn = (tune >> 4) & 3;     // > 2 GB operand: register-staged kernel (64-bit addresses)
     if (tbm) bm = tbm == 1 ? 64 : 128;
     if (tbn) bn = tbn == 1 ? 32 : (tbn == 2 ? 64 : 128);
@@ -2343,179 +2346,82 @@ template <typename T, bool EP>
 int gemm_dispatch(const void* in, const void* wp, void* out, float* psum, float* psq, const pn2_conv_desc& d, const pn2_conv_ep& ep, hipStream_t st) {
     int kern, bm, bn;
     gemm_select<T>(d, kern, bm, bn);
-    if constexpr (sizeof(T) == 2) {
-        if (((d.flags >> 8) & 0x80) && kern >= 2 && bm == 64 && bn == 64) {          // tuning-code bit 7: intra-workgroup split-K over FOUR K groups (64 x 64 tiles)
-            return launch_dma_ks<EP, 64, 64, 2, 2, 2, 4>(in, wp, out, psum, psq, d, ep, st);          // (four 3-stage rings of a 64 x 64 tile would take 192 KB: 2 stages)
-        }
-        if (((d.flags >> 8) & 0x40) && kern >= 2 && bn >= 64) {          // tuning-code bit 6: intra-workgroup split-K over two K groups of four waves
-            if (kern == 3) {
-                if (bm == 128) return bn == 128 ? launch_dma_ks<EP, 128, 128, 2, 2, 2, 2>(in, wp, out, psum, psq, d, ep, st) : launch_dma_ks<EP, 128, 64, 2, 2, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-                return bn == 128 ? launch_dma_ks<EP, 64, 128, 2, 2, 2, 2>(in, wp, out, psum, psq, d, ep, st) : launch_dma_ks<EP, 64, 64, 2, 2, 2, 2>(in, wp, out, psum, psq, d, ep, st);
+    return with_tile(bm, bn, [&](auto tile) {
+        using L = decltype(tile);
+        constexpr int BM = L::BM, BN = L::BN, WM = L::WM, WN = L::WN;
+        if constexpr (sizeof(T) == 2) {
+            const int ks = kern >= 2 ? conv_tune(d) & (TUNE_KS2 | TUNE_KS4) : 0;
+            if constexpr (BM == 64 && BN == 64) {          // split-K over FOUR K groups (64 x 64 tiles); four 3-stage rings of a 64 x 64 tile would take 192 KB: 2 stages
+                if (ks & TUNE_KS4) return launch_dma_ks<EP, 64, 64, 2, 2, 2, 4>(in, wp, out, psum, psq, d, ep, st);
             }
-            if (bm == 128) return bn == 128 ? -4 : launch_dma_ks<EP, 128, 64, 2, 2, 3, 2>(in, wp, out, psum, psq, d, ep, st);
-            return bn == 128 ? launch_dma_ks<EP, 64, 128, 2, 2, 3, 2>(in, wp, out, psum, psq, d, ep, st) : launch_dma_ks<EP, 64, 64, 2, 2, 3, 2>(in, wp, out, psum, psq, d, ep, st);
-        }
-        if (kern == 3) {              // LDS-DMA, 2-stage ring (more workgroups per CU)
-            if (bm == 128) {
-                if (bn == 128) return launch_dma<EP, 128, 128, 2, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-                if (bn == 64) return launch_dma<EP, 128, 64, 2, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-                return launch_dma<EP, 128, 32, 4, 1, 2>(in, wp, out, psum, psq, d, ep, st);
+            if constexpr (BN >= 64) {          // split-K over two K groups of four waves
+                if ((ks & TUNE_KS2) && kern == 3) return launch_dma_ks<EP, BM, BN, WM, WN, 2, 2>(in, wp, out, psum, psq, d, ep, st);
+                if constexpr (BM == 128 && BN == 128) { if (ks & TUNE_KS2) return -4; }          // (two 3-stage rings of a 128 x 128 tile: 192 KB)
+                else if (ks & TUNE_KS2) return launch_dma_ks<EP, BM, BN, WM, WN, 3, 2>(in, wp, out, psum, psq, d, ep, st);
             }
-            if (bn == 128) return launch_dma<EP, 64, 128, 2, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-            if (bn == 64) return launch_dma<EP, 64, 64, 2, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-            return launch_dma<EP, 64, 32, 4, 1, 2>(in, wp, out, psum, psq, d, ep, st);
+            if (kern == 3) return launch_dma<EP, BM, BN, WM, WN, 2>(in, wp, out, psum, psq, d, ep, st);          // LDS-DMA, 2-stage ring (more workgroups per CU)
+            if (kern == 2) return launch_dma<EP, BM, BN, WM, WN>(in, wp, out, psum, psq, d, ep, st);
         }
-        if (kern == 2) {
-            if (bm == 128) {
-                if (bn == 128) return launch_dma<EP, 128, 128, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-                if (bn == 64) return launch_dma<EP, 128, 64, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-                return launch_dma<EP, 128, 32, 4, 1>(in, wp, out, psum, psq, d, ep, st);
-            }
-            if (bn == 128) return launch_dma<EP, 64, 128, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-            if (bn == 64) return launch_dma<EP, 64, 64, 2, 2>(in, wp, out, psum, psq, d, ep, st);
-            return launch_dma<EP, 64, 32, 4, 1>(in, wp, out, psum, psq, d, ep, st);
-        }
-    }
-    if (bm == 128) {
-        if (bn == 128) {
-            if constexpr (!MMA<T>::F64ROWS) return launch_gemm<T, 128, 128, 2, 2, EP>(in, wp, out, psum, psq, d, ep, st);
-        }
-        if (bn == 64) return launch_gemm<T, 128, 64, 2, 2, EP>(in, wp, out, psum, psq, d, ep, st);
-        return launch_gemm<T, 128, 32, 4, 1, EP>(in, wp, out, psum, psq, d, ep, st);
-    }
-    if (bn == 128) {
-        if constexpr (!MMA<T>::F64ROWS) return launch_gemm<T, 64, 128, 2, 2, EP>(in, wp, out, psum, psq, d, ep, st);
-    }
-    if (bn == 64) return launch_gemm<T, 64, 64, 2, 2, EP>(in, wp, out, psum, psq, d, ep, st);
-    return launch_gemm<T, 64, 32, 4, 1, EP>(in, wp, out, psum, psq, d, ep, st);
+        if constexpr (BN == 128 && MMA<T>::F64ROWS) return -2;          // (never selected: f64 accumulators of a 128-wide wave tile would take 128 registers)
+        else return launch_gemm<T, BM, BN, WM, WN, EP>(in, wp, out, psum, psq, d, ep, st);
+    });
 }
 
 // table-driven conv GEMM launches: general (non-pointwise-specialised) kernels, LDS-DMA 3-stage for bf16, register-staged for fp32
 template <bool EP, int BM, int BN, int WM, int WN>
 int launch_dma_tab(const pn2_conv_job* jobs, const int* bstart, int njobs, int total, int bits, hipStream_t st) {
-    constexpr int stage_b = (BM + BN) * 128, max_b = 3 * stage_b, epi_b = BM * (BN * 2 + 16) + 3 * WM * BN * 4;
-    int lds = max_b > epi_b ? max_b : epi_b;
-    if (EP && ep2_tile(BM, BN)) { const int e2 = ep2_lds_bits<BM, BN>(bits); if (e2 > lds) lds = e2; }
-    else if (EP && lds < ep_lds_bytes(8)) lds = ep_lds_bytes(8);
-    if (lds > 160 * 1024) return -4;
-    static bool done = false;
-    if (!done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_gemm_tab<BM, BN, WM, WN, false, 3, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, EP ? 160 * 1024 : lds);
-        done = true;
-    }
-    hipLaunchKernelGGL((conv_dma_gemm_tab<BM, BN, WM, WN, false, 3, EP>), dim3(total), dim3(256), lds, st, jobs, bstart, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    using L = ConvLds<bf16_t, BM, BN, WM>;
+    const int lds = L::template with_ep<EP>(imax(3 * L::stage, L::epi), bits);
+    if (lds > LDS_MAX) return -4;
+    return pn2_launch<conv_dma_gemm_tab<BM, BN, WM, WN, false, 3, EP>>(dim3(total), dim3(256), lds, EP ? LDS_MAX : lds, st, jobs, bstart, njobs);
 }
 // table-driven launch of the intra-workgroup split-K kernel (two K groups, 3-stage rings): jobs whose shape rule asks for it share tables among themselves
 template <bool EP, int BM, int BN, int WM, int WN>
 int launch_dma_tab_ks2(const pn2_conv_job* jobs, const int* bstart, int njobs, int total, int bits, hipStream_t st) {
-    constexpr int stage_b = (BM + BN) * 128, max_b = 2 * 3 * stage_b, epi_b = BM * (BN * 2 + 16) + 3 * WM * BN * 4, xch_b = BM * BN * 4;
-    static_assert(max_b <= 160 * 1024, "tile does not fit");
-    int lds = max_b > epi_b ? max_b : epi_b;
-    if (xch_b > lds) lds = xch_b;
-    if (EP && ep2_tile(BM, BN)) { const int e2 = ep2_lds_bits<BM, BN>(bits); if (e2 > lds) lds = e2; }
-    else if (EP && lds < ep_lds_bytes(8)) lds = ep_lds_bytes(8);
-    if (lds > 160 * 1024) return -4;
-    static bool done = false;
-    if (!done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_gemm_tab_ks2<BM, BN, WM, WN, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        done = true;
-    }
-    hipLaunchKernelGGL((conv_dma_gemm_tab_ks2<BM, BN, WM, WN, EP>), dim3(total), dim3(512), lds, st, jobs, bstart, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    using L = ConvLds<bf16_t, BM, BN, WM>;
+    static_assert(2 * 3 * L::stage <= LDS_MAX, "tile does not fit");
+    const int lds = L::template with_ep<EP>(imax(imax(2 * 3 * L::stage, L::epi), L::xch(2)), bits);
+    if (lds > LDS_MAX) return -4;
+    return pn2_launch<conv_dma_gemm_tab_ks2<BM, BN, WM, WN, EP>>(dim3(total), dim3(512), lds, LDS_MAX, st, jobs, bstart, njobs);
 }
 template <typename T, bool EP, int BM, int BN, int WM, int WN>
 int launch_gather_tab_f32(const pn2_conv_job* jobs, const int* bstart, int njobs, int total, hipStream_t st) {
-    constexpr int main_b = 2 * (BM + BN) * (RS + lo_row<T>), epi_b = BM * (BN * 4 + 16) + 3 * WM * BN * 4, ep_b = EP ? ep_lds_bytes(4) : 0;
-    constexpr int lds = (main_b > epi_b ? main_b : epi_b) > ep_b ? (main_b > epi_b ? main_b : epi_b) : ep_b;
-    static bool done = false;
-    if (!done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gather_gemm_tab<T, BM, BN, WM, WN, false, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        done = true;
-    }
-    hipLaunchKernelGGL((conv_gather_gemm_tab<T, BM, BN, WM, WN, false, EP>), dim3(total), dim3(256), lds, st, jobs, bstart, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    using L = ConvLds<T, BM, BN, WM>;
+    const int lds = L::template with_ep<EP>(imax(L::gather, L::epi));
+    return pn2_launch<conv_gather_gemm_tab<T, BM, BN, WM, WN, false, EP>>(dim3(total), dim3(256), lds, lds, st, jobs, bstart, njobs);
 }
 template <bool EP>
 int gemm_multi_dispatch(int dtype, int bm, int bn, int bits, const pn2_conv_job* jobs, const int* bstart, int njobs, int total, hipStream_t st) {
-    if (dtype == PN2_BF16 && (bm & 0x100)) {          // tile code of pn2_conv_gemm_tile with the split-K bit: the two-K-group table kernel
-        bm &= 0xff;
-        if (bm == 128 && bn == 64) return launch_dma_tab_ks2<EP, 128, 64, 2, 2>(jobs, bstart, njobs, total, bits, st);
-        if (bm == 64 && bn == 128) return launch_dma_tab_ks2<EP, 64, 128, 2, 2>(jobs, bstart, njobs, total, bits, st);
-        if (bm == 64 && bn == 64) return launch_dma_tab_ks2<EP, 64, 64, 2, 2>(jobs, bstart, njobs, total, bits, st);
-        return -2;
-    }
-    if (dtype == PN2_BF16) {
-        if (bm == 128) {
-            if (bn == 128) return launch_dma_tab<EP, 128, 128, 2, 2>(jobs, bstart, njobs, total, bits, st);
-            if (bn == 64) return launch_dma_tab<EP, 128, 64, 2, 2>(jobs, bstart, njobs, total, bits, st);
-            if (bn == 32) return launch_dma_tab<EP, 128, 32, 4, 1>(jobs, bstart, njobs, total, bits, st);
-        } else if (bm == 64) {
-            if (bn == 128) return launch_dma_tab<EP, 64, 128, 2, 2>(jobs, bstart, njobs, total, bits, st);
-            if (bn == 64) return launch_dma_tab<EP, 64, 64, 2, 2>(jobs, bstart, njobs, total, bits, st);
-            if (bn == 32) return launch_dma_tab<EP, 64, 32, 4, 1>(jobs, bstart, njobs, total, bits, st);
-        }
-        return -2;
-    }
-    if (dtype == PN2_F32) {
-        if (bm == 128) {
-            if (bn == 64) return launch_gather_tab_f32<float, EP, 128, 64, 2, 2>(jobs, bstart, njobs, total, st);
-            if (bn == 32) return launch_gather_tab_f32<float, EP, 128, 32, 4, 1>(jobs, bstart, njobs, total, st);
-        } else if (bm == 64) {
-            if (bn == 64) return launch_gather_tab_f32<float, EP, 64, 64, 2, 2>(jobs, bstart, njobs, total, st);
-            if (bn == 32) return launch_gather_tab_f32<float, EP, 64, 32, 4, 1>(jobs, bstart, njobs, total, st);
-        }
-        return -2;
-    }
-    if (dtype == PN2_F32F) {          // (no 128-wide tiles: gemm_select and pn2_conv_gemm_tile never pick them for 4-byte types)
-        if (bm == 128) {
-            if (bn == 64) return launch_gather_tab_f32<f32f_t, EP, 128, 64, 2, 2>(jobs, bstart, njobs, total, st);
-            if (bn == 32) return launch_gather_tab_f32<f32f_t, EP, 128, 32, 4, 1>(jobs, bstart, njobs, total, st);
-        } else if (bm == 64) {
-            if (bn == 64) return launch_gather_tab_f32<f32f_t, EP, 64, 64, 2, 2>(jobs, bstart, njobs, total, st);
-            if (bn == 32) return launch_gather_tab_f32<f32f_t, EP, 64, 32, 4, 1>(jobs, bstart, njobs, total, st);
-        }
-        return -2;
-    }
-    if (dtype == PN2_F32X3) {         // (no 128-wide tiles either)
-        if (bm == 128) {
-            if (bn == 64) return launch_gather_tab_f32<f32x3_t, EP, 128, 64, 2, 2>(jobs, bstart, njobs, total, st);
-            if (bn == 32) return launch_gather_tab_f32<f32x3_t, EP, 128, 32, 4, 1>(jobs, bstart, njobs, total, st);
-        } else if (bm == 64) {
-            if (bn == 64) return launch_gather_tab_f32<f32x3_t, EP, 64, 64, 2, 2>(jobs, bstart, njobs, total, st);
-            if (bn == 32) return launch_gather_tab_f32<f32x3_t, EP, 64, 32, 4, 1>(jobs, bstart, njobs, total, st);
-        }
-        return -2;
-    }
-    return -3;
+    const bool ks2 = dtype == PN2_BF16 && (bm & TILE_KS2);          // tile code of pn2_conv_gemm_tile with the split-K bit: the two-K-group table kernel
+    if (ks2) bm &= 0xff;
+    return with_dtype(dtype, [&](auto ty) {
+        using T = typename decltype(ty)::type;
+        return with_tile(bm, bn, [&](auto tile) {
+            using L = decltype(tile);
+            constexpr int BM = L::BM, BN = L::BN, WM = L::WM, WN = L::WN;
+            if constexpr (sizeof(T) == 2) {
+                if constexpr (BN >= 64 && !(BM == 128 && BN == 128)) { if (ks2) return launch_dma_tab_ks2<EP, BM, BN, WM, WN>(jobs, bstart, njobs, total, bits, st); }
+                else if (ks2) return -2;
+                return launch_dma_tab<EP, BM, BN, WM, WN>(jobs, bstart, njobs, total, bits, st);
+            } else if constexpr (BN == 128) return -2;          // (no 128-wide tiles: gemm_select and pn2_conv_gemm_tile never pick them for 4-byte types)
+            else return launch_gather_tab_f32<T, EP, BM, BN, WM, WN>(jobs, bstart, njobs, total, st);
+        });
+    });
 }
+
+// LDS bytes of the three-stage ring of the DMA wgrad kernels
+constexpr int wg_dma_ring_bytes(int bmc, int bnk) { return 3 * wg_px(bmc) * (bmc * 2 + bnk * 2); }
 
 template <int BMC, int WM, int WN, int BNK = 128>
 int launch_wgrad_dma(const void* dy, const void* x, float* slab, const pn2_wgrad_desc& d, int nsplit, hipStream_t st) {
-    constexpr int PX = wg_px(BMC), stage_b = PX * (BMC * 2 + BNK * 2), max_b = 3 * stage_b;
+    constexpr int PX = wg_px(BMC), max_b = wg_dma_ring_bytes(BMC, BNK);
     const int M = d.N * d.OH * d.OW;
     const int total_steps = (M + PX - 1) / PX, spb = (total_steps + nsplit - 1) / nsplit;
-    const int lds = (spb < 3 ? (spb < 1 ? 1 : spb) : 3) * stage_b;
-    const int grid = 8 * ((nsplit + 7) / 8) * (d.Rp / BMC) * ((d.Kp + BNK - 1) / BNK);
-    const bool pw = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0;
-    if (max_b > 64 * 1024) {
-        static bool done = false;
-        if (!done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma<BMC, WM, WN, true, BNK>), hipFuncAttributeMaxDynamicSharedMemorySize, max_b);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma<BMC, WM, WN, false, BNK>), hipFuncAttributeMaxDynamicSharedMemorySize, max_b);
-            done = true;
-        }
-    }
-    if (pw) hipLaunchKernelGGL((conv_wgrad_dma<BMC, WM, WN, true, BNK>), dim3(grid), dim3(256), lds, st, (const bf16_t*)dy, (const bf16_t*)x, slab, d, nsplit);
-    else hipLaunchKernelGGL((conv_wgrad_dma<BMC, WM, WN, false, BNK>), dim3(grid), dim3(256), lds, st, (const bf16_t*)dy, (const bf16_t*)x, slab, d, nsplit);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const int lds = (spb < 3 ? (spb < 1 ? 1 : spb) : 3) * (max_b / 3);
+    const dim3 grid(8 * ((nsplit + 7) / 8) * (d.Rp / BMC) * ((d.Kp + BNK - 1) / BNK));
+    if (is_pointwise(d)) return pn2_launch<conv_wgrad_dma<BMC, WM, WN, true, BNK>>(grid, dim3(256), lds, max_b, st, (const bf16_t*)dy, (const bf16_t*)x, slab, d, nsplit);
+    return pn2_launch<conv_wgrad_dma<BMC, WM, WN, false, BNK>>(grid, dim3(256), lds, max_b, st, (const bf16_t*)dy, (const bf16_t*)x, slab, d, nsplit);
 }
-
-inline bool wgrad_pw(const pn2_wgrad_desc& d) { return d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0; }
 
 // kernel instantiation a wgrad job runs on: dma * 6 + (co tile 32/64/128 -> 0/1/2) * 2 + pointwise; 12 + pointwise: the DMA kernel with 128 x 256 tiles.
 // d.tune: 0 heuristic, 1 register-staged, 2 LDS-DMA (128-wide contraction tiles), 3 LDS-DMA with 128 x 256 tiles (bf16, co tile 128, Kp >= 256; else as 2)
@@ -2524,13 +2430,13 @@ int wgrad_variant(const pn2_wgrad_desc& d) {
     const int bmc = pn2_wgrad_tile_co(d.Cout_p);
     bool dma = false, wide = false;
     if constexpr (sizeof(T) == 2) {
-        dma = d.tune ? d.tune >= 2 : (wgrad_pw(d) && d.N * d.OH * d.OW >= 8192);      // default: the DMA pipeline pays off for pointwise convs with many pixels
+        dma = d.tune ? d.tune >= 2 : (is_pointwise(d) && d.N * d.OH * d.OW >= 8192);      // default: the DMA pipeline pays off for pointwise convs with many pixels
         // the DMA kernel addresses both operands with 32-bit byte offsets (buffer descriptors): extents below 2 GB
         if ((size_t)d.N * d.OH * d.OW * d.ld_dy * 2 >= 0x80000000ull || (size_t)d.N * d.H * d.W * d.ld_x * 2 >= 0x80000000ull) dma = false;
         wide = dma && bmc == 128 && d.Kp >= 256 && d.tune == 3;
     }
-    if (wide) return 12 + (wgrad_pw(d) ? 1 : 0);
-    return (dma ? 6 : 0) + (bmc == 128 ? 2 : (bmc == 64 ? 1 : 0)) * 2 + (wgrad_pw(d) ? 1 : 0);
+    if (wide) return 12 + (is_pointwise(d) ? 1 : 0);
+    return (dma ? 6 : 0) + (bmc == 128 ? 2 : (bmc == 64 ? 1 : 0)) * 2 + (is_pointwise(d) ? 1 : 0);
 }
 
 template <typename T>
@@ -2545,84 +2451,45 @@ int wgrad_dispatch(const void* dy, const void* x, float* slab, const pn2_wgrad_d
     const int bmc = pn2_wgrad_tile_co(d.Cout_p);
     if (d.Rp % bmc || d.Kp % 128) return -2;
     const int v = wgrad_variant<T>(d);
-    if constexpr (sizeof(T) == 2) {
-        if (v >= 12) return launch_wgrad_dma<128, 2, 2, 256>(dy, x, slab, d, nsplit, st);
-        if (v >= 6) {
-            if (bmc == 128) return launch_wgrad_dma<128, 2, 2>(dy, x, slab, d, nsplit, st);
-            if (bmc == 64) return launch_wgrad_dma<64, 2, 2>(dy, x, slab, d, nsplit, st);
-            return launch_wgrad_dma<32, 1, 4>(dy, x, slab, d, nsplit, st);
+    return with_wgrad_tile(bmc, [&](auto tile) {
+        using L = decltype(tile);
+        if constexpr (sizeof(T) == 2) {
+            if (v >= 12) return launch_wgrad_dma<128, 2, 2, 256>(dy, x, slab, d, nsplit, st);
+            if (v >= 6) return launch_wgrad_dma<L::BM, L::WM, L::WN>(dy, x, slab, d, nsplit, st);
         }
-    }
-    if (bmc == 128) return launch_wgrad<T, 128, 2, 2>(dy, x, slab, d, nsplit, st);
-    if (bmc == 64) return launch_wgrad<T, 64, 2, 2>(dy, x, slab, d, nsplit, st);
-    return launch_wgrad<T, 32, 1, 4>(dy, x, slab, d, nsplit, st);
+        return launch_wgrad<T, L::BM, L::WM, L::WN>(dy, x, slab, d, nsplit, st);
+    });
 }
 
 template <typename T, int BMC, int WM, int WN>
 int launch_wgrad_tab(bool pw, const pn2_wgrad_job* jobs, const int* bstart, int njobs, int total, hipStream_t st) {
     constexpr int BNK = 128;
-    constexpr int lds = 2 * wg_stage_bytes<T>(BMC, BNK);
-    if constexpr (X3<T>) {
-        static bool done = false;
-        if (!done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tab<T, BMC, BNK, WM, WN, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tab<T, BMC, BNK, WM, WN, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            done = true;
-        }
-    }
-    if (pw) hipLaunchKernelGGL((conv_wgrad_tab<T, BMC, BNK, WM, WN, true>), dim3(total), dim3(256), lds, st, jobs, bstart, njobs);
-    else hipLaunchKernelGGL((conv_wgrad_tab<T, BMC, BNK, WM, WN, false>), dim3(total), dim3(256), lds, st, jobs, bstart, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    constexpr int lds = 2 * wg_stage_bytes<T>(BMC, BNK), cap = X3<T> ? lds : 0;
+    if (pw) return pn2_launch<conv_wgrad_tab<T, BMC, BNK, WM, WN, true>>(dim3(total), dim3(256), lds, cap, st, jobs, bstart, njobs);
+    return pn2_launch<conv_wgrad_tab<T, BMC, BNK, WM, WN, false>>(dim3(total), dim3(256), lds, cap, st, jobs, bstart, njobs);
 }
 
 template <int BMC, int WM, int WN, int BNK = 128>
 int launch_wgrad_dma_tab(bool pw, const pn2_wgrad_job* jobs, const int* bstart, int njobs, int total, hipStream_t st) {
-    constexpr int max_b = 3 * wg_px(BMC) * (BMC * 2 + BNK * 2);
-    if (max_b > 64 * 1024) {
-        static bool done = false;
-        if (!done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma_tab<BMC, WM, WN, true, BNK>), hipFuncAttributeMaxDynamicSharedMemorySize, max_b);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma_tab<BMC, WM, WN, false, BNK>), hipFuncAttributeMaxDynamicSharedMemorySize, max_b);
-            done = true;
-        }
-    }
-    if (pw) hipLaunchKernelGGL((conv_wgrad_dma_tab<BMC, WM, WN, true, BNK>), dim3(total), dim3(256), max_b, st, jobs, bstart, njobs);
-    else hipLaunchKernelGGL((conv_wgrad_dma_tab<BMC, WM, WN, false, BNK>), dim3(total), dim3(256), max_b, st, jobs, bstart, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    constexpr int max_b = wg_dma_ring_bytes(BMC, BNK);
+    if (pw) return pn2_launch<conv_wgrad_dma_tab<BMC, WM, WN, true, BNK>>(dim3(total), dim3(256), max_b, max_b, st, jobs, bstart, njobs);
+    return pn2_launch<conv_wgrad_dma_tab<BMC, WM, WN, false, BNK>>(dim3(total), dim3(256), max_b, max_b, st, jobs, bstart, njobs);
 }
 
 template <typename T>
 int wgrad_multi_dispatch(int v, const pn2_wgrad_job* jobs, const int* bstart, int njobs, int total, hipStream_t st) {
     const bool pw = v & 1;
-    const int bi = (v % 6) >> 1;
-    if (v == 14) {          // variants 12 + 13 in one table (conv_wgrad_dma_tab_mix)
+    if (v >= 6 && sizeof(T) != 2) return -3;          // the DMA kernels are bf16 only
+    return with_wgrad_tile(32 << ((v % 6) >> 1), [&](auto tile) {
+        using L = decltype(tile);
         if constexpr (sizeof(T) == 2) {
-            constexpr int max_b = 3 * wg_px(128) * (128 * 2 + 256 * 2);
-            static bool done = false;
-            if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma_tab_mix<128, 2, 2, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, max_b); done = true; }
-            hipLaunchKernelGGL((conv_wgrad_dma_tab_mix<128, 2, 2, 256>), dim3(total), dim3(256), max_b, st, jobs, bstart, njobs);
-            PN2_CHECK_LAUNCH();
-            return 0;
+            constexpr int wide_b = wg_dma_ring_bytes(128, 256);
+            if (v == 14) return pn2_launch<conv_wgrad_dma_tab_mix<128, 2, 2, 256>>(dim3(total), dim3(256), wide_b, wide_b, st, jobs, bstart, njobs);          // variants 12 + 13 in one table
+            if (v >= 12) return launch_wgrad_dma_tab<128, 2, 2, 256>(pw, jobs, bstart, njobs, total, st);
+            if (v >= 6) return launch_wgrad_dma_tab<L::BM, L::WM, L::WN>(pw, jobs, bstart, njobs, total, st);
         }
-        return -3;
-    }
-    if (v >= 12) {
-        if constexpr (sizeof(T) == 2) return launch_wgrad_dma_tab<128, 2, 2, 256>(pw, jobs, bstart, njobs, total, st);
-        return -3;
-    }
-    if (v >= 6) {
-        if constexpr (sizeof(T) == 2) {
-            if (bi == 2) return launch_wgrad_dma_tab<128, 2, 2>(pw, jobs, bstart, njobs, total, st);
-            if (bi == 1) return launch_wgrad_dma_tab<64, 2, 2>(pw, jobs, bstart, njobs, total, st);
-            return launch_wgrad_dma_tab<32, 1, 4>(pw, jobs, bstart, njobs, total, st);
-        }
-        return -3;
-    }
-    if (bi == 2) return launch_wgrad_tab<T, 128, 2, 2>(pw, jobs, bstart, njobs, total, st);
-    if (bi == 1) return launch_wgrad_tab<T, 64, 2, 2>(pw, jobs, bstart, njobs, total, st);
-    return launch_wgrad_tab<T, 32, 1, 4>(pw, jobs, bstart, njobs, total, st);
+        return launch_wgrad_tab<T, L::BM, L::WM, L::WN>(pw, jobs, bstart, njobs, total, st);
+    });
 }
 
 
@@ -2794,20 +2661,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_k(const float* __restrict__
 
 static int conv_gemm_impl(int dtype, const void* in, const void* wp, void* out, float* psum, float* psq, const pn2_conv_desc* d, const pn2_conv_ep& ep, void* stream) {
     if (!in || !wp || !out || !d) return -1;
-    if (d->Cin_p % 8 || d->ld_in % 8 || d->Kp % 128 || (d->stride != 1 && d->stride != 2 && d->stride != 4 && d->stride != 8)) return -2;
+    if (!conv_desc_ok(*d)) return -2;
     if ((d->flags & PN2_CONV_STATS) && (!psum || !psq)) return -1;
     if ((d->flags & PN2_CONV_BIAS) && (!psum || (d->flags & PN2_CONV_STATS))) return -1;
-    if (((d->flags >> 16) & 15) > 1 && (dtype != PN2_BF16 || !psum || (d->flags & (PN2_CONV_STATS | PN2_CONV_BIAS | PN2_CONV_ACCUM)) || ((d->flags >> 8) & 3) < 2)) return -2;
+    if (conv_ksplit(*d) > 1 && (dtype != PN2_BF16 || !psum || (d->flags & (PN2_CONV_STATS | PN2_CONV_BIAS | PN2_CONV_ACCUM)) || (conv_tune(*d) & 3) < 2)) return -2;
     if (d->flags & PN2_CONV_AFFINE) return -2;                 // (pn2_conv_gemm_affine owns that flag)
     const bool gated = d->flags & PN2_CONV_ROWGATE;
     const int vec_ = dtype == PN2_BF16 ? 8 : 4;
-    if (gated && (!ep.a.par || (ep.a.mode | ep.b.mode) != 0 || ep.b.out || (d->flags & PN2_CONV_BIAS) || ((d->flags >> 16) & 15) > 1 || d->Cout % vec_ || d->ld_out % vec_)) return -2;
+    if (gated && (!ep.a.par || (ep.a.mode | ep.b.mode) != 0 || ep.b.out || (d->flags & PN2_CONV_BIAS) || conv_ksplit(*d) > 1 || d->Cout % vec_ || d->ld_out % vec_)) return -2;
     const bool use_ep = (ep.a.mode | ep.b.mode) != 0 || ep.b.out != nullptr || gated;      // the gate lives in the epilogue-statistics instantiations
-    if (dtype == PN2_BF16) return use_ep ? gemm_dispatch<bf16_t, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<bf16_t, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
-    if (dtype == PN2_F32) return use_ep ? gemm_dispatch<float, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<float, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
-    if (dtype == PN2_F32F) return use_ep ? gemm_dispatch<f32f_t, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<f32f_t, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
-    if (dtype == PN2_F32X3) return use_ep ? gemm_dispatch<f32x3_t, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<f32x3_t, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
-    return -3;
+    return with_dtype(dtype, [&](auto ty) {
+        using T = typename decltype(ty)::type;
+        return use_ep ? gemm_dispatch<T, true>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream) : gemm_dispatch<T, false>(in, wp, out, psum, psq, *d, ep, (hipStream_t)stream);
+    });
 }
 
 static int bnb_check(const pn2_bnb_target& t, int vec, bool is_b) {
@@ -2847,19 +2713,17 @@ int pn2_conv_gemm(int dtype, const void* in, const void* wp, void* out, float* p
 int pn2_conv_gemm_affine(int dtype, const void* in, const void* wp, void* out, const float* scale, const float* shift, const void* res, int ld_res, const pn2_conv_desc* d,
                          void* stream) {
     if (!d || !scale || !shift) return -1;
-    if (!(d->flags & PN2_CONV_AFFINE) || (d->flags & (PN2_CONV_STATS | PN2_CONV_BIAS | PN2_CONV_ACCUM | PN2_CONV_ROWGATE)) || ((d->flags >> 16) & 15) > 1) return -2;
+    if (!(d->flags & PN2_CONV_AFFINE) || (d->flags & (PN2_CONV_STATS | PN2_CONV_BIAS | PN2_CONV_ACCUM | PN2_CONV_ROWGATE)) || conv_ksplit(*d) > 1) return -2;
     const int vec_ = dtype == PN2_BF16 ? 8 : 4;
     if (res && (d->Cout % vec_ || d->ld_out % vec_ || ld_res % vec_)) return -2;
     pn2_conv_ep ep;
     memset(&ep, 0, sizeof(ep));
     ep.a.y = res; ep.a.ld_y = ld_res;
     if (!in || !wp || !out) return -1;
-    if (d->Cin_p % 8 || d->ld_in % 8 || d->Kp % 128 || (d->stride != 1 && d->stride != 2 && d->stride != 4 && d->stride != 8)) return -2;
-    if (dtype == PN2_BF16) return gemm_dispatch<bf16_t, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
-    if (dtype == PN2_F32) return gemm_dispatch<float, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
-    if (dtype == PN2_F32F) return gemm_dispatch<f32f_t, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
-    if (dtype == PN2_F32X3) return gemm_dispatch<f32x3_t, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
-    return -3;
+    if (!conv_desc_ok(*d)) return -2;
+    return with_dtype(dtype, [&](auto ty) {
+        return gemm_dispatch<typename decltype(ty)::type, false>(in, wp, out, const_cast<float*>(scale), const_cast<float*>(shift), *d, ep, (hipStream_t)stream);
+    });
 }
 
 int pn2_conv_gemm_gated(int dtype, const void* in, const void* wp, void* out, float* psum, float* psq, const pn2_conv_desc* d, const float* gate, void* stream) {
@@ -2875,7 +2739,7 @@ int pn2_conv_gemm_gated(int dtype, const void* in, const void* wp, void* out, fl
 int pn2_conv_gemm_ep(int dtype, const void* in, const void* wp, void* out, const pn2_conv_desc* d, const pn2_conv_ep* ep, void* stream) {
     if (!d || !ep) return -1;
     const int vec = dtype == PN2_BF16 ? 8 : 4;
-    if ((d->flags & (PN2_CONV_STATS | PN2_CONV_BIAS)) || ((d->flags >> 16) & 15) > 1) return -2;
+    if ((d->flags & (PN2_CONV_STATS | PN2_CONV_BIAS)) || conv_ksplit(*d) > 1) return -2;
     if (d->Cout % vec || d->ld_out % vec) return -2;                      // the statistics live in the 16-byte store path
     if (ep->c.mode) {          // second BatchNorm behind target a's masked gradient: LDS-DMA / matrix-core epilogue form only (tiles of <= 4096 elements, bf16, single launches)
         if (dtype != PN2_BF16 || ep->c.mode != PN2_BNB_STATS || !(ep->a.mode & PN2_BNB_STATS) || ep->b.out || ep->c.split) return -2;
@@ -2895,25 +2759,26 @@ int pn2_conv_gemm_ep(int dtype, const void* in, const void* wp, void* out, const
 /* tile (bm << 8 | bn) pn2_conv_gemm would run this desc on (its tuning bits included); < 0: the launch cannot join a table (split-K, alignment) */
 int pn2_conv_gemm_tile(int dtype, const pn2_conv_desc* d) {
     if (!d) return -1;
-    if (d->Cin_p % 8 || d->ld_in % 8 || d->Kp % 128 || (d->stride != 1 && d->stride != 2 && d->stride != 4 && d->stride != 8)) return -2;
-    if (((d->flags >> 16) & 15) > 1) return -2;
-    const int ksb = (d->flags >> 8) & 0xC0;          // intra-workgroup split-K (another fp32 summation order): such jobs only share tables among themselves
-    if (ksb & 0x80) return -2;
+    if (!conv_desc_ok(*d)) return -2;
+    if (conv_ksplit(*d) > 1) return -2;
+    const int ksb = conv_tune(*d) & (TUNE_KS2 | TUNE_KS4);          // intra-workgroup split-K (another fp32 summation order): such jobs only share tables among themselves
+    if (ksb & TUNE_KS4) return -2;
     int kern, bm, bn;
-    if (dtype == PN2_BF16) { gemm_select<bf16_t>(*d, kern, bm, bn); if (!dma_extent_ok(*d)) return -2; }      // (a register-staged choice joins the table on the LDS-DMA kernel: same bits)
-    else if (dtype == PN2_F32) gemm_select<float>(*d, kern, bm, bn);
-    else if (dtype == PN2_F32F) gemm_select<f32f_t>(*d, kern, bm, bn);
-    else if (dtype == PN2_F32X3) gemm_select<f32x3_t>(*d, kern, bm, bn);
-    else return -3;
+    const int rc = with_dtype(dtype, [&](auto ty) {
+        using T = typename decltype(ty)::type;
+        gemm_select<T>(*d, kern, bm, bn);
+        return sizeof(T) == 2 && !dma_extent_ok(*d) ? -2 : 0;          // (a register-staged bf16 choice joins the table on the LDS-DMA kernel: same bits)
+    });
+    if (rc) return rc;
     if (ksb) {
         if (dtype != PN2_BF16 || bn < 64 || (bm == 128 && bn == 128)) return -2;
-        return ((bm | 0x100) << 8) | bn;          // bm carries the split-K bit through pn2_conv_gemm_job_blocks / pn2_conv_gemm_multi
+        return ((bm | TILE_KS2) << 8) | bn;          // bm carries the split-K bit through pn2_conv_gemm_job_blocks / pn2_conv_gemm_multi
     }
     return (bm << 8) | bn;
 }
 
 int pn2_conv_gemm_job_blocks(int dtype, const pn2_conv_job* j, int bm, int bn) {
-    bm &= 0xff;          // (bit 8: the split-K table kernel, same tile)
+    bm &= 0xff;          // (TILE_KS2: the split-K table kernel, same tile)
     if (!j || !j->in || !j->wp || !j->out || bm < 1 || bn < 1) return -1;
     const pn2_conv_desc& d = j->d;
     if ((d.flags & PN2_CONV_STATS) && (!j->psum || !j->psq)) return -1;
@@ -2939,16 +2804,12 @@ int pn2_conv_wgrad(int dtype, const void* dy, const void* x, float* slab, const 
     if (!dy || !x || !slab || !d || nsplit < 1) return -1;
     if (d->Cin_p % 8 || d->ld_x % 8 || d->ld_dy % 8 || d->Cout_p % 8) return -2;
     if (dtype != PN2_BF16 && d->tune >= 2) return -2;           // the LDS-DMA kernels (and pn2_conv_wgrad_blocks' tile for them) are bf16 only
-    if (dtype == PN2_BF16) return wgrad_dispatch<bf16_t>(dy, x, slab, *d, nsplit, (hipStream_t)stream);
-    if (dtype == PN2_F32) return wgrad_dispatch<float>(dy, x, slab, *d, nsplit, (hipStream_t)stream);
-    if (dtype == PN2_F32F) return wgrad_dispatch<f32f_t>(dy, x, slab, *d, nsplit, (hipStream_t)stream);
-    if (dtype == PN2_F32X3) return wgrad_dispatch<f32x3_t>(dy, x, slab, *d, nsplit, (hipStream_t)stream);
-    return -3;
+    return with_dtype(dtype, [&](auto ty) { return wgrad_dispatch<typename decltype(ty)::type>(dy, x, slab, *d, nsplit, (hipStream_t)stream); });
 }
 
 int pn2_conv_wgrad_variant(int dtype, const pn2_wgrad_desc* d) {
     if (!d) return -1;
-    return dtype == PN2_BF16 ? wgrad_variant<bf16_t>(*d) : ((dtype == PN2_F32 || dtype == PN2_F32F || dtype == PN2_F32X3) ? wgrad_variant<float>(*d) : -3);
+    return with_dtype(dtype, [&](auto ty) { return sizeof(typename decltype(ty)::type) == 2 ? wgrad_variant<bf16_t>(*d) : wgrad_variant<float>(*d); });      // (one rule for the three fp32 modes)
 }
 
 int pn2_conv_wgrad_blocks(const pn2_wgrad_desc* d, int nsplit) {
@@ -2960,11 +2821,7 @@ int pn2_conv_wgrad_blocks(const pn2_wgrad_desc* d, int nsplit) {
 
 int pn2_conv_wgrad_multi(int dtype, int variant, const pn2_wgrad_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
     if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1 || variant < 0 || variant >= 15) return -1;
-    if (dtype == PN2_BF16) return wgrad_multi_dispatch<bf16_t>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream);
-    if (dtype == PN2_F32) return wgrad_multi_dispatch<float>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream);
-    if (dtype == PN2_F32F) return wgrad_multi_dispatch<f32f_t>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream);
-    if (dtype == PN2_F32X3) return wgrad_multi_dispatch<f32x3_t>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream);
-    return -3;
+    return with_dtype(dtype, [&](auto ty) { return wgrad_multi_dispatch<typename decltype(ty)::type>(variant, jobs_dev, block_start_dev, njobs, total_blocks, (hipStream_t)stream); });
 }
 
 int pn2_pack_weight(int dtype, const float* w, void* wp, const pn2_pack_desc* p, void* stream) {

@@ -1495,9 +1495,7 @@ static int attn_fwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld
     const size_t lds = (size_t)2 * HD * (NP + 1) * 4;
     const int qpb = 64;
     const dim3 grid((Nq + qpb - 1) / qpb, heads, B);
-#define PN2_ATTN_FWD(NKV) { if (lds > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_k<T, NKV, HD>), \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; } } \
-        hipLaunchKernelGGL((attn_fwd_k<T, NKV, HD>), grid, dim3(256), lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (T*)out, ld_o, lse, Nq, Nkv, heads, scale, qpb); }
+#define PN2_ATTN_FWD(NKV) return pn2_launch<attn_fwd_k<T, NKV, HD>>(grid, dim3(256), lds, (int)lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (T*)out, ld_o, lse, Nq, Nkv, heads, scale, qpb);
     constexpr bool use_mfma = true;
     if (dt == PN2_BF16 && use_mfma && (ld_q % 8) == 0 && (ld_kv % 8) == 0 && (ld_o % 8) == 0) {
         const int NPK = NK == 3 ? 256 : NP;                        // 129..192 keys run the 256-key instantiation (zero-padded keys are masked)
@@ -1505,18 +1503,12 @@ static int attn_fwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld
         const int ntile = (Nq + 127) / 128;
         int gx = (attn_target_blocks() + B * heads - 1) / (B * heads); if (gx > ntile) gx = ntile; if (gx < 1) gx = 1;
         const dim3 gm(gx, heads, B);
-#define PN2_ATTN_FWD_M(NKV) { if (lm > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_mfma_k<NKV, HD>), \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); done = true; } } \
-        hipLaunchKernelGGL((attn_fwd_mfma_k<NKV, HD>), gm, dim3(512), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (bf16_t*)out, ld_o, lse, Nq, Nkv, heads, scale); }
+#define PN2_ATTN_FWD_M(NKV) return pn2_launch<attn_fwd_mfma_k<NKV, HD>>(gm, dim3(512), lm, (int)lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (bf16_t*)out, ld_o, lse, Nq, Nkv, heads, scale);
         if (NK == 1) PN2_ATTN_FWD_M(1) else if (NK == 2) PN2_ATTN_FWD_M(2) else PN2_ATTN_FWD_M(4)
 #undef PN2_ATTN_FWD_M
-        PN2_CHECK_LAUNCH();
-        return 0;
     }
     VIT_DISPATCH(dt, { if (NK == 1) PN2_ATTN_FWD(1) else if (NK == 2) PN2_ATTN_FWD(2) else if (NK == 3) PN2_ATTN_FWD(3) else PN2_ATTN_FWD(4) })
 #undef PN2_ATTN_FWD
-    PN2_CHECK_LAUNCH();
-    return 0;
 }
 
 static bool attn_use_mfma(int dt, int ld_a, int ld_b) {
@@ -1538,17 +1530,11 @@ static int attn_bwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld
             const int nkb = NP - key0 >= 128 ? 2 : 1;
             const int np = nkb * 64;
             const size_t lm = ((size_t)np * at_tr<HD>() + (size_t)np * (HD + 8) + 2 * 64 * at_tr<HD>() + 64 * (np + 8) + 2 * (size_t)np * 72) * 2;
-            if (nkb == 2) {
-                static bool done = false;
-                if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_k<2, HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); done = true; }
-                hipLaunchKernelGGL((attn_bwd_mfma_k<2, HD>), grid, dim3(256), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta, (bf16_t*)dq, ld_dq,
-                                   partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0);
-            } else {
-                static bool done1 = false;
-                if (!done1) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_k<1, HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); done1 = true; }
-                hipLaunchKernelGGL((attn_bwd_mfma_k<1, HD>), grid, dim3(256), lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta, (bf16_t*)dq, ld_dq,
-                                   partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0);
-            }
+            const int rc = nkb == 2 ? pn2_launch<attn_bwd_mfma_k<2, HD>>(grid, dim3(256), lm, (int)lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta,
+                                                                         (bf16_t*)dq, ld_dq, partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0)
+                                    : pn2_launch<attn_bwd_mfma_k<1, HD>>(grid, dim3(256), lm, (int)lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta,
+                                                                         (bf16_t*)dq, ld_dq, partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0);
+            if (rc) return rc;
         }
         hipLaunchKernelGGL((attn_bwd_kv_reduce_k<bf16_t, HD>), dim3(Nkv, heads, B), dim3(HD), 0, st, partial, (bf16_t*)dkv, ld_dkv, Nkv, NP, heads, nqt);
         PN2_CHECK_LAUNCH();
@@ -1560,12 +1546,12 @@ static int attn_bwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld
     const int QB = NK == 4 ? 2 : AT_QB;                 // 256 keys: smaller query groups so that K, V and the tiles fit the 160 KiB of LDS
     const size_t lds = ((size_t)2 * HD * (NP + 1) + 2 * 4 * QB * NP + 2 * 4 * QB * HD) * 4;
     const dim3 grid(nqb, heads, B);
-#define PN2_ATTN_BWD(NKV, QBV) { if (lds > 64 * 1024) { static bool done = false; if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_k<T, NKV, QBV, HD>), \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; } } \
-        hipLaunchKernelGGL((attn_bwd_k<T, NKV, QBV, HD>), grid, dim3(256), lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (const T*)dout, ld_do, lse, (T*)dq, ld_dq, \
-                           partial, Nq, Nkv, heads, scale); }
+#define PN2_ATTN_BWD(NKV, QBV) rc = pn2_launch<attn_bwd_k<T, NKV, QBV, HD>>(grid, dim3(256), lds, (int)lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (const T*)dout, ld_do, lse, (T*)dq, ld_dq, \
+                                                                          partial, Nq, Nkv, heads, scale);
+    int rc;
     VIT_DISPATCH(dt, {
         if (NK == 1) PN2_ATTN_BWD(1, AT_QB) else if (NK == 2) PN2_ATTN_BWD(2, AT_QB) else if (NK == 3) PN2_ATTN_BWD(3, AT_QB) else PN2_ATTN_BWD(4, 2)
+        if (rc) return rc;
         hipLaunchKernelGGL((attn_bwd_kv_reduce_k<T, HD>), dim3(Nkv, heads, B), dim3(HD), 0, st, partial, (T*)dkv, ld_dkv, Nkv, NP, heads, nqb); })
 #undef PN2_ATTN_BWD
     PN2_CHECK_LAUNCH();
