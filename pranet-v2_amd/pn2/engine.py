@@ -1,7 +1,8 @@
 """Host engine: the Engine class = core state (allocation, tape, lock-step regions) + the op mix-ins.
 
 pn2/core.py       activations, caches, tuning table, behaviour switches, deferred weight-gradient queue
-pn2/ops_conv.py   packing, tuners, conv + BatchNorm ops (forward and backward)
+pn2/ops_conv.py   packing, tuners, conv + BatchNorm ops (forward and backward): descriptor builders (_conv_desc, _wgrad_desc, _bn_desc), conv_bn_act as an
+                  orchestrator over named steps with one per-call record, the one BatchNorm path (_bn_forward, _bn_backward_plain) and weight-gradient path (_wgrad)
 pn2/ops_encoder.py  PVTv2 / EMCAD ops
 pn2/ops_spatial.py  pooling, resampling, element-wise, DSRA ops
 Everything importable from pn2.engine before the split still is (the switches live in pn2.core: patch them there)."""

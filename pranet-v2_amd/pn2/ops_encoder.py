@@ -1,13 +1,14 @@
 """Engine ops, part 2: what the PVTv2 encoder and the EMCAD decoder need beyond convs - LayerNorm, attention, depth-wise convs, DropPath, channel
 shuffles, gates, global pools.  Mixed into pn2.engine.Engine."""
 import ctypes as C
+from types import SimpleNamespace
 
 import torch
 
-from . import capi
 from . import core
 from .capi import call, F32, BF16
 from .core import (Act, _PERMS, _p, _stream, rup)
+from .ops_conv import _bn_desc, _relu_code
 
 
 _DP_KEEP = {}          # (drop probabilities, batch, device) -> [K][N] table of keep probabilities (drop_path_plan)
@@ -179,54 +180,25 @@ class EncoderOps:
         raw = self.empty(N, H, W, Cc)
         psum, psq = (self.fbuf(nblk, Cc), self.fbuf(nblk, Cc)) if train else (None, None)
         launch(raw, psum, psq)
-        bd = capi.BnDesc()
-        bd.M, bd.Cp, bd.C, bd.gw, bd.gwp, bd.eps, bd.momentum = M, Cc, Cc, Cc, Cc, bn.eps, (bn.momentum if bn.momentum is not None else 0.1)
-        scale, shift = self.fbuf(Cc), self.fbuf(Cc)
-        mean = invstd = None
-        if train:
-            mean, invstd = self.fbuf(Cc), self.fbuf(Cc)
-            call.pn2_bn_finalize(_p(psum), _p(psq), nblk, C.byref(bd), _p(bn.weight), _p(bn.bias), _p(bn.running_mean), _p(bn.running_var),
-                                 _p(scale), _p(shift), _p(mean), _p(invstd), st)
-            self.bn_modules.append(bn)
-            if bias is not None:
-                with torch.no_grad():
-                    bn.running_mean.add_(bias.detach(), alpha=bd.momentum)
-        else:
-            call.pn2_bn_eval_prepare(C.byref(bd), _p(bn.weight), _p(bn.bias), _p(bn.running_mean), _p(bn.running_var), _p(scale), _p(shift), st)
-            if bias is not None:
-                shift += bias.detach() * scale
+        bd = _bn_desc(bn, M, Cc, Cc, Cc, Cc)
+        rows = (self.fbuf(Cc), self.fbuf(Cc)) + ((self.fbuf(Cc), self.fbuf(Cc)) if train else (None, None))
+        scale, shift, mean, invstd = self._bn_forward(bn, bd, rows, psum, psq, nblk, bias)
         out = Act(self, self.empty(N, H, W, Cc), Cc, Cc, Cc, self.dt)
-        if residual is not None:
-            assert residual.Cp == Cc and residual.dt == self.dt
+        assert residual is None or (residual.Cp == Cc and residual.dt == self.dt)
         call.pn2_affine_act(self.dt, _p(raw), Cc, self.dt, out.ptr, out.ld, M, Cc, _p(scale), _p(shift),
-                            residual.ptr if residual is not None else C.c_void_p(0), residual.ld if residual is not None else 0, (2 if relu == 2 else 1) if relu else 0, st)
+                            residual.ptr if residual is not None else C.c_void_p(0), residual.ld if residual is not None else 0, _relu_code(relu), st)
         if not self.need_grad:
             return out
 
         def bwd():
-            st = _stream()
             if not train:
                 raise RuntimeError("backward through eval-mode BatchNorm is not supported")
             dy = out.grad_buf()
             assert out.grad_written or out.child_written
             draw = self.empty(N, H, W, Cc)
-            ymask = out if relu else None
-            r6 = 1 if relu == 2 else 0
-            nul = C.c_void_p(0)
-            nb = call.pn2_bn_bwd_blocks(M, Cc, self.dt)
-            p1, p2 = self.fbuf(nb, Cc), self.fbuf(nb, Cc)
-            call.pn2_bn_bwd_reduce(self.dt, self.dt, _p(dy), dy.stride(2), Cc, ymask.ptr if ymask else nul, ymask.ld if ymask else 0, self.dt,
-                                   _p(raw), Cc, M, Cc, _p(mean), _p(invstd), _p(p1), _p(p2), nb, nul, nul, r6, st)
-            coef = self.fbuf(3 * Cc)
-            gg, ga = self.pgrads.sink(bn.weight)
-            gb, gba = self.pgrads.sink(bn.bias)
-            call.pn2_bn_bwd_finalize(_p(p1), _p(p2), nb, C.byref(bd), _p(bn.weight), _p(invstd), _p(gg), _p(gb), ga, _p(coef), st)
-            rg, racc = (None, 0)
-            if residual is not None and residual.requires_grad:
-                rg, racc = residual.grad_sink()
-            call.pn2_bn_bwd_apply(self.dt, self.dt, _p(dy), dy.stride(2), Cc, ymask.ptr if ymask else nul, ymask.ld if ymask else 0, self.dt,
-                                  _p(raw), Cc, M, Cc, _p(mean), _p(invstd), _p(coef), _p(draw), Cc,
-                                  _p(rg), rg.stride(2) if rg is not None else 0, racc, nul, nul, r6, st)
+            b = SimpleNamespace(st=_stream(), dy=dy, dt_dy=self.dt, Cdy=Cc, ymask=out if relu else None, raw=raw, raw_ld=Cc, M=M, Cp=Cc, mean=mean, invstd=invstd,
+                                msc=None, msh=None, r6=1 if relu == 2 else 0)
+            self._bn_backward_plain(b, [(bn, bd, 0)], draw, res_sink=lambda: residual.grad_sink() if residual is not None and residual.requires_grad else (None, 0))
             if bias is not None:
                 gbi, gbia = self.pgrads.sink(bias)
                 self.colsum(draw, M, Cc, Cc, gbi, gbia)
