@@ -757,79 +757,108 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows_tab(const pn2_bnapply_j
 }
 
 
-inline void rows_geometry(int M, int CV, int& cvp, int& rows_per_blk, int& nblk) {
-    cvp = 1; while (cvp < CV && cvp < 256) cvp <<= 1;
-    const int R = 256 / cvp;
-    // aim at ~1024 workgroups (4 per CU).  With scalar parameter loads every block paid a ~60-instruction prologue and 512 was the optimum; with the
-    // 16-byte parameter loads the step time is flat from 768 up (15.59 / 15.57 / 15.51 / 15.51 / 15.49 ms at 384 / 512 / 768 / 1024 / 2048)
-    constexpr int target = 1024;         // workgroups of a streaming pass (swept 256 .. 2048: flat up to 512 per pass kind)
-    int want = (M + target - 1) / target;
-    rows_per_blk = ((want + R - 1) / R) * R;
-    if (rows_per_blk < R) rows_per_blk = R;
-    if (rows_per_blk > R * RU * 4) rows_per_blk = R * RU * 4;
-    nblk = (M + rows_per_blk - 1) / rows_per_blk;
+// rows per block of the row-walk kernels (affine_rows_*, bn_bwd_apply_rows_*): at least one and at most 4 * RU rows per row lane
+inline void rows_geometry(int M, int CV, int& cvp, int& rows_per_blk, int& nblk) { rows_walk_geometry(M, CV, 1, RU * 4, cvp, rows_per_blk, nblk); }
+
+using namespace pn2_host;
+constexpr int GRID_CAP = 8192;          // grid_for cap of this file's element-wise kernels
+
+// ---- launch plans.  One function per kernel family decides vector-or-scalar and the geometry; the single-launch entry point and its
+// pn2_*_job_blocks twin both call it, so the table-driven launches run the single launches' arithmetic by construction.
+struct RowsPlan {
+    bool vec;                        // the kernel over 16-byte vectors (else the element-wise / scalar one)
+    int cvp, rows_per_blk, nblk;     // channel vectors (scalar reduce: channels) per block, a power of two; rows per block; grid
+};
+// affine and BN backward apply: row walk over vectors (rows_geometry), else one thread per element
+inline RowsPlan rows_plan(bool vec, int M, int C, int V) {
+    RowsPlan p{vec, 0, 0, 0};
+    if (vec) rows_geometry(M, C / V, p.cvp, p.rows_per_blk, p.nblk);
+    else p.nblk = grid_for((size_t)M * C, GRID_CAP);
+    return p;
+}
+// BN backward reduce: the caller brings the grid (pn2_bn_bwd_blocks), a block takes ceil(M / nblk) rows
+inline RowsPlan reduce_plan(bool vec, int M, int Cp, int V, int nblk) {
+    int cvp = pow2ceil(vec ? Cp / V : Cp); if (cvp > 256) cvp = 256;
+    return RowsPlan{vec, cvp, (M + nblk - 1) / nblk, nblk};
+}
+inline bool affine_aligned(int V, int C, int ld_x, int ld_y, const void* res, int ld_res) { return C % V == 0 && ld_x % V == 0 && ld_y % V == 0 && (!res || ld_res % V == 0); }
+inline bool reduce_aligned(int V, int Cp, int ld_dy, int ld_x, const void* y, int ld_y) { return Cp % V == 0 && ld_dy % V == 0 && ld_x % V == 0 && (!y || ld_y % V == 0); }
+inline bool apply_aligned(int V, int Cp, int ld_dy, int ld_dx, const void* coef, int ld_x, const void* y, int ld_y, const void* dres, int ld_dres) {
+    return Cp % V == 0 && ld_dy % V == 0 && ld_dx % V == 0 && (!coef || ld_x % V == 0) && (!y || ld_y % V == 0) && (!dres || ld_dres % V == 0);
+}
+// the finalize kernels: channels per block from the number of partial rows, grid over the channels
+struct FinPlan { int cpb, nblk; };
+inline FinPlan finalize_plan(int nrows, int Cp) { const int cpb = finalize_cpb(nrows); return FinPlan{cpb, (Cp + cpb - 1) / cpb}; }
+// segmented partial rows: the most rows of any segment, or the refusal.  increasing_c0: pn2_bn_bwd_finalize_seg refuses segment starts that do not
+// increase; pn2_bn_bwd_finalize_job_blocks never did and still does not (its callers build the segments themselves)
+inline int seg_rows(const pn2_bn_segs& sg, bool increasing_c0) {
+    if (sg.nseg < 1 || sg.nseg > 4 || sg.c0[0] != 0) return -2;
+    int nmax = 1;
+    for (int k = 0; k < sg.nseg; ++k) {
+        if (!sg.p1[k] || !sg.p2[k] || sg.nblk[k] < 1 || sg.ldp[k] < 1) return -1;
+        if (increasing_c0 && k && sg.c0[k] <= sg.c0[k - 1]) return -2;
+        if (sg.nblk[k] > nmax) nmax = sg.nblk[k];
+    }
+    return nmax;
 }
 
-inline int grid_for(size_t total) { size_t g = (total + 255) / 256; return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
-inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+template <typename T>
+int launch_affine_rows(const RowsPlan& p, hipStream_t st, const void* x, int ld_x, void* y, int ld_y, int M, int C, const float* scale, const float* shift, const void* res, int ld_res, int relu,
+                       const void* add = nullptr, int ld_add = 0, void* y2 = nullptr, int ld_y2 = 0, void* y3 = nullptr, int ld_y3 = 0, int c_lo = 0) {
+    return pn2_launch<affine_rows_k<T>>(dim3(p.nblk), dim3(256), 0, 0, st, (const T*)x, ld_x, (T*)y, ld_y, M, C, scale, shift, (const T*)res, ld_res, relu, p.rows_per_blk, p.cvp,
+                                        (const T*)add, ld_add, (T*)y2, ld_y2, (T*)y3, ld_y3, c_lo);
+}
 
 template <typename Ti, typename To>
 int affine_dispatch(const void* x, int ld_x, void* y, int ld_y, int M, int C, const float* scale, const float* shift, const void* res, int ld_res, int relu, hipStream_t st) {
     constexpr int V = TT<Ti>::VEC;
-    const bool vec = sizeof(Ti) == sizeof(To) && C % V == 0 && ld_x % V == 0 && ld_y % V == 0 && (!res || ld_res % V == 0);
-    if constexpr (sizeof(Ti) == sizeof(To)) {
-        if (vec) {
-            int cvp, rpb, nblk;
-            rows_geometry(M, C / V, cvp, rpb, nblk);
-            hipLaunchKernelGGL((affine_rows_k<Ti>), dim3(nblk), dim3(256), 0, st, (const Ti*)x, ld_x, (Ti*)y, ld_y, M, C, scale, shift, (const Ti*)res, ld_res, relu, rpb, cvp);
-            PN2_CHECK_LAUNCH();
-            return 0;
-        }
+    constexpr bool same = sizeof(Ti) == sizeof(To);
+    const RowsPlan p = rows_plan(same && affine_aligned(V, C, ld_x, ld_y, res, ld_res), M, C, V);
+    if constexpr (same) {
+        if (p.vec) return launch_affine_rows<Ti>(p, st, x, ld_x, y, ld_y, M, C, scale, shift, res, ld_res, relu);
     }
-    if (vec) hipLaunchKernelGGL((affine_act_k<Ti, To, V>), dim3(grid_for((size_t)M * (C / V))), dim3(256), 0, st, (const Ti*)x, ld_x, (To*)y, ld_y, M, C, scale, shift, (const Ti*)res, ld_res, relu);
-    else hipLaunchKernelGGL((affine_act_k<Ti, To, 1>), dim3(grid_for((size_t)M * C)), dim3(256), 0, st, (const Ti*)x, ld_x, (To*)y, ld_y, M, C, scale, shift, (const Ti*)res, ld_res, relu);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    auto elementwise = [&](auto w, int grid) {
+        return pn2_launch<affine_act_k<Ti, To, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, st, (const Ti*)x, ld_x, (To*)y, ld_y, M, C, scale, shift, (const Ti*)res, ld_res, relu);
+    };
+    if (p.vec) return elementwise(Int<V>{}, grid_for((size_t)M * (C / V), GRID_CAP));          // (never taken: a vector plan has left above; the instantiation is part of the built set)
+    return elementwise(Int<1>{}, p.nblk);
 }
 
 template <typename T, typename Tdy>
 int bwd_reduce_dispatch(const void* dy, int ld_dy, int Cdy, const void* y, int ld_y, const void* x, int ld_x, int M, int Cp,
                         const float* mean, const float* invstd, float* p1, float* p2, int nblk, const float* msc, const float* msh, int r6, hipStream_t st) {
     constexpr int V = TT<T>::VEC;
-    const bool vec = sizeof(T) == sizeof(Tdy) && Cdy == Cp && Cp % V == 0 && ld_dy % V == 0 && ld_x % V == 0 && (!y || ld_y % V == 0);
-    const int rows = (M + nblk - 1) / nblk;
-    if (vec) {
-        int cvp = pow2ceil(Cp / V); if (cvp > 256) cvp = 256;
-        if (!y) hipLaunchKernelGGL((bn_bwd_reduce_k<T, Tdy, V, true>), dim3(nblk), dim3(256), 2 * 256 * V * 4, st, (const Tdy*)dy, ld_dy, Cdy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, p1, p2, rows, cvp, msc, msh, r6);
-        else hipLaunchKernelGGL((bn_bwd_reduce_k<T, Tdy, V>), dim3(nblk), dim3(256), 2 * 256 * V * 4, st, (const Tdy*)dy, ld_dy, Cdy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, p1, p2, rows, cvp, msc, msh, r6);
-    } else {
-        int cvp = pow2ceil(Cp); if (cvp > 256) cvp = 256;
-        hipLaunchKernelGGL((bn_bwd_reduce_k<T, Tdy, 1>), dim3(nblk), dim3(256), 2 * 256 * 4, st, (const Tdy*)dy, ld_dy, Cdy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, p1, p2, rows, cvp, msc, msh, r6);
-    }
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const RowsPlan p = reduce_plan(sizeof(T) == sizeof(Tdy) && Cdy == Cp && reduce_aligned(V, Cp, ld_dy, ld_x, y, ld_y), M, Cp, V, nblk);
+    auto launch = [&](auto w, auto lean) {
+        constexpr int W = decltype(w)::value;
+        return pn2_launch<bn_bwd_reduce_k<T, Tdy, W, decltype(lean)::value>>(dim3(p.nblk), dim3(256), 2 * 256 * W * 4, 0, st, (const Tdy*)dy, ld_dy, Cdy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp,
+                                                                             mean, invstd, p1, p2, p.rows_per_blk, p.cvp, msc, msh, r6);
+    };
+    if (!p.vec) return launch(Int<1>{}, Bool<false>{});
+    return y ? launch(Int<V>{}, Bool<false>{}) : launch(Int<V>{}, Bool<true>{});          // no stored activation: the register-lean instantiation
 }
 
 template <typename T, typename Tdy>
 int bwd_apply_dispatch(const void* dy, int ld_dy, int Cdy, const void* y, int ld_y, const void* x, int ld_x, int M, int Cp, const float* mean,
                        const float* invstd, const float* coef, void* dx, int ld_dx, void* dres, int ld_dres, int dres_accum, const float* msc, const float* msh, int r6, hipStream_t st) {
     constexpr int V = TT<T>::VEC;
-    const bool vec = sizeof(T) == sizeof(Tdy) && Cdy == Cp && Cp % V == 0 && ld_dy % V == 0 && ld_dx % V == 0 && (!coef || ld_x % V == 0) &&
-                     (!y || ld_y % V == 0) && (!dres || ld_dres % V == 0);
-    if constexpr (sizeof(T) == sizeof(Tdy)) {
-        if (vec) {
-            int cvp, rpb, nblk;
-            rows_geometry(M, Cp / V, cvp, rpb, nblk);
-            if (!y && !dres) hipLaunchKernelGGL((bn_bwd_apply_rows_k<T, true>), dim3(nblk), dim3(256), 0, st, (const T*)dy, ld_dy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, coef, (T*)dx, ld_dx, (T*)dres, ld_dres, dres_accum, rpb, cvp, msc, msh, r6);
-            else hipLaunchKernelGGL((bn_bwd_apply_rows_k<T, false>), dim3(nblk), dim3(256), 0, st, (const T*)dy, ld_dy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, coef, (T*)dx, ld_dx, (T*)dres, ld_dres, dres_accum, rpb, cvp, msc, msh, r6);
-            PN2_CHECK_LAUNCH();
-            return 0;
+    constexpr bool same = sizeof(T) == sizeof(Tdy);
+    const RowsPlan p = rows_plan(same && Cdy == Cp && apply_aligned(V, Cp, ld_dy, ld_dx, coef, ld_x, y, ld_y, dres, ld_dres), M, Cp, V);
+    if constexpr (same) {
+        if (p.vec) {
+            auto rows = [&](auto lean) {
+                return pn2_launch<bn_bwd_apply_rows_k<T, decltype(lean)::value>>(dim3(p.nblk), dim3(256), 0, 0, st, (const T*)dy, ld_dy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, coef,
+                                                                                 (T*)dx, ld_dx, (T*)dres, ld_dres, dres_accum, p.rows_per_blk, p.cvp, msc, msh, r6);
+            };
+            return (!y && !dres) ? rows(Bool<true>{}) : rows(Bool<false>{});          // LEAN: neither a stored activation nor a residual gradient
         }
     }
-    if (vec) hipLaunchKernelGGL((bn_bwd_apply_k<T, Tdy, V>), dim3(grid_for((size_t)M * (Cp / V))), dim3(256), 0, st, (const Tdy*)dy, ld_dy, Cdy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, coef, (T*)dx, ld_dx, (T*)dres, ld_dres, dres_accum, r6);
-    else hipLaunchKernelGGL((bn_bwd_apply_k<T, Tdy, 1>), dim3(grid_for((size_t)M * Cp)), dim3(256), 0, st, (const Tdy*)dy, ld_dy, Cdy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, coef, (T*)dx, ld_dx, (T*)dres, ld_dres, dres_accum, r6);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    auto elementwise = [&](auto w, int grid) {
+        return pn2_launch<bn_bwd_apply_k<T, Tdy, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, st, (const Tdy*)dy, ld_dy, Cdy, (const T*)y, ld_y, (const T*)x, ld_x, M, Cp, mean, invstd, coef,
+                                                                      (T*)dx, ld_dx, (T*)dres, ld_dres, dres_accum, r6);
+    };
+    if (p.vec) return elementwise(Int<V>{}, grid_for((size_t)M * (Cp / V), GRID_CAP));          // (never taken, as in affine_dispatch)
+    return elementwise(Int<1>{}, p.nblk);
 }
 
 }  // namespace
@@ -839,39 +868,31 @@ extern "C" {
 int pn2_bn_finalize(const float* psum, const float* psq, int nblk, const pn2_bn_desc* d, const float* gamma, const float* beta,
                     float* running_mean, float* running_var, float* scale, float* shift, float* mean, float* invstd, void* stream) {
     if (!psum || !psq || !d || !gamma || !beta || !scale || !shift || !mean || !invstd) return -1;
-    const int cpb = finalize_cpb(nblk);
-    hipLaunchKernelGGL(bn_finalize_k, dim3((d->Cp + cpb - 1) / cpb), dim3(256), 0, (hipStream_t)stream, psum, psq, nblk, *d, gamma, beta, running_mean, running_var, scale, shift, mean, invstd, cpb);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const FinPlan p = finalize_plan(nblk, d->Cp);
+    return pn2_launch<bn_finalize_k>(dim3(p.nblk), dim3(256), 0, 0, (hipStream_t)stream, psum, psq, nblk, *d, gamma, beta, running_mean, running_var, scale, shift, mean, invstd, p.cpb);
 }
 
 int pn2_bn_eval_prepare(const pn2_bn_desc* d, const float* gamma, const float* beta, const float* rm, const float* rv, float* scale, float* shift, void* stream) {
     if (!d || !gamma || !beta || !rm || !rv || !scale || !shift) return -1;
-    hipLaunchKernelGGL(bn_eval_prepare_k, dim3((d->Cp + 255) / 256), dim3(256), 0, (hipStream_t)stream, *d, gamma, beta, rm, rv, scale, shift);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<bn_eval_prepare_k>(dim3((d->Cp + 255) / 256), dim3(256), 0, 0, (hipStream_t)stream, *d, gamma, beta, rm, rv, scale, shift);
 }
 
 int pn2_bn_eval_prepare_multi(const pn2_bnprep_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    hipLaunchKernelGGL(bn_eval_prepare_tab, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
+    return pn2_launch<bn_eval_prepare_tab>(dim3(total_blocks), dim3(256), 0, 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
 }
 
 int pn2_affine_act(int dt_in, const void* x, int ld_x, int dt_out, void* y, int ld_y, int M, int Cout, const float* scale, const float* shift,
                    const void* res, int ld_res, int relu, void* stream) {
     if (!x || !y) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt_in == PN2_BF16 && dt_out == PN2_BF16) return affine_dispatch<bf16_t, bf16_t>(x, ld_x, y, ld_y, M, Cout, scale, shift, res, ld_res, relu, st);
-    if (dt_in == PN2_BF16 && dt_out == PN2_F32) return affine_dispatch<bf16_t, float>(x, ld_x, y, ld_y, M, Cout, scale, shift, res, ld_res, relu, st);
-    if (dt_in == PN2_F32 && dt_out == PN2_F32) return affine_dispatch<float, float>(x, ld_x, y, ld_y, M, Cout, scale, shift, res, ld_res, relu, st);
-    return -3;
+    return with_dtype_pair(dt_in, dt_out, [&](auto ti, auto to) {
+        return affine_dispatch<type_of<decltype(ti)>, type_of<decltype(to)>>(x, ld_x, y, ld_y, M, Cout, scale, shift, res, ld_res, relu, (hipStream_t)stream);
+    });
 }
 
 int pn2_bn_bwd_blocks(int M, int Cp, int dt) {
     // >= 8 rows per thread: 256 threads = CVP channel vectors x R row lanes
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     const int cv = Cp % V == 0 ? Cp / V : Cp;
     int cvp = 1; while (cvp < cv && cvp < 256) cvp <<= 1;
     const int rows = (256 / cvp) * 2;     // >= 2 rows per thread, at most 512 partial rows for the finalize pass (measured optimum)
@@ -885,36 +906,25 @@ int pn2_bn_bwd_reduce(int dt, int dt_dy, const void* dy, int ld_dy, int Cdy, con
                       const float* mask_scale, const float* mask_shift, int relu6, void* stream) {
     if (!dy || !x || !mean || !invstd || !p1 || !p2) return -1;
     if (y && dt_y != dt) return -2;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16 && dt_dy == PN2_BF16) return bwd_reduce_dispatch<bf16_t, bf16_t>(dy, ld_dy, Cdy, y, ld_y, x, ld_x, M, Cp, mean, invstd, p1, p2, nblk, mask_scale, mask_shift, relu6, st);
-    if (dt == PN2_BF16 && dt_dy == PN2_F32) return bwd_reduce_dispatch<bf16_t, float>(dy, ld_dy, Cdy, y, ld_y, x, ld_x, M, Cp, mean, invstd, p1, p2, nblk, mask_scale, mask_shift, relu6, st);
-    if (dt == PN2_F32 && dt_dy == PN2_F32) return bwd_reduce_dispatch<float, float>(dy, ld_dy, Cdy, y, ld_y, x, ld_x, M, Cp, mean, invstd, p1, p2, nblk, mask_scale, mask_shift, relu6, st);
-    return -3;
+    return with_dtype_pair(dt, dt_dy, [&](auto t, auto tdy) {
+        return bwd_reduce_dispatch<type_of<decltype(t)>, type_of<decltype(tdy)>>(dy, ld_dy, Cdy, y, ld_y, x, ld_x, M, Cp, mean, invstd, p1, p2, nblk, mask_scale, mask_shift, relu6, (hipStream_t)stream);
+    });
 }
 
 int pn2_bn_bwd_finalize(const float* p1, const float* p2, int nblk, const pn2_bn_desc* d, const float* gamma, const float* invstd,
                         float* dgamma, float* dbeta, int accumulate, float* coef, void* stream) {
     if (!p1 || !p2 || !d || !gamma || !invstd || !dgamma || !dbeta || !coef) return -1;
-    const int cpb = finalize_cpb(nblk);
-    hipLaunchKernelGGL(bn_bwd_finalize_k, dim3((d->Cp + cpb - 1) / cpb), dim3(256), 0, (hipStream_t)stream, p1, p2, nblk, *d, gamma, invstd, dgamma, dbeta, accumulate, coef, cpb);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const FinPlan p = finalize_plan(nblk, d->Cp);
+    return pn2_launch<bn_bwd_finalize_k>(dim3(p.nblk), dim3(256), 0, 0, (hipStream_t)stream, p1, p2, nblk, *d, gamma, invstd, dgamma, dbeta, accumulate, coef, p.cpb);
 }
 
 int pn2_bn_bwd_finalize_seg(const pn2_bn_segs* segs, const pn2_bn_desc* d, const float* gamma, const float* invstd,
                             float* dgamma, float* dbeta, int accumulate, float* coef, void* stream) {
     if (!segs || !d || !gamma || !invstd || !dgamma || !dbeta || !coef) return -1;
-    if (segs->nseg < 1 || segs->nseg > 4 || segs->c0[0] != 0) return -2;
-    int nmax = 1;
-    for (int k = 0; k < segs->nseg; ++k) {
-        if (!segs->p1[k] || !segs->p2[k] || segs->nblk[k] < 1 || segs->ldp[k] < 1) return -1;
-        if (k && segs->c0[k] <= segs->c0[k - 1]) return -2;
-        if (segs->nblk[k] > nmax) nmax = segs->nblk[k];
-    }
-    const int cpb = finalize_cpb(nmax);
-    hipLaunchKernelGGL(bn_bwd_finalize_seg_k, dim3((d->Cp + cpb - 1) / cpb), dim3(256), 0, (hipStream_t)stream, *segs, *d, gamma, invstd, dgamma, dbeta, accumulate, coef, cpb);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const int nmax = seg_rows(*segs, true);
+    if (nmax < 0) return nmax;
+    const FinPlan p = finalize_plan(nmax, d->Cp);
+    return pn2_launch<bn_bwd_finalize_seg_k>(dim3(p.nblk), dim3(256), 0, 0, (hipStream_t)stream, *segs, *d, gamma, invstd, dgamma, dbeta, accumulate, coef, p.cpb);
 }
 
 int pn2_bn_bwd_apply(int dt, int dt_dy, const void* dy, int ld_dy, int Cdy, const void* y, int ld_y, int dt_y, const void* x, int ld_x,
@@ -923,11 +933,10 @@ int pn2_bn_bwd_apply(int dt, int dt_dy, const void* dy, int ld_dy, int Cdy, cons
     if (!dy || !dx) return -1;
     if (coef && (!x || !mean || !invstd)) return -1;
     if (y && dt_y != dt) return -2;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16 && dt_dy == PN2_BF16) return bwd_apply_dispatch<bf16_t, bf16_t>(dy, ld_dy, Cdy, y, ld_y, x, ld_x, M, Cp, mean, invstd, coef, dx, ld_dx, dres, ld_dres, dres_accum, mask_scale, mask_shift, relu6, st);
-    if (dt == PN2_BF16 && dt_dy == PN2_F32) return bwd_apply_dispatch<bf16_t, float>(dy, ld_dy, Cdy, y, ld_y, x, ld_x, M, Cp, mean, invstd, coef, dx, ld_dx, dres, ld_dres, dres_accum, mask_scale, mask_shift, relu6, st);
-    if (dt == PN2_F32 && dt_dy == PN2_F32) return bwd_apply_dispatch<float, float>(dy, ld_dy, Cdy, y, ld_y, x, ld_x, M, Cp, mean, invstd, coef, dx, ld_dx, dres, ld_dres, dres_accum, mask_scale, mask_shift, relu6, st);
-    return -3;
+    return with_dtype_pair(dt, dt_dy, [&](auto t, auto tdy) {
+        return bwd_apply_dispatch<type_of<decltype(t)>, type_of<decltype(tdy)>>(dy, ld_dy, Cdy, y, ld_y, x, ld_x, M, Cp, mean, invstd, coef, dx, ld_dx, dres, ld_dres, dres_accum,
+                                                                                mask_scale, mask_shift, relu6, (hipStream_t)stream);
+    });
 }
 
 
@@ -935,16 +944,14 @@ int pn2_bn_bwd_apply(int dt, int dt_dy, const void* dy, int ld_dy, int Cdy, cons
 int pn2_bn_relu_maxpool_fwd(int dt, const void* raw, int ld_raw, const float* scale, const float* shift, void* y, int ld_y, unsigned char* idx,
                             int N, int H, int W, int C, int OH, int OW, void* stream) {
     if (!raw || !scale || !shift || !y || !idx) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (C % V || ld_raw % V || ld_y % V || OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1) return -2;
     if ((size_t)N * OH * OW * (C / V) >= ((size_t)1 << 32) - ((size_t)8192 << 8)) return -2;
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = grid_for((size_t)N * OH * OW * (C / V));
-    if (dt == PN2_BF16) hipLaunchKernelGGL((bn_relu_maxpool_fwd_k<bf16_t, 8>), dim3(grid), dim3(256), 0, st, (const bf16_t*)raw, ld_raw, scale, shift, (bf16_t*)y, ld_y, idx, N, H, W, C, OH, OW);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((bn_relu_maxpool_fwd_k<float, 4>), dim3(grid), dim3(256), 0, st, (const float*)raw, ld_raw, scale, shift, (float*)y, ld_y, idx, N, H, W, C, OH, OW);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const int grid = grid_for((size_t)N * OH * OW * (C / V), GRID_CAP);
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<bn_relu_maxpool_fwd_k<T, TT<T>::VEC>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)raw, ld_raw, scale, shift, (T*)y, ld_y, idx, N, H, W, C, OH, OW);
+    });
 }
 
 /* Backward of pn2_bn_relu_maxpool_fwd without the full-resolution gradient tensor (even H, W; C / V a power of two <= 256): pn2_bn_bwd_reduce / pn2_bn_bwd_apply with the
@@ -952,31 +959,29 @@ int pn2_bn_relu_maxpool_fwd(int dt, const void* raw, int ld_raw, const float* sc
 int pn2_pool_bn_bwd_reduce(int dt, const void* dpool, int ld_dp, const unsigned char* idx, const void* raw, int ld_raw, int N, int H, int W, int C, int OH, int OW,
                            const float* mean, const float* invstd, const float* mask_scale, const float* mask_shift, float* p1, float* p2, int nblk, void* stream) {
     if (!dpool || !idx || !raw || !mean || !invstd || !mask_scale || !mask_shift || !p1 || !p2 || nblk < 1) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8, CV = C / V;
+    const int V = vec_of(dt), CV = C / V;
     if (C % V || ld_dp % V || ld_raw % V || (H & 1) || (W & 1) || OH != H / 2 || OW != W / 2 || CV < 1 || CV > 256 || (CV & (CV - 1))) return -2;
     if ((size_t)N * (H / 2) * (W / 2) >= ((size_t)1 << 24) - 65536 * 32) return -2;          // (quad indices decoded through a float reciprocal)
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((pool_bn_bwd_reduce_k<bf16_t, 8>), dim3(nblk), dim3(256), 0, st, (const bf16_t*)dpool, ld_dp, idx, (const bf16_t*)raw, ld_raw, N, H, W, OH, OW, C, mean, invstd, mask_scale, mask_shift, p1, p2);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((pool_bn_bwd_reduce_k<float, 4>), dim3(nblk), dim3(256), 0, st, (const float*)dpool, ld_dp, idx, (const float*)raw, ld_raw, N, H, W, OH, OW, C, mean, invstd, mask_scale, mask_shift, p1, p2);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<pool_bn_bwd_reduce_k<T, TT<T>::VEC>>(dim3(nblk), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dpool, ld_dp, idx, (const T*)raw, ld_raw, N, H, W, OH, OW, C,
+                                                               mean, invstd, mask_scale, mask_shift, p1, p2);
+    });
 }
 int pn2_pool_bn_bwd_apply(int dt, const void* dpool, int ld_dp, const unsigned char* idx, const void* raw, int ld_raw, int N, int H, int W, int C, int OH, int OW,
                           const float* mean, const float* invstd, const float* coef, const float* mask_scale, const float* mask_shift, void* dz, int ld_dz, void* stream) {
     if (!dpool || !idx || !raw || !mean || !invstd || !coef || !mask_scale || !mask_shift || !dz) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8, CV = C / V;
+    const int V = vec_of(dt), CV = C / V;
     if (C % V || ld_dp % V || ld_raw % V || ld_dz % V || (H & 1) || (W & 1) || OH != H / 2 || OW != W / 2 || CV < 1 || CV > 256 || (CV & (CV - 1))) return -2;
     const size_t nq = (size_t)N * (H / 2) * (W / 2);
     if (nq >= ((size_t)1 << 24) - 65536 * 32) return -2;
     const int QL = 256 / CV;
     int grid = (int)((nq + QL - 1) / QL); if (grid > 8192) grid = 8192; if (grid < 1) grid = 1;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((pool_bn_bwd_apply_k<bf16_t, 8>), dim3(grid), dim3(256), 0, st, (const bf16_t*)dpool, ld_dp, idx, (const bf16_t*)raw, ld_raw, N, H, W, OH, OW, C, mean, invstd, coef, mask_scale, mask_shift, (bf16_t*)dz, ld_dz);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((pool_bn_bwd_apply_k<float, 4>), dim3(grid), dim3(256), 0, st, (const float*)dpool, ld_dp, idx, (const float*)raw, ld_raw, N, H, W, OH, OW, C, mean, invstd, coef, mask_scale, mask_shift, (float*)dz, ld_dz);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<pool_bn_bwd_apply_k<T, TT<T>::VEC>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dpool, ld_dp, idx, (const T*)raw, ld_raw, N, H, W, OH, OW, C,
+                                                              mean, invstd, coef, mask_scale, mask_shift, (T*)dz, ld_dz);
+    });
 }
 
 /* pn2_affine_act (same dtype in / out, no residual) with a second output y2 = y + add: the branch sum of Bottle2neck.forward
@@ -984,144 +989,111 @@ int pn2_pool_bn_bwd_apply(int dt, const void* dpool, int ld_dp, const unsigned c
 int pn2_affine_act_sum(int dt, const void* x, int ld_x, void* y, int ld_y, int M, int C, const float* scale, const float* shift, int relu,
                        const void* add, int ld_add, void* y2, int ld_y2, void* stream) {
     if (!x || !y || !add || !y2) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
-    if (C % V || ld_x % V || ld_y % V || ld_add % V || ld_y2 % V) return -2;
-    int cvp, rpb, nblk;
-    rows_geometry(M, C / V, cvp, rpb, nblk);
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((affine_rows_k<bf16_t>), dim3(nblk), dim3(256), 0, st, (const bf16_t*)x, ld_x, (bf16_t*)y, ld_y, M, C, scale, shift, (const bf16_t*)nullptr, 0, relu, rpb, cvp,
-                                           (const bf16_t*)add, ld_add, (bf16_t*)y2, ld_y2);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((affine_rows_k<float>), dim3(nblk), dim3(256), 0, st, (const float*)x, ld_x, (float*)y, ld_y, M, C, scale, shift, (const float*)nullptr, 0, relu, rpb, cvp,
-                                               (const float*)add, ld_add, (float*)y2, ld_y2);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const int V = vec_of(dt);
+    if (!affine_aligned(V, C, ld_x, ld_y, nullptr, 0) || ld_add % V || ld_y2 % V) return -2;
+    const RowsPlan p = rows_plan(true, M, C, V);
+    return with_storage_dtype(dt, [&](auto ty) {
+        return launch_affine_rows<type_of<decltype(ty)>>(p, (hipStream_t)stream, x, ld_x, y, ld_y, M, C, scale, shift, nullptr, 0, relu, add, ld_add, y2, ld_y2);
+    });
 }
 
 int pn2_affine_act_tee(int dt, const void* x, int ld_x, void* y, int ld_y, int M, int C, const float* scale, const float* shift, int relu,
                        void* y3, int ld_y3, int c_lo, void* stream) {
     if (!x || !y || !y3) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
-    if (C % V || ld_x % V || ld_y % V || ld_y3 % V || c_lo % V || c_lo < 0 || c_lo >= C) return -2;
-    int cvp, rpb, nblk;
-    rows_geometry(M, C / V, cvp, rpb, nblk);
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((affine_rows_k<bf16_t>), dim3(nblk), dim3(256), 0, st, (const bf16_t*)x, ld_x, (bf16_t*)y, ld_y, M, C, scale, shift, (const bf16_t*)nullptr, 0, relu, rpb, cvp,
-                                           (const bf16_t*)nullptr, 0, (bf16_t*)nullptr, 0, (bf16_t*)y3, ld_y3, c_lo);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((affine_rows_k<float>), dim3(nblk), dim3(256), 0, st, (const float*)x, ld_x, (float*)y, ld_y, M, C, scale, shift, (const float*)nullptr, 0, relu, rpb, cvp,
-                                               (const float*)nullptr, 0, (float*)nullptr, 0, (float*)y3, ld_y3, c_lo);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const int V = vec_of(dt);
+    if (!affine_aligned(V, C, ld_x, ld_y, nullptr, 0) || ld_y3 % V || c_lo % V || c_lo < 0 || c_lo >= C) return -2;
+    const RowsPlan p = rows_plan(true, M, C, V);
+    return with_storage_dtype(dt, [&](auto ty) {
+        return launch_affine_rows<type_of<decltype(ty)>>(p, (hipStream_t)stream, x, ld_x, y, ld_y, M, C, scale, shift, nullptr, 0, relu, nullptr, 0, nullptr, 0, y3, ld_y3, c_lo);
+    });
 }
 
 /* ------------------------------------------------------------------------------------------------ table-driven launches
  * pn2_*_job_blocks fill the derived geometry of a job (host side) and return its workgroup count (< 0: this call cannot be batched - launch it on
  * its own); pn2_*_multi run many jobs of one kind in ONE launch from a DEVICE job table (block_start_dev: njobs + 1 prefix sums).  Same arithmetic,
- * bit for bit, as the single launches. */
+ * bit for bit, as the single launches: both sides take their geometry from the launch plans above. */
 int pn2_bn_finalize_job_blocks(pn2_bnfin_job* j) {
     if (!j || !j->psum || !j->psq || !j->gamma || !j->beta || !j->scale || !j->shift || !j->mean || !j->invstd || j->nblk < 1) return -1;
-    j->cpb = finalize_cpb(j->nblk);
-    return (j->d.Cp + j->cpb - 1) / j->cpb;
+    const FinPlan p = finalize_plan(j->nblk, j->d.Cp);
+    j->cpb = p.cpb;
+    return p.nblk;
 }
 int pn2_bn_finalize_multi(const pn2_bnfin_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    hipLaunchKernelGGL(bn_finalize_tab, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
+    return pn2_launch<bn_finalize_tab>(dim3(total_blocks), dim3(256), 0, 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
 }
 
 int pn2_affine_job_blocks(int dt, pn2_affine_job* j) {
     if (!j || !j->x || !j->y) return -1;
-    if (dt == (PN2_BF16 | PN2_MULTI_F32OUT)) {          // bf16 in, fp32 out, element-wise (pn2_affine_act's own grid)
+    if (dt == (PN2_BF16 | PN2_MULTI_F32OUT)) {          // bf16 in, fp32 out: the element-wise plan of affine_dispatch<bf16_t, float>
         if (j->y2 || j->add || j->M < 1 || j->C < 1) return -2;
-        return grid_for((size_t)j->M * j->C);
+        return rows_plan(false, j->M, j->C, 1).nblk;
     }
-    const int V = dt == PN2_F32 ? 4 : 8;
-    if (j->C % V || j->ld_x % V || j->ld_y % V || (j->res && j->ld_res % V) || (j->y2 && (!j->add || j->ld_add % V || j->ld_y2 % V))) return -2;
-    int nblk;
-    rows_geometry(j->M, j->C / V, j->cvp, j->rows_per_blk, nblk);
-    return nblk;
+    const int V = vec_of(dt);
+    if (!affine_aligned(V, j->C, j->ld_x, j->ld_y, j->res, j->ld_res) || (j->y2 && (!j->add || j->ld_add % V || j->ld_y2 % V))) return -2;
+    const RowsPlan p = rows_plan(true, j->M, j->C, V);
+    j->cvp = p.cvp; j->rows_per_blk = p.rows_per_blk;
+    return p.nblk;
 }
 int pn2_affine_multi(int dt, const pn2_affine_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    if (dt == (PN2_BF16 | PN2_MULTI_F32OUT)) hipLaunchKernelGGL(affine_act_tab_f32out, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else if (dt == PN2_BF16) hipLaunchKernelGGL((affine_rows_tab<bf16_t>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((affine_rows_tab<float>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (dt == (PN2_BF16 | PN2_MULTI_F32OUT)) return pn2_launch<affine_act_tab_f32out>(dim3(total_blocks), dim3(256), 0, 0, st, jobs_dev, block_start_dev, njobs);
+    return with_storage_dtype(dt, [&](auto ty) { return pn2_launch<affine_rows_tab<type_of<decltype(ty)>>>(dim3(total_blocks), dim3(256), 0, 0, st, jobs_dev, block_start_dev, njobs); });
 }
 
 int pn2_bn_bwd_finalize_job_blocks(pn2_bnbfin_job* j) {
     if (!j || !j->gamma || !j->invstd || !j->dgamma || !j->dbeta || !j->coef) return -1;
-    if (j->sg.nseg < 1 || j->sg.nseg > 4 || j->sg.c0[0] != 0) return -2;
-    int nmax = 1;
-    for (int k = 0; k < j->sg.nseg; ++k) {
-        if (!j->sg.p1[k] || !j->sg.p2[k] || j->sg.nblk[k] < 1 || j->sg.ldp[k] < 1) return -1;
-        if (j->sg.nblk[k] > nmax) nmax = j->sg.nblk[k];
-    }
-    j->cpb = finalize_cpb(nmax);
-    return (j->d.Cp + j->cpb - 1) / j->cpb;
+    const int nmax = seg_rows(j->sg, false);
+    if (nmax < 0) return nmax;
+    const FinPlan p = finalize_plan(nmax, j->d.Cp);
+    j->cpb = p.cpb;
+    return p.nblk;
 }
 int pn2_bn_bwd_finalize_multi(const pn2_bnbfin_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    hipLaunchKernelGGL(bn_bwd_finalize_tab, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
+    return pn2_launch<bn_bwd_finalize_tab>(dim3(total_blocks), dim3(256), 0, 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
 }
 
 int pn2_bn_bwd_apply_job_blocks(int dt, pn2_bnapply_job* j) {
     if (!j || !j->dy || !j->dx) return -1;
     if (j->coef && (!j->x || !j->mean || !j->invstd)) return -1;
-    if (dt == (PN2_BF16 | PN2_MULTI_F32DY)) return (j->M < 1 || j->Cp < 1 || j->pad_ < 1) ? -2 : grid_for((size_t)j->M * j->Cp);
-    const int V = dt == PN2_F32 ? 4 : 8;
-    if (j->Cp % V || j->ld_dy % V || j->ld_dx % V || (j->coef && j->ld_x % V) || (j->y && j->ld_y % V) || (j->dres && j->ld_dres % V)) return -2;
-    int nblk;
-    rows_geometry(j->M, j->Cp / V, j->cvp, j->rows_per_blk, nblk);
-    return nblk;
+    if (dt == (PN2_BF16 | PN2_MULTI_F32DY)) return (j->M < 1 || j->Cp < 1 || j->pad_ < 1) ? -2 : rows_plan(false, j->M, j->Cp, 1).nblk;          // element-wise, as bwd_apply_dispatch<bf16_t, float>
+    const int V = vec_of(dt);
+    if (!apply_aligned(V, j->Cp, j->ld_dy, j->ld_dx, j->coef, j->ld_x, j->y, j->ld_y, j->dres, j->ld_dres)) return -2;
+    const RowsPlan p = rows_plan(true, j->M, j->Cp, V);
+    j->cvp = p.cvp; j->rows_per_blk = p.rows_per_blk;
+    return p.nblk;
 }
 int pn2_bn_bwd_apply_multi(int dt, const pn2_bnapply_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (dt == (PN2_BF16 | PN2_MULTI_F32DY)) {
-        hipLaunchKernelGGL(bn_bwd_apply_tab_f32dy, dim3(total_blocks), dim3(256), 0, st, jobs_dev, block_start_dev, njobs);
-        PN2_CHECK_LAUNCH();
-        return 0;
-    }
+    if (dt == (PN2_BF16 | PN2_MULTI_F32DY)) return pn2_launch<bn_bwd_apply_tab_f32dy>(dim3(total_blocks), dim3(256), 0, 0, st, jobs_dev, block_start_dev, njobs);
     const bool lean = dt & PN2_MULTI_LEAN;
-    dt &= ~PN2_MULTI_LEAN;
-    if (dt == PN2_BF16 && lean) hipLaunchKernelGGL((bn_bwd_apply_rows_tab<bf16_t, true>), dim3(total_blocks), dim3(256), 0, st, jobs_dev, block_start_dev, njobs);
-    else if (dt == PN2_BF16) hipLaunchKernelGGL((bn_bwd_apply_rows_tab<bf16_t, false>), dim3(total_blocks), dim3(256), 0, st, jobs_dev, block_start_dev, njobs);
-    else if (dt == PN2_F32 && lean) hipLaunchKernelGGL((bn_bwd_apply_rows_tab<float, true>), dim3(total_blocks), dim3(256), 0, st, jobs_dev, block_start_dev, njobs);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((bn_bwd_apply_rows_tab<float, false>), dim3(total_blocks), dim3(256), 0, st, jobs_dev, block_start_dev, njobs);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt & ~PN2_MULTI_LEAN, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return lean ? pn2_launch<bn_bwd_apply_rows_tab<T, true>>(dim3(total_blocks), dim3(256), 0, 0, st, jobs_dev, block_start_dev, njobs)
+                    : pn2_launch<bn_bwd_apply_rows_tab<T, false>>(dim3(total_blocks), dim3(256), 0, 0, st, jobs_dev, block_start_dev, njobs);
+    });
 }
 
 int pn2_bn_bwd_reduce_job_blocks(int dt, pn2_bnreduce_job* j) {
     if (!j || !j->dy || !j->x || !j->mean || !j->invstd || !j->p1 || !j->p2 || j->nblk < 1) return -1;
-    if (dt == (PN2_BF16 | PN2_MULTI_F32DY)) {          // the scalar form of bwd_reduce_dispatch<bf16_t, float>
-        if (j->pad_ < 1) return -2;
-        int cvp = pow2ceil(j->Cp); if (cvp > 256) cvp = 256;
-        j->cvp = cvp; j->rows_per_blk = (j->M + j->nblk - 1) / j->nblk;
-        return j->nblk;
-    }
-    const int V = dt == PN2_F32 ? 4 : 8;
-    if (j->Cp % V || j->ld_dy % V || j->ld_x % V || (j->y && j->ld_y % V)) return -2;
-    int cvp = pow2ceil(j->Cp / V); if (cvp > 256) cvp = 256;
-    j->cvp = cvp; j->rows_per_blk = (j->M + j->nblk - 1) / j->nblk;
-    return j->nblk;
+    const bool f32dy = dt == (PN2_BF16 | PN2_MULTI_F32DY);          // the scalar plan of bwd_reduce_dispatch<bf16_t, float>
+    const int V = vec_of(dt);
+    if (f32dy ? j->pad_ < 1 : !reduce_aligned(V, j->Cp, j->ld_dy, j->ld_x, j->y, j->ld_y)) return -2;
+    const RowsPlan p = reduce_plan(!f32dy, j->M, j->Cp, V, j->nblk);
+    j->cvp = p.cvp; j->rows_per_blk = p.rows_per_blk;
+    return p.nblk;
 }
 int pn2_bn_bwd_reduce_multi(int dt, const pn2_bnreduce_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    if (dt == (PN2_BF16 | PN2_MULTI_F32DY)) hipLaunchKernelGGL(bn_bwd_reduce_tab_f32dy, dim3(total_blocks), dim3(256), 2 * 256 * 4, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else if (dt == PN2_BF16) hipLaunchKernelGGL((bn_bwd_reduce_tab<bf16_t>), dim3(total_blocks), dim3(256), 2 * 256 * 8 * 4, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((bn_bwd_reduce_tab<float>), dim3(total_blocks), dim3(256), 2 * 256 * 4 * 4, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (dt == (PN2_BF16 | PN2_MULTI_F32DY)) return pn2_launch<bn_bwd_reduce_tab_f32dy>(dim3(total_blocks), dim3(256), 2 * 256 * 4, 0, st, jobs_dev, block_start_dev, njobs);
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<bn_bwd_reduce_tab<T>>(dim3(total_blocks), dim3(256), 2 * 256 * TT<T>::VEC * 4, 0, st, jobs_dev, block_start_dev, njobs);
+    });
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
-// pn2_common.h — shared device helpers for the PraNet-V2 gfx950 kernels.
+// pn2_common.h — shared device helpers and the host launch layer of the PraNet-V2 gfx950 kernels.
 // All activations are NHWC "views": base pointer (already offset to the first channel of the
 // view), row = one pixel, `ld` = channel stride between consecutive pixels (elements).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/pn2.h"          // PN2_F32 / PN2_BF16 / PN2_F32F / PN2_F32X3
 
 typedef unsigned short bf16_t;   // storage type; arithmetic always in f32
@@ -141,4 +142,60 @@ inline int pn2_launch(dim3 grid, dim3 block, size_t lds, int lds_cap, hipStream_
     hipLaunchKernelGGL(K, grid, block, lds, st, args...);
     PN2_CHECK_LAUNCH();
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ host launch layer
+// storage type handed to a with_*dtype visitor
+template <typename T> struct Ty { using type = T; };
+template <typename X> using type_of = typename X::type;
+// compile-time int / bool handed to a generic lambda, so that one argument list serves every instantiation of a kernel
+template <int N> using Int = std::integral_constant<int, N>;
+template <bool B> using Bool = std::integral_constant<bool, B>;
+// storage type of a PN2_* dtype code, the four codes of the conv contraction entry points: f(Ty<T>), -3 for an unknown code
+template <typename F>
+int with_dtype(int dtype, F f) {
+    if (dtype == PN2_BF16) return f(Ty<bf16_t>{});
+    if (dtype == PN2_F32) return f(Ty<float>{});
+    if (dtype == PN2_F32F) return f(Ty<f32f_t>{});
+    if (dtype == PN2_F32X3) return f(Ty<f32x3_t>{});
+    return -3;
+}
+// ... of the storage-only kernels (everything but the conv contractions): bf16 and fp32, -3 for any other code
+template <typename F>
+int with_storage_dtype(int dtype, F f) {
+    if (dtype == PN2_BF16) return f(Ty<bf16_t>{});
+    if (dtype == PN2_F32) return f(Ty<float>{});
+    return -3;
+}
+// (storage, gradient / output) pairs of the mixed-type entry points: bf16 -> bf16, bf16 -> fp32, fp32 -> fp32; f(Ty<T>, Ty<Tg>), -3 for any other pair
+template <typename F>
+int with_dtype_pair(int dt, int dt_g, F f) {
+    if (dt == PN2_BF16 && dt_g == PN2_BF16) return f(Ty<bf16_t>{}, Ty<bf16_t>{});
+    if (dt == PN2_BF16 && dt_g == PN2_F32) return f(Ty<bf16_t>{}, Ty<float>{});
+    if (dt == PN2_F32 && dt_g == PN2_F32) return f(Ty<float>{}, Ty<float>{});
+    return -3;
+}
+// elements per 16-byte vector of a dtype code.  An unknown code counts as bf16 (8) ON PURPOSE: the entry points test alignment (-2) before they
+// dispatch on the dtype (-3), so this answer decides which of the two a call with a bad dtype and a misaligned shape gets
+inline int vec_of(int dt) { return dt == PN2_F32 ? 4 : 8; }
+inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+// rows per block of the "256 threads = cvp channel vectors x R row lanes, a lane walks rows" kernels: ~1024 blocks (4 per CU), a multiple of R, between
+// min_mult * R and (max_mult > 0) max_mult * R rows.  With scalar parameter loads every block paid a ~60-instruction prologue and 512 blocks was the
+// optimum; with the 16-byte parameter loads the step time is flat from 768 up (15.59 / 15.57 / 15.51 / 15.51 / 15.49 ms at 384 / 512 / 768 / 1024 / 2048)
+inline void rows_walk_geometry(int M, int CV, int min_mult, int max_mult, int& cvp, int& rows_per_blk, int& nblk) {
+    cvp = pow2ceil(CV); if (cvp > 256) cvp = 256;
+    const int R = 256 / cvp;
+    constexpr int target = 1024;         // workgroups of a streaming pass (swept 256 .. 2048: flat up to 512 per pass kind)
+    const int want = (M + target - 1) / target;
+    rows_per_blk = ((want + R - 1) / R) * R;
+    if (rows_per_blk < min_mult * R) rows_per_blk = min_mult * R;
+    if (max_mult > 0 && rows_per_blk > max_mult * R) rows_per_blk = max_mult * R;
+    nblk = (M + rows_per_blk - 1) / rows_per_blk;
+}
+// (pn2_tail.hip still has a grid_for of its own with this signature: the shared one lives in a namespace that the other files open)
+// arguments of a table-driven launch (pn2_*_multi): device job table, njobs + 1 prefix sums, counts
+inline bool table_ok(const void* jobs_dev, const int* block_start_dev, int njobs, int total_blocks) { return jobs_dev && block_start_dev && njobs >= 1 && total_blocks >= 1; }
+namespace pn2_host {
+// workgroups of a grid-stride kernel with 256 threads per element: ceil(total / 256) in [1, cap]
+inline int grid_for(size_t total, int cap) { size_t g = (total + 255) / 256; return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g)); }
 }

@@ -2287,9 +2287,8 @@ inline void pick_tiles(int M, int cout, bool f32, int& bm, int& bn) {
     if (blocks() < 160 && bn == 64 && cout > 32) bn = 32;
 }
 
-// compile-time tile handed to a with_tile / with_wgrad_tile visitor, and the storage type handed to a with_dtype visitor
+// compile-time tile handed to a with_tile / with_wgrad_tile visitor (the storage type of a dtype code: with_dtype, pn2_common.h)
 template <int BM_, int BN_, int WM_, int WN_> struct Tile { static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_; };
-template <typename T> struct Ty { using type = T; };
 // the built conv GEMM tiles (BM x BN, WM x WN waves): f(Tile) for (bm, bn), -2 for any other pair
 template <typename F>
 int with_tile(int bm, int bn, F f) {
@@ -2308,15 +2307,6 @@ int with_wgrad_tile(int bmc, F f) {
     if (bmc == 64) return f(Tile<64, 0, 2, 2>{});
     if (bmc == 32) return f(Tile<32, 0, 1, 4>{});
     return -2;
-}
-// storage type of a PN2_* dtype code: f(Ty<T>), -3 for an unknown code
-template <typename F>
-int with_dtype(int dtype, F f) {
-    if (dtype == PN2_BF16) return f(Ty<bf16_t>{});
-    if (dtype == PN2_F32) return f(Ty<float>{});
-    if (dtype == PN2_F32F) return f(Ty<f32f_t>{});
-    if (dtype == PN2_F32X3) return f(Ty<f32x3_t>{});
-    return -3;
 }
 
 template <typename T, int BMC, int WM, int WN>

@@ -16,18 +16,11 @@ namespace {
 
 template <typename T> __device__ __forceinline__ void ldv(const T* p, float* f) { TT<T>::unpack(*reinterpret_cast<const uint4*>(p), f); }
 template <typename T> __device__ __forceinline__ void stv(T* p, const float* f) { *reinterpret_cast<uint4*>(p) = TT<T>::pack(f); }
-inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-inline int grid_for(size_t total) { size_t g = (total + 255) / 256; return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g)); }
+using namespace pn2_host;
+constexpr int GRID_CAP = 16384;
 
-// rows (pixels) per block of the "thread owns a channel vector and walks pixels" kernels: ~1024 blocks, a multiple of R
-inline void walk_geometry(int M, int CV, int& cvp, int& pix, int& nblk) {
-    cvp = pow2ceil(CV); if (cvp > 256) cvp = 256;
-    const int R = 256 / cvp;
-    pix = (M + 1023) / 1024;
-    pix = ((pix + R - 1) / R) * R;
-    if (pix < 4 * R) pix = 4 * R;
-    nblk = (M + pix - 1) / pix;
-}
+// rows (pixels) per block of the "thread owns a channel vector and walks pixels" kernels: at least four rows per row lane, no upper bound
+inline void walk_geometry(int M, int CV, int& cvp, int& pix, int& nblk) { rows_walk_geometry(M, CV, 4, 0, cvp, pix, nblk); }
 
 // cross-row-lane sum of per-thread channel-vector accumulators a[V] -> dst[c] (block partial row), through LDS, fixed order
 template <int V>
@@ -858,173 +851,155 @@ __global__ __launch_bounds__(256) void mloss_bwd_k(ml_maps m, const long long* _
     }
 }
 
-}  // namespace
+// the built depth-wise walks (K x K window, VT channels per thread): f(Int<K>, Int<VT>) for a built pair, -2 for any other.  bf16 packs two channels
+// per register and has no VT = 1; fp32 has no VT = 8; wider windows take fewer channels per thread (registers)
+template <typename T, typename F>
+int with_dw_kernel(int K, int VT, F f) {
+    constexpr bool bf = sizeof(T) == 2;
+    if (K == 1 && VT == 8) { if constexpr (bf) return f(Int<1>{}, Int<8>{}); }
+    if (K == 1 && VT == 4) return f(Int<1>{}, Int<4>{});
+    if (K == 1 && VT == 2) return f(Int<1>{}, Int<2>{});
+    if (K == 1 && VT == 1) { if constexpr (!bf) return f(Int<1>{}, Int<1>{}); }
+    if (K == 3 && VT == 4) return f(Int<3>{}, Int<4>{});
+    if (K == 3 && VT == 2) return f(Int<3>{}, Int<2>{});
+    if (K == 3 && VT == 1) { if constexpr (!bf) return f(Int<3>{}, Int<1>{}); }
+    if (K == 5 && VT == 2) return f(Int<5>{}, Int<2>{});
+    if (K == 5 && VT == 1) { if constexpr (!bf) return f(Int<5>{}, Int<1>{}); }
+    return -2;
+}
 
-#define EM_DISPATCH(dt, BODY) \
-    if ((dt) == PN2_BF16) { typedef bf16_t T; BODY } else if ((dt) == PN2_F32) { typedef float T; BODY } else return -3;
-#define EM_K(K_, BODY) \
-    if ((K_) == 1) { constexpr int KK_ = 1; BODY } else if ((K_) == 3) { constexpr int KK_ = 3; BODY } else if ((K_) == 5) { constexpr int KK_ = 5; BODY } else return -2;
-
-extern "C" {
-
-// geometry of the K x K depth-wise walks.  kind 0: forward / data gradient, 1: weight gradient.  Channels per thread shrink with the window
-// (registers: K*K weights or accumulators per channel); blocks.x is capped near 1024 because it is also the number of partial rows.
-static int dwk_geometry(int dt, int kind, int N, int H, int W, int C, int K, int& VT, int& SEG, int& SPR, int& SPB, int& cvp, int& gx, int& gy) {
-    const int vmax = dt == PN2_F32 ? 4 : 8;
-    VT = K == 1 ? vmax : (K == 3 ? (kind ? 2 : 4) : 2);
-    if (VT > vmax) VT = vmax;
-    while (VT > 1 && C % VT) VT >>= 1;
-    if (VT * (dt == PN2_F32 ? 4 : 2) < 4) return -2;          // at least one 32-bit word per thread (bf16: even channel counts)
-    const int CV = C / VT;
+// geometry of the segment walks (depth-wise K x K and pair conv): a thread owns VT channels (outputs) and walks row segments of SEG pixels, SPR per image
+// row; a block = cvp channel groups x 256 / cvp lanes and takes SPB segments; grid (gx, gy).  gx is capped near 1024: it is also the number of partial rows
+struct SegWalk { int VT, SEG, SPR, SPB, cvp, gx, gy; };
+// CV: channel groups; lanes: the most of them that one block takes
+inline void seg_walk(int N, int H, int W, int CV, int lanes, SegWalk& g) {
     int target = 16;
     if ((long long)N * H * ((W + 15) / 16) * CV < 200000) target = 8;
-    SPR = (W + target - 1) / target; SEG = (W + SPR - 1) / SPR;
-    const int lanes = (dt == PN2_F32 ? 64 : 128) / VT;        // 256 contiguous bytes of one pixel per block
-    cvp = CV >= lanes ? lanes : pow2ceil(CV);
-    const int R = 256 / cvp, nseg = N * H * SPR;
-    gy = (CV + cvp - 1) / cvp;
-    int want = 2048 / gy; if (want < 1) want = 1; if (want > 1024) want = 1024;
-    SPB = (nseg + want - 1) / want;
-    SPB = ((SPB + R - 1) / R) * R;
-    gx = (nseg + SPB - 1) / SPB;
+    g.SPR = (W + target - 1) / target; g.SEG = (W + g.SPR - 1) / g.SPR;
+    g.cvp = CV >= lanes ? lanes : pow2ceil(CV);
+    const int R = 256 / g.cvp, nseg = N * H * g.SPR;
+    g.gy = (CV + g.cvp - 1) / g.cvp;
+    int want = 2048 / g.gy; if (want < 1) want = 1; if (want > 1024) want = 1024;
+    g.SPB = (nseg + want - 1) / want;
+    g.SPB = ((g.SPB + R - 1) / R) * R;
+    g.gx = (nseg + g.SPB - 1) / g.SPB;
+}
+// depth-wise K x K.  kind 0: forward / data gradient, 1: weight gradient.  Channels per thread shrink with the window (registers: K*K weights or
+// accumulators per channel); a block spans 256 contiguous bytes of one pixel
+inline int dwk_geometry(int dt, int kind, int N, int H, int W, int C, int K, SegWalk& g) {
+    const int vmax = vec_of(dt);
+    g.VT = K == 1 ? vmax : (K == 3 ? (kind ? 2 : 4) : 2);
+    if (g.VT > vmax) g.VT = vmax;
+    while (g.VT > 1 && C % g.VT) g.VT >>= 1;
+    if (g.VT * (dt == PN2_F32 ? 4 : 2) < 4) return -2;          // at least one 32-bit word per thread (bf16: even channel counts)
+    seg_walk(N, H, W, C / g.VT, (dt == PN2_F32 ? 64 : 128) / g.VT, g);
     return 0;
 }
+// pair conv: VT outputs per thread (one 16-byte vector of 2*VT inputs), 32 output groups per block
+inline int pc_geometry(int dt, int N, int H, int W, int F, SegWalk& g) {
+    g.VT = dt == PN2_F32 ? 2 : 4;
+    if (F % g.VT || N < 1 || H < 1 || W < 1) return -2;
+    seg_walk(N, H, W, F / g.VT, 32, g);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
 
 /* rows of the BatchNorm partial buffers of pn2_dwconv (wgrad = 0) / of the partial buffer of pn2_dwconv_wgrad (wgrad = 1) */
 int pn2_dwconv_blocks(int dt, int N, int H, int W, int C, int K, int wgrad) {
     if (N < 1 || H < 1 || W < 1 || (K != 1 && K != 3 && K != 5)) return -1;
-    int VT, SEG, SPR, SPB, cvp, gx, gy;
-    if (dwk_geometry(dt, wgrad ? 1 : 0, N, H, W, C, K, VT, SEG, SPR, SPB, cvp, gx, gy)) return -1;
-    return gx;
+    SegWalk g;
+    return dwk_geometry(dt, wgrad ? 1 : 0, N, H, W, C, K, g) ? -1 : g.gx;
 }
-
-#define EM_KV(K_, VT_, BODY) \
-    if ((K_) == 1 && (VT_) == 8) { constexpr int KK_ = 1, VV_ = 8; BODY } else if ((K_) == 1 && (VT_) == 4) { constexpr int KK_ = 1, VV_ = 4; BODY } \
-    else if ((K_) == 1 && (VT_) == 2) { constexpr int KK_ = 1, VV_ = 2; BODY } else if ((K_) == 3 && (VT_) == 4) { constexpr int KK_ = 3, VV_ = 4; BODY } \
-    else if ((K_) == 3 && (VT_) == 2) { constexpr int KK_ = 3, VV_ = 2; BODY } else if ((K_) == 5 && (VT_) == 2) { constexpr int KK_ = 5, VV_ = 2; BODY } \
-    else return -2;
-#define EM_KV32(K_, VT_, BODY) \
-    if ((K_) == 1 && (VT_) == 4) { constexpr int KK_ = 1, VV_ = 4; BODY } else if ((K_) == 1 && (VT_) == 2) { constexpr int KK_ = 1, VV_ = 2; BODY } \
-    else if ((K_) == 1 && (VT_) == 1) { constexpr int KK_ = 1, VV_ = 1; BODY } else if ((K_) == 3 && (VT_) == 4) { constexpr int KK_ = 3, VV_ = 4; BODY } \
-    else if ((K_) == 3 && (VT_) == 2) { constexpr int KK_ = 3, VV_ = 2; BODY } else if ((K_) == 3 && (VT_) == 1) { constexpr int KK_ = 3, VV_ = 1; BODY } \
-    else if ((K_) == 5 && (VT_) == 2) { constexpr int KK_ = 5, VV_ = 2; BODY } else if ((K_) == 5 && (VT_) == 1) { constexpr int KK_ = 5, VV_ = 1; BODY } \
-    else return -2;
 
 /* depth-wise K x K conv (K = 1, 3, 5), pad K/2, stride 1, no bias; flip = data gradient; psum/psq: BatchNorm partial rows
  * [pn2_dwconv_blocks(dt, N, H, W, C, K, 0)][C] */
 int pn2_dwconv(int dt, const void* x, const float* w, void* z, int N, int H, int W, int C, int K, int flip, int accumulate, float* psum, float* psq, void* stream) {
     if (!x || !w || !z || (psum && !psq)) return -1;
-    int VT, SEG, SPR, SPB, cvp, gx, gy;
-    if (dwk_geometry(dt, 0, N, H, W, C, K, VT, SEG, SPR, SPB, cvp, gx, gy)) return -2;
-    const dim3 grid(gx, gy);
-    const size_t lds = (size_t)256 * VT * 4;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) { EM_KV(K, VT, { hipLaunchKernelGGL((dwconv_row_k<bf16_t, KK_, VV_>), grid, dim3(256), lds, st, (const bf16_t*)x, w, (bf16_t*)z, N, H, W, C, flip, accumulate,
-                                                            psum, psq, SEG, SPR, SPB, cvp); }) }
-    else if (dt == PN2_F32) { EM_KV32(K, VT, { hipLaunchKernelGGL((dwconv_row_k<float, KK_, VV_>), grid, dim3(256), lds, st, (const float*)x, w, (float*)z, N, H, W, C, flip, accumulate,
-                                                                  psum, psq, SEG, SPR, SPB, cvp); }) }
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    SegWalk g;
+    if (dwk_geometry(dt, 0, N, H, W, C, K, g)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return with_dw_kernel<T>(K, g.VT, [&](auto k, auto vt) {
+            return pn2_launch<dwconv_row_k<T, decltype(k)::value, decltype(vt)::value>>(dim3(g.gx, g.gy), dim3(256), (size_t)256 * g.VT * 4, 0, (hipStream_t)stream, (const T*)x, w, (T*)z, N, H, W, C,
+                                                                                        flip, accumulate, psum, psq, g.SEG, g.SPR, g.SPB, g.cvp);
+        });
+    });
 }
 
 /* partial[pn2_dwconv_blocks(dt, N, H, W, C, K, 1)][C*K*K] of the depth-wise weight gradient; finish with pn2_colsum_finalize(partial, nblk, C*K*K, C*K*K, dW, acc) */
 int pn2_dwconv_wgrad(int dt, const void* dz, const void* x, float* partial, int N, int H, int W, int C, int K, void* stream) {
     if (!dz || !x || !partial) return -1;
-    int VT, SEG, SPR, SPB, cvp, gx, gy;
-    if (dwk_geometry(dt, 1, N, H, W, C, K, VT, SEG, SPR, SPB, cvp, gx, gy)) return -2;
-    const dim3 grid(gx, gy);
-    const size_t lds = (size_t)256 * VT * 4;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) { EM_KV(K, VT, { hipLaunchKernelGGL((dwconv_wgrad_row_k<bf16_t, KK_, VV_>), grid, dim3(256), lds, st, (const bf16_t*)dz, (const bf16_t*)x, partial,
-                                                            N, H, W, C, SEG, SPR, SPB, cvp); }) }
-    else if (dt == PN2_F32) { EM_KV32(K, VT, { hipLaunchKernelGGL((dwconv_wgrad_row_k<float, KK_, VV_>), grid, dim3(256), lds, st, (const float*)dz, (const float*)x, partial,
-                                                                  N, H, W, C, SEG, SPR, SPB, cvp); }) }
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
-}
-
-// geometry of the pair-conv walks: VT outputs per thread (one 16-byte vector of 2*VT inputs), segments as the depth-wise kernels
-static int pc_geometry(int dt, int N, int H, int W, int F, int& VT, int& SEG, int& SPR, int& SPB, int& cvp, int& gx, int& gy) {
-    VT = dt == PN2_F32 ? 2 : 4;
-    if (F % VT || N < 1 || H < 1 || W < 1) return -2;
-    const int FV = F / VT;
-    int target = 16;
-    if ((long long)N * H * ((W + 15) / 16) * FV < 200000) target = 8;
-    SPR = (W + target - 1) / target; SEG = (W + SPR - 1) / SPR;
-    cvp = FV >= 32 ? 32 : pow2ceil(FV);
-    const int R = 256 / cvp, nseg = N * H * SPR;
-    gy = (FV + cvp - 1) / cvp;
-    int want = 2048 / gy; if (want < 1) want = 1; if (want > 1024) want = 1024;
-    SPB = (nseg + want - 1) / want;
-    SPB = ((SPB + R - 1) / R) * R;
-    gx = (nseg + SPB - 1) / SPB;
-    return 0;
+    SegWalk g;
+    if (dwk_geometry(dt, 1, N, H, W, C, K, g)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return with_dw_kernel<T>(K, g.VT, [&](auto k, auto vt) {
+            return pn2_launch<dwconv_wgrad_row_k<T, decltype(k)::value, decltype(vt)::value>>(dim3(g.gx, g.gy), dim3(256), (size_t)256 * g.VT * 4, 0, (hipStream_t)stream, (const T*)dz, (const T*)x, partial,
+                                                                                              N, H, W, C, g.SEG, g.SPR, g.SPB, g.cvp);
+        });
+    });
 }
 
 /* rows of the BatchNorm partial buffers of pn2_pairconv3x3_fwd and of the partial buffer of pn2_pairconv3x3_wgrad */
 int pn2_pairconv_blocks(int dt, int N, int H, int W, int F) {
-    int VT, SEG, SPR, SPB, cvp, gx, gy;
-    if (pc_geometry(dt, N, H, W, F, VT, SEG, SPR, SPB, cvp, gx, gy)) return -1;
-    return gx;
+    SegWalk g;
+    return pc_geometry(dt, N, H, W, F, g) ? -1 : g.gx;
 }
 
 /* grouped 3x3 conv, groups = F, 2 input channels per group (LGAG.W_g / W_x), pad 1, bias-free here (the bias is folded by the caller):
  * x [M][2F] -> z [M][F] + BN partial rows [pn2_pairconv_blocks(dt, N, H, W, F)][F] ; w [F][2][9] fp32 */
 int pn2_pairconv3x3_fwd(int dt, const void* x, const float* w, void* z, int N, int H, int W, int F, float* psum, float* psq, void* stream) {
     if (!x || !w || !z || !psum || !psq) return -1;
-    int VT, SEG, SPR, SPB, cvp, gx, gy;
-    if (pc_geometry(dt, N, H, W, F, VT, SEG, SPR, SPB, cvp, gx, gy)) return -2;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((pairconv_fwd_k<bf16_t, 4>), dim3(gx, gy), dim3(256), 256 * 4 * 4, st, (const bf16_t*)x, w, (bf16_t*)z, N, H, W, F, psum, psq, SEG, SPR, SPB, cvp);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((pairconv_fwd_k<float, 2>), dim3(gx, gy), dim3(256), 256 * 2 * 4, st, (const float*)x, w, (float*)z, N, H, W, F, psum, psq, SEG, SPR, SPB, cvp);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    SegWalk g;
+    if (pc_geometry(dt, N, H, W, F, g)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        constexpr int VT = TT<T>::VEC / 2;
+        return pn2_launch<pairconv_fwd_k<T, VT>>(dim3(g.gx, g.gy), dim3(256), 256 * VT * 4, 0, (hipStream_t)stream, (const T*)x, w, (T*)z, N, H, W, F, psum, psq, g.SEG, g.SPR, g.SPB, g.cvp);
+    });
 }
 
 int pn2_pairconv3x3_dgrad(int dt, const void* dz, const float* w, void* dx, int N, int H, int W, int F, int accumulate, void* stream) {
     if (!dz || !w || !dx) return -1;
-    int VT, SEG, SPR, SPB, cvp, gx, gy;
-    if (pc_geometry(dt, N, H, W, F, VT, SEG, SPR, SPB, cvp, gx, gy)) return -2;
-    const int R = 256 / cvp, nseg = N * H * SPR;
-    const dim3 grid((nseg + R - 1) / R, gy);
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((pairconv_dgrad_k<bf16_t, 4>), grid, dim3(256), 0, st, (const bf16_t*)dz, w, (bf16_t*)dx, N, H, W, F, accumulate, SEG, SPR, cvp);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((pairconv_dgrad_k<float, 2>), grid, dim3(256), 0, st, (const float*)dz, w, (float*)dx, N, H, W, F, accumulate, SEG, SPR, cvp);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    SegWalk g;
+    if (pc_geometry(dt, N, H, W, F, g)) return -2;
+    const int R = 256 / g.cvp, nseg = N * H * g.SPR;          // one segment per lane: no partial rows to bound
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<pairconv_dgrad_k<T, TT<T>::VEC / 2>>(dim3((nseg + R - 1) / R, g.gy), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dz, w, (T*)dx, N, H, W, F, accumulate, g.SEG, g.SPR, g.cvp);
+    });
 }
 
 /* partial[pn2_pairconv_blocks(dt, N, H, W, F)][F*18] ; finish with pn2_colsum_finalize */
 int pn2_pairconv3x3_wgrad(int dt, const void* dz, const void* x, float* partial, int N, int H, int W, int F, void* stream) {
     if (!dz || !x || !partial) return -1;
-    int VT, SEG, SPR, SPB, cvp, gx, gy;
-    if (pc_geometry(dt, N, H, W, F, VT, SEG, SPR, SPB, cvp, gx, gy)) return -2;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((pairconv_wgrad_k<bf16_t, 4>), dim3(gx, gy), dim3(256), 256 * 4 * 4, st, (const bf16_t*)dz, (const bf16_t*)x, partial, N, H, W, F, SEG, SPR, SPB, cvp);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((pairconv_wgrad_k<float, 2>), dim3(gx, gy), dim3(256), 256 * 2 * 4, st, (const float*)dz, (const float*)x, partial, N, H, W, F, SEG, SPR, SPB, cvp);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    SegWalk g;
+    if (pc_geometry(dt, N, H, W, F, g)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        constexpr int VT = TT<T>::VEC / 2;
+        return pn2_launch<pairconv_wgrad_k<T, VT>>(dim3(g.gx, g.gy), dim3(256), 256 * VT * 4, 0, (hipStream_t)stream, (const T*)dz, (const T*)x, partial, N, H, W, F, g.SEG, g.SPR, g.SPB, g.cvp);
+    });
 }
 
 /* y (+)= x * gate ; mode 0: gate [N][C] (CAB), mode 1: gate [N][HW] (SAB, LGAG) ; gate fp32.  Also the data gradient (x := dy). */
 int pn2_gate_mul(int dt, const void* x, const float* gate, void* y, int N, int HW, int C, int mode, int accumulate, void* stream) {
     if (!x || !gate || !y) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (C % V) return -2;
-    EM_DISPATCH(dt, { hipLaunchKernelGGL(gate_mul_k<T>, dim3(grid_for((size_t)N * HW * (C / V))), dim3(256), 0, (hipStream_t)stream, (const T*)x, gate, (T*)y, N, HW, C, mode, accumulate); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<gate_mul_k<T>>(dim3(grid_for((size_t)N * HW * (C / V), GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, gate, (T*)y, N, HW, C, mode, accumulate);
+    });
 }
 
 /* gate gradient.  mode 1: dgate [N][HW] = sum_c dy*x, written directly.  mode 0: partial [pn2_gate_blocks(dt, HW, C)][N*C] rows, finish with
  * pn2_colsum_finalize(partial, nblk, N*C, N*C, dgate, acc) */
 int pn2_gate_blocks(int dt, int HW, int C) {
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (HW < 1 || C % V) return -1;
     int cvp, pix, nblk; walk_geometry(HW, C / V, cvp, pix, nblk);
     return nblk;
@@ -1032,91 +1007,99 @@ int pn2_gate_blocks(int dt, int HW, int C) {
 
 int pn2_gate_bwd(int dt, const void* dy, const void* x, float* dgate_or_partial, int N, int HW, int C, int mode, void* stream) {
     if (!dy || !x || !dgate_or_partial) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (C % V) return -2;
-    if (mode == 1) {
-        EM_DISPATCH(dt, { hipLaunchKernelGGL(gate_dpix_k<T>, dim3(grid_for((size_t)N * HW * 64)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)x, dgate_or_partial, (size_t)N * HW, C); })
-    } else {
+    hipStream_t st = (hipStream_t)stream;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        if (mode == 1) return pn2_launch<gate_dpix_k<T>>(dim3(grid_for((size_t)N * HW * 64, GRID_CAP)), dim3(256), 0, 0, st, (const T*)dy, (const T*)x, dgate_or_partial, (size_t)N * HW, C);
         int cvp, pix, nblk; walk_geometry(HW, C / V, cvp, pix, nblk);
-        EM_DISPATCH(dt, { hipLaunchKernelGGL(gate_dchan_k<T>, dim3(nblk, N), dim3(256), 256 * TT<T>::VEC * 4, (hipStream_t)stream, (const T*)dy, (const T*)x, dgate_or_partial, N, HW, C, pix, cvp); })
-    }
-    PN2_CHECK_LAUNCH();
-    return 0;
+        return pn2_launch<gate_dchan_k<T>>(dim3(nblk, N), dim3(256), 256 * TT<T>::VEC * 4, 0, st, (const T*)dy, (const T*)x, dgate_or_partial, N, HW, C, pix, cvp);
+    });
 }
 
 /* nn.AdaptiveAvgPool2d(1) and nn.AdaptiveMaxPool2d(1) in one pass (CAB): avg, mx [N][C] in the compute dtype, arg [N][C] = argmax pixel */
 int pn2_global_pool(int dt, const void* x, void* avg, void* mx, int* arg, int N, int HW, int C, void* stream) {
     if (!x || !avg || !mx || !arg) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (C % V) return -2;
-    EM_DISPATCH(dt, { hipLaunchKernelGGL(global_pool_k<T>, dim3((C / V + 7) / 8, N), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)avg, (T*)mx, arg, HW, C); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<global_pool_k<T>>(dim3((C / V + 7) / 8, N), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, (T*)avg, (T*)mx, arg, HW, C);
+    });
 }
 
 int pn2_global_pool_bwd(int dt, const void* davg, const void* dmax, const int* arg, void* dx, int N, int HW, int C, int accumulate, void* stream) {
     if (!davg || !dmax || !arg || !dx) return -1;
-    EM_DISPATCH(dt, { hipLaunchKernelGGL(global_pool_bwd_k<T>, dim3(grid_for((size_t)N * HW * C)), dim3(256), 0, (hipStream_t)stream, (const T*)davg, (const T*)dmax, arg, (T*)dx, N, HW, C, accumulate); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<global_pool_bwd_k<T>>(dim3(grid_for((size_t)N * HW * C, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)davg, (const T*)dmax, arg, (T*)dx, N, HW, C, accumulate);
+    });
 }
 
 /* SAB input: out [NP][8] = (mean over channels, max over channels, 0 x 6), arg [NP] = argmax channel */
 int pn2_chan_stats(int dt, const void* x, void* out8, int* arg, long long NP, int C, void* stream) {
     if (!x || !out8 || !arg) return -1;
-    EM_DISPATCH(dt, { hipLaunchKernelGGL(chan_stats_k<T>, dim3(grid_for((size_t)NP * 64)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)out8, arg, (size_t)NP, C); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<chan_stats_k<T>>(dim3(grid_for((size_t)NP * 64, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, (T*)out8, arg, (size_t)NP, C);
+    });
 }
 
 int pn2_chan_stats_bwd(int dt, const void* dout8, const int* arg, void* dx, long long NP, int C, int accumulate, void* stream) {
     if (!dout8 || !arg || !dx) return -1;
-    EM_DISPATCH(dt, { hipLaunchKernelGGL(chan_stats_bwd_k<T>, dim3(grid_for((size_t)NP * C)), dim3(256), 0, (hipStream_t)stream, (const T*)dout8, arg, (T*)dx, (size_t)NP, C, accumulate); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<chan_stats_bwd_k<T>>(dim3(grid_for((size_t)NP * C, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dout8, arg, (T*)dx, (size_t)NP, C, accumulate);
+    });
 }
 
 /* nn.Upsample(scale_factor=2) (nearest) and its adjoint */
 int pn2_upsample_nearest2x(int dt, const void* x, void* y, int N, int H, int W, int C, void* stream) {
     if (!x || !y) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (C % V) return -2;
-    EM_DISPATCH(dt, { hipLaunchKernelGGL(up2_k<T>, dim3(grid_for((size_t)N * 4 * H * W * (C / V))), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, N, H, W, C); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<up2_k<T>>(dim3(grid_for((size_t)N * 4 * H * W * (C / V), GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, (T*)y, N, H, W, C);
+    });
 }
 
 int pn2_upsample_nearest2x_bwd(int dt, const void* dy, void* dx, int N, int H, int W, int C, int accumulate, void* stream) {
     if (!dy || !dx) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (C % V) return -2;
-    EM_DISPATCH(dt, { hipLaunchKernelGGL(up2_bwd_k<T>, dim3(grid_for((size_t)N * H * W * (C / V))), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (T*)dx, N, H, W, C, accumulate); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<up2_bwd_k<T>>(dim3(grid_for((size_t)N * H * W * (C / V), GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dy, (T*)dx, N, H, W, C, accumulate);
+    });
 }
 
 /* y[p][c] = a[p][perm[c]] + b[p][perm[c]] + c[p][perm[c]]   (b, c optional): the MSDC branch sum written through channel_shuffle, and (with the
  * inverse permutation, b = c = null) its adjoint */
 int pn2_gather_sum(int dt, const void* a, const void* b, const void* c, const int* perm, void* y, long long M, int C, void* stream) {
     if (!a || !perm || !y) return -1;
-    EM_DISPATCH(dt, { hipLaunchKernelGGL(gather_sum_k<T>, dim3(grid_for((size_t)M * C)), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, (const T*)c, perm, (T*)y, (size_t)M, C); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<gather_sum_k<T>>(dim3(grid_for((size_t)M * C, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)a, (const T*)b, (const T*)c, perm, (T*)y, (size_t)M, C);
+    });
 }
 
 /* y = sigmoid(x) as fp32 [n] from a [rows][ld] map with C used channels; dx (+)= dy * y * (1 - y) */
 int pn2_sigmoid(int dt_in, const void* x, int ld, int C, float* y, long long n, void* stream) {
     if (!x || !y || n < 1) return -1;
-    EM_DISPATCH(dt_in, { hipLaunchKernelGGL(sigmoid_k<T>, dim3(grid_for((size_t)n)), dim3(256), 0, (hipStream_t)stream, (const T*)x, y, (size_t)n, ld, C); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt_in, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<sigmoid_k<T>>(dim3(grid_for((size_t)n, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, y, (size_t)n, ld, C);
+    });
 }
 
 int pn2_sigmoid_bwd(int dt_out, const float* dy, const float* y, void* dx, int ld, int C, long long n, int accumulate, void* stream) {
     if (!dy || !y || !dx || n < 1) return -1;
-    EM_DISPATCH(dt_out, { hipLaunchKernelGGL(sigmoid_bwd_k<T>, dim3(grid_for((size_t)n)), dim3(256), 0, (hipStream_t)stream, dy, y, (T*)dx, (size_t)n, ld, C, accumulate); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt_out, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<sigmoid_bwd_k<T>>(dim3(grid_for((size_t)n, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, dy, y, (T*)dx, (size_t)n, ld, C, accumulate);
+    });
 }
 
 static int ml_blocks(long long npix) { return (int)((npix + 255) / 256); }
@@ -1138,11 +1121,9 @@ int pn2_mutation_loss_fwd(const float* const* fg, const float* const* bg, const 
     const int ngrp = nblk < 8 * ML_RG ? (nblk + 7) / 8 : ML_RG;
     double* grp = reinterpret_cast<double*>(partial + (((size_t)nblk * NV + 1) & ~(size_t)1));          // 8-byte aligned, after the block rows
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mloss_fwd_k<9>, dim3(nblk), dim3(256), 0, st, m, label, bg_mask, NP, (size_t)HW, partial);
-    hipLaunchKernelGGL(mloss_reduce_k<9>, dim3(ngrp), dim3(256), 0, st, partial, nblk, grp);
-    hipLaunchKernelGGL(mloss_finalize_k<9>, dim3(1), dim3(256), 0, st, grp, ngrp, sums, loss, (double)NP, lc1, lc2, lc3);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<mloss_fwd_k<9>>(dim3(nblk), dim3(256), 0, 0, st, m, label, bg_mask, NP, (size_t)HW, partial)) return rc;
+    if (int rc = pn2_launch<mloss_reduce_k<9>>(dim3(ngrp), dim3(256), 0, 0, st, partial, nblk, grp)) return rc;
+    return pn2_launch<mloss_finalize_k<9>>(dim3(1), dim3(256), 0, 0, st, grp, ngrp, sums, loss, (double)NP, lc1, lc2, lc3);
 }
 
 int pn2_mutation_loss_bwd(const float* const* fg, const float* const* bg, float* const* dfg, float* const* dbg, const long long* label, const float* bg_mask,
@@ -1152,9 +1133,7 @@ int pn2_mutation_loss_bwd(const float* const* fg, const float* const* bg, float*
     ml_maps m;
     for (int i = 0; i < 4; ++i) { m.fg[i] = fg[i]; m.bg[i] = bg[i]; m.dfg[i] = dfg[i]; m.dbg[i] = dbg[i]; if (!fg[i] || !bg[i] || !dfg[i] || !dbg[i]) return -1; }
     const size_t NP = (size_t)N * HW;
-    hipLaunchKernelGGL(mloss_bwd_k<9>, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, label, bg_mask, NP, (size_t)HW, sums, gscale, lc1, lc2, lc3);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<mloss_bwd_k<9>>(dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, m, label, bg_mask, NP, (size_t)HW, sums, gscale, lc1, lc2, lc3);
 }
 
 }  // extern "C"

@@ -28,11 +28,12 @@ template <typename T, int W> struct VL {
     }
 };
 
-// The kernels index with 32 bits and step by gridDim.x * 256 <= 16384 * 256: the C entry points refuse (status -2) element counts within one step
-// of 2^32, where `idx += step` would wrap and the loop never end (PN2_TOO_MANY); grid_for keeps the impossible-grid backstop.
-constexpr size_t PIX_MAX = 0xFFFFFFFFull - 16384ull * 256ull;
-#define PN2_TOO_MANY(total) do { if ((size_t)(total) > PIX_MAX) return -2; } while (0)
-inline int grid_for(size_t total) { if (total > PIX_MAX) return -1; size_t g = (total + 255) / 256; return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g)); }
+// The kernels index with 32 bits and step by gridDim.x * 256 <= GRID_CAP * 256: the C entry points refuse (status -2) element counts within one step
+// of 2^32, where `idx += step` would wrap and the loop never end (too_many), before they size a grid.
+using namespace pn2_host;
+constexpr int GRID_CAP = 16384;
+constexpr size_t PIX_MAX = 0xFFFFFFFFull - (size_t)GRID_CAP * 256ull;
+inline bool too_many(size_t total) { return total > PIX_MAX; }
 
 // 32-bit element index (the C entry points refuse tensors of 2^32 or more vectors): the 64-bit `idx % CV`, `p % W`, `p / H` chains of a pixel decode were
 // ~100 instructions each - most of what these streaming kernels executed
@@ -455,11 +456,12 @@ template <typename T> bool vec_ok(int C, int a, int b = 0, int c = 0, int d = 0)
     constexpr int V = TT<T>::VEC;
     return C % V == 0 && a % V == 0 && b % V == 0 && c % V == 0 && d % V == 0;
 }
-
-#define DISPATCH_T(dt, CALL)                                     \
-    if ((dt) == PN2_BF16) { using T = bf16_t; CALL }             \
-    else if ((dt) == PN2_F32) { using T = float; CALL }          \
-    else return -3;
+// the two forms of an element-wise kernel over `total` elements: launch(Int<W>, grid) with W = the 16-byte vector of T when `vec`, else one element
+template <typename T, typename F>
+int vec_or_scalar(bool vec, size_t total, F launch) {
+    constexpr int V = TT<T>::VEC;
+    return vec ? launch(Int<V>{}, grid_for(total / V, GRID_CAP)) : launch(Int<1>{}, grid_for(total, GRID_CAP));
+}
 
 }  // namespace
 
@@ -467,161 +469,162 @@ extern "C" {
 
 int pn2_maxpool3x3s2_fwd(int dt, const void* x, int ld_x, void* y, int ld_y, unsigned char* idx, int N, int H, int W, int C, int OH, int OW, void* stream) {
     if (!x || !y || !idx) return -1;
-    PN2_TOO_MANY((size_t)N * OH * OW * C);
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dt, {
-        if (vec_ok<T>(C, ld_x, ld_y)) hipLaunchKernelGGL((maxpool_fwd_k<T, TT<T>::VEC>), dim3(grid_for((size_t)N * OH * OW * C / TT<T>::VEC)), dim3(256), 0, st, (const T*)x, ld_x, (T*)y, ld_y, idx, N, H, W, C, OH, OW);
-        else hipLaunchKernelGGL((maxpool_fwd_k<T, 1>), dim3(grid_for((size_t)N * OH * OW * C)), dim3(256), 0, st, (const T*)x, ld_x, (T*)y, ld_y, idx, N, H, W, C, OH, OW);
-    })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const size_t total = (size_t)N * OH * OW * C;
+    if (too_many(total)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return vec_or_scalar<T>(vec_ok<T>(C, ld_x, ld_y), total, [&](auto w, int grid) {
+            return pn2_launch<maxpool_fwd_k<T, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, ld_x, (T*)y, ld_y, idx, N, H, W, C, OH, OW);
+        });
+    });
 }
 
 int pn2_maxpool3x3s2_bwd(int dt, const void* dy, int ld_dy, const unsigned char* idx, void* dx, int ld_dx, int N, int H, int W, int C, int OH, int OW, void* stream) {
     if (!dy || !dx || !idx) return -1;
-    PN2_TOO_MANY((size_t)N * H * W * C);
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dt, {
-        if (vec_ok<T>(C, ld_dy, ld_dx)) hipLaunchKernelGGL((maxpool_bwd_k<T, TT<T>::VEC>), dim3(grid_for((size_t)N * H * W * C / TT<T>::VEC)), dim3(256), 0, st, (const T*)dy, ld_dy, idx, (T*)dx, ld_dx, N, H, W, C, OH, OW);
-        else hipLaunchKernelGGL((maxpool_bwd_k<T, 1>), dim3(grid_for((size_t)N * H * W * C)), dim3(256), 0, st, (const T*)dy, ld_dy, idx, (T*)dx, ld_dx, N, H, W, C, OH, OW);
-    })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const size_t total = (size_t)N * H * W * C;
+    if (too_many(total)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return vec_or_scalar<T>(vec_ok<T>(C, ld_dy, ld_dx), total, [&](auto w, int grid) {
+            return pn2_launch<maxpool_bwd_k<T, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dy, ld_dy, idx, (T*)dx, ld_dx, N, H, W, C, OH, OW);
+        });
+    });
 }
 
 int pn2_avgpool_fwd(int dt, const void* x, int ld_x, void* y, int ld_y, int N, int H, int W, int C, int OH, int OW, int k, int stride, int pad, int inc, void* stream) {
     if (!x || !y) return -1;
-    PN2_TOO_MANY((size_t)N * OH * OW * C);
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dt, {
-        if (vec_ok<T>(C, ld_x, ld_y)) hipLaunchKernelGGL((avgpool_fwd_k<T, TT<T>::VEC>), dim3(grid_for((size_t)N * OH * OW * C / TT<T>::VEC)), dim3(256), 0, st, (const T*)x, ld_x, (T*)y, ld_y, N, H, W, C, OH, OW, k, stride, pad, inc);
-        else hipLaunchKernelGGL((avgpool_fwd_k<T, 1>), dim3(grid_for((size_t)N * OH * OW * C)), dim3(256), 0, st, (const T*)x, ld_x, (T*)y, ld_y, N, H, W, C, OH, OW, k, stride, pad, inc);
-    })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const size_t total = (size_t)N * OH * OW * C;
+    if (too_many(total)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return vec_or_scalar<T>(vec_ok<T>(C, ld_x, ld_y), total, [&](auto w, int grid) {
+            return pn2_launch<avgpool_fwd_k<T, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, ld_x, (T*)y, ld_y, N, H, W, C, OH, OW, k, stride, pad, inc);
+        });
+    });
 }
 
 int pn2_avgpool_bwd(int dt, const void* dy, int ld_dy, void* dx, int ld_dx, int N, int H, int W, int C, int OH, int OW, int k, int stride, int pad, int inc, int accumulate, void* stream) {
     if (!dy || !dx) return -1;
-    PN2_TOO_MANY((size_t)N * H * W * C);
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dt, {
-        if (vec_ok<T>(C, ld_dy, ld_dx)) hipLaunchKernelGGL((avgpool_bwd_k<T, TT<T>::VEC>), dim3(grid_for((size_t)N * H * W * C / TT<T>::VEC)), dim3(256), 0, st, (const T*)dy, ld_dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, k, stride, pad, inc, accumulate);
-        else hipLaunchKernelGGL((avgpool_bwd_k<T, 1>), dim3(grid_for((size_t)N * H * W * C)), dim3(256), 0, st, (const T*)dy, ld_dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, k, stride, pad, inc, accumulate);
-    })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const size_t total = (size_t)N * H * W * C;
+    if (too_many(total)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return vec_or_scalar<T>(vec_ok<T>(C, ld_dy, ld_dx), total, [&](auto w, int grid) {
+            return pn2_launch<avgpool_bwd_k<T, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dy, ld_dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, k, stride, pad, inc, accumulate);
+        });
+    });
 }
 
 int pn2_bilinear_fwd(int dt, const void* x, int ld_x, void* y, int ld_y, int N, int H, int W, int C, int OH, int OW, int ac, float rh, float rw, void* stream) {
     if (!x || !y) return -1;
-    PN2_TOO_MANY((size_t)N * OH * OW * C);
+    const size_t total = (size_t)N * OH * OW * C;
+    if (too_many(total)) return -2;
     hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dt, {
-        if (vec_ok<T>(C, ld_x, ld_y)) hipLaunchKernelGGL((bilinear_fwd_k<T, TT<T>::VEC>), dim3(grid_for((size_t)N * OH * OW * C / TT<T>::VEC)), dim3(256), 0, st, (const T*)x, ld_x, (T*)y, ld_y, N, H, W, C, OH, OW, ac, rh, rw);
-        else if (sizeof(T) == 4 && C % 3 == 0 && ld_x % 3 == 0 && ld_y % 3 == 0)      // fp32 K = 9 class maps: 12-byte vectors
-            hipLaunchKernelGGL((bilinear_fwd_k<float, 3>), dim3(grid_for((size_t)N * OH * OW * C / 3)), dim3(256), 0, st, (const float*)x, ld_x, (float*)y, ld_y, N, H, W, C, OH, OW, ac, rh, rw);
-        else hipLaunchKernelGGL((bilinear_fwd_k<T, 1>), dim3(grid_for((size_t)N * OH * OW * C)), dim3(256), 0, st, (const T*)x, ld_x, (T*)y, ld_y, N, H, W, C, OH, OW, ac, rh, rw);
-    })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        const bool vec = vec_ok<T>(C, ld_x, ld_y);
+        if (!vec && sizeof(T) == 4 && C % 3 == 0 && ld_x % 3 == 0 && ld_y % 3 == 0)      // fp32 K = 9 class maps: 12-byte vectors
+            return pn2_launch<bilinear_fwd_k<float, 3>>(dim3(grid_for(total / 3, GRID_CAP)), dim3(256), 0, 0, st, (const float*)x, ld_x, (float*)y, ld_y, N, H, W, C, OH, OW, ac, rh, rw);
+        return vec_or_scalar<T>(vec, total, [&](auto w, int grid) {
+            return pn2_launch<bilinear_fwd_k<T, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, st, (const T*)x, ld_x, (T*)y, ld_y, N, H, W, C, OH, OW, ac, rh, rw);
+        });
+    });
 }
 
 int pn2_bilinear_bwd(int dt, const void* dy, int ld_dy, void* dx, int ld_dx, int N, int H, int W, int C, int OH, int OW, int ac, float rh, float rw, int accumulate, void* stream) {
     if (!dy || !dx) return -1;
-    PN2_TOO_MANY((size_t)N * H * W * C);
+    const size_t total = (size_t)N * H * W * C;
+    if (too_many(total)) return -2;
     hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dt, {
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
         if ((C < TT<T>::VEC || (sizeof(T) == 4 && C <= 16)) && OH >= 4 * H && OW >= 4 * W && ld_dy == C && OW * C <= 8192)      // K-channel fp32 maps (K = 1 .. 9)
-            hipLaunchKernelGGL((bilinear_bwd_rows_k<T>), dim3(N * H), dim3(256), OW * C * 4, st, (const T*)dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
-        else if (C < TT<T>::VEC && OH >= 4 * H && OW >= 4 * W)
-            hipLaunchKernelGGL((bilinear_bwd_wave_k<T>), dim3((unsigned)(((size_t)N * H * W * C + 3) / 4)), dim3(256), 0, st, (const T*)dy, ld_dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
-        else if (vec_ok<T>(C, ld_dy, ld_dx)) hipLaunchKernelGGL((bilinear_bwd_k<T, TT<T>::VEC>), dim3(grid_for((size_t)N * H * W * C / TT<T>::VEC)), dim3(256), 0, st, (const T*)dy, ld_dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
-        else if (sizeof(T) == 4 && C % 3 == 0 && ld_dy % 3 == 0 && ld_dx % 3 == 0)      // fp32 K = 9 class maps: 12-byte vectors
-            hipLaunchKernelGGL((bilinear_bwd_k<float, 3>), dim3(grid_for((size_t)N * H * W * C / 3)), dim3(256), 0, st, (const float*)dy, ld_dy, (float*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
-        else hipLaunchKernelGGL((bilinear_bwd_k<T, 1>), dim3(grid_for((size_t)N * H * W * C)), dim3(256), 0, st, (const T*)dy, ld_dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
-    })
-    PN2_CHECK_LAUNCH();
-    return 0;
+            return pn2_launch<bilinear_bwd_rows_k<T>>(dim3(N * H), dim3(256), OW * C * 4, 0, st, (const T*)dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
+        if (C < TT<T>::VEC && OH >= 4 * H && OW >= 4 * W)
+            return pn2_launch<bilinear_bwd_wave_k<T>>(dim3((unsigned)((total + 3) / 4)), dim3(256), 0, 0, st, (const T*)dy, ld_dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
+        const bool vec = vec_ok<T>(C, ld_dy, ld_dx);
+        if (!vec && sizeof(T) == 4 && C % 3 == 0 && ld_dy % 3 == 0 && ld_dx % 3 == 0)      // fp32 K = 9 class maps: 12-byte vectors
+            return pn2_launch<bilinear_bwd_k<float, 3>>(dim3(grid_for(total / 3, GRID_CAP)), dim3(256), 0, 0, st, (const float*)dy, ld_dy, (float*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
+        return vec_or_scalar<T>(vec, total, [&](auto w, int grid) {
+            return pn2_launch<bilinear_bwd_k<T, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, st, (const T*)dy, ld_dy, (T*)dx, ld_dx, N, H, W, C, OH, OW, ac, rh, rw, accumulate);
+        });
+    });
 }
 
 int pn2_binary(int dt, int op, const void* a, int ld_a, const void* b, int ld_b, void* out, int ld_out, int M, int C, int accumulate, void* stream) {
     if (!a || !b || !out) return -1;
-    PN2_TOO_MANY((size_t)M * C);
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dt, {
-        if (vec_ok<T>(C, ld_a, ld_b, ld_out)) hipLaunchKernelGGL((binary_k<T, TT<T>::VEC>), dim3(grid_for((size_t)M * C / TT<T>::VEC)), dim3(256), 0, st, op, (const T*)a, ld_a, (const T*)b, ld_b, (T*)out, ld_out, M, C, accumulate);
-        else hipLaunchKernelGGL((binary_k<T, 1>), dim3(grid_for((size_t)M * C)), dim3(256), 0, st, op, (const T*)a, ld_a, (const T*)b, ld_b, (T*)out, ld_out, M, C, accumulate);
-    })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const size_t total = (size_t)M * C;
+    if (too_many(total)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return vec_or_scalar<T>(vec_ok<T>(C, ld_a, ld_b, ld_out), total, [&](auto w, int grid) {
+            return pn2_launch<binary_k<T, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, op, (const T*)a, ld_a, (const T*)b, ld_b, (T*)out, ld_out, M, C, accumulate);
+        });
+    });
 }
 
+/* equal dtypes (vector rows where they align), or a conversion fp32 <-> bf16 (element-wise) */
 int pn2_copy(int dt_in, const void* src, int ld_s, int dt_out, void* dst, int ld_d, int M, int C, int accumulate, void* stream) {
     if (!src || !dst) return -1;
-    PN2_TOO_MANY((size_t)M * C);
+    const size_t total = (size_t)M * C;
+    if (too_many(total)) return -2;
     hipStream_t st = (hipStream_t)stream;
-    if (dt_in == dt_out) {
-        DISPATCH_T(dt_in, {
-            if (vec_ok<T>(C, ld_s, ld_d)) hipLaunchKernelGGL((copy_k<T, T, TT<T>::VEC>), dim3(grid_for((size_t)M * C / TT<T>::VEC)), dim3(256), 0, st, (const T*)src, ld_s, (T*)dst, ld_d, M, C, accumulate);
-            else hipLaunchKernelGGL((copy_k<T, T, 1>), dim3(grid_for((size_t)M * C)), dim3(256), 0, st, (const T*)src, ld_s, (T*)dst, ld_d, M, C, accumulate);
-        })
-    } else if (dt_in == PN2_F32 && dt_out == PN2_BF16)
-        hipLaunchKernelGGL((copy_k<float, bf16_t, 1>), dim3(grid_for((size_t)M * C)), dim3(256), 0, st, (const float*)src, ld_s, (bf16_t*)dst, ld_d, M, C, accumulate);
-    else if (dt_in == PN2_BF16 && dt_out == PN2_F32)
-        hipLaunchKernelGGL((copy_k<bf16_t, float, 1>), dim3(grid_for((size_t)M * C)), dim3(256), 0, st, (const bf16_t*)src, ld_s, (float*)dst, ld_d, M, C, accumulate);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    auto copy = [&](auto ti, auto to, auto w, int grid) {
+        using Ti = type_of<decltype(ti)>; using To = type_of<decltype(to)>;
+        return pn2_launch<copy_k<Ti, To, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, st, (const Ti*)src, ld_s, (To*)dst, ld_d, M, C, accumulate);
+    };
+    if (dt_in == dt_out) return with_storage_dtype(dt_in, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return vec_or_scalar<T>(vec_ok<T>(C, ld_s, ld_d), total, [&](auto w, int grid) { return copy(ty, ty, w, grid); });
+    });
+    if (dt_in == PN2_F32 && dt_out == PN2_BF16) return copy(Ty<float>{}, Ty<bf16_t>{}, Int<1>{}, grid_for(total, GRID_CAP));
+    if (dt_in == PN2_BF16 && dt_out == PN2_F32) return copy(Ty<bf16_t>{}, Ty<float>{}, Int<1>{}, grid_for(total, GRID_CAP));
+    return -3;
 }
 
 int pn2_mul_bwd(int dt, const void* g, int ld_g, const void* a, int ld_a, const void* b, int ld_b, void* ga, int ld_ga, int acc_a, void* gb, int ld_gb, int acc_b,
                 int M, int C, void* stream) {
     if (!g || !a || !b || !ga || !gb || ga == gb) return -1;
-    PN2_TOO_MANY((size_t)M * C);
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_T(dt, {
-        if (vec_ok<T>(C, ld_g, ld_a, ld_b) && vec_ok<T>(C, ld_ga, ld_gb))
-            hipLaunchKernelGGL((mul_bwd_k<T, TT<T>::VEC>), dim3(grid_for((size_t)M * C / TT<T>::VEC)), dim3(256), 0, st, (const T*)g, ld_g, (const T*)a, ld_a, (const T*)b, ld_b, (T*)ga, ld_ga, acc_a, (T*)gb, ld_gb, acc_b, M, C);
-        else hipLaunchKernelGGL((mul_bwd_k<T, 1>), dim3(grid_for((size_t)M * C)), dim3(256), 0, st, (const T*)g, ld_g, (const T*)a, ld_a, (const T*)b, ld_b, (T*)ga, ld_ga, acc_a, (T*)gb, ld_gb, acc_b, M, C);
-    })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const size_t total = (size_t)M * C;
+    if (too_many(total)) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return vec_or_scalar<T>(vec_ok<T>(C, ld_g, ld_a, ld_b) && vec_ok<T>(C, ld_ga, ld_gb), total, [&](auto w, int grid) {
+            return pn2_launch<mul_bwd_k<T, decltype(w)::value>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)g, ld_g, (const T*)a, ld_a, (const T*)b, ld_b,
+                                                                (T*)ga, ld_ga, acc_a, (T*)gb, ld_gb, acc_b, M, C);
+        });
+    });
 }
 
+/* table copy (pn2_copy_multi): vector rows only, four 16-byte vectors per thread, at most 4096 workgroups per job */
 int pn2_copy_job_blocks(int dt, const pn2_copy_job* j) {
     if (!j || !j->src || !j->dst || j->M < 1 || j->C < 1) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if ((dt != PN2_F32 && dt != PN2_BF16) || j->C % V || j->ld_s % V || j->ld_d % V) return -2;
     const size_t vecs = (size_t)j->M * (j->C / V);
-    const size_t nb = (vecs + 1023) / 1024;          // four 16-byte vectors per thread
+    const size_t nb = (vecs + 1023) / 1024;
     return (int)(nb > 4096 ? 4096 : nb);
 }
 int pn2_copy_multi(int dt, const pn2_copy_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    if (dt == PN2_BF16) hipLaunchKernelGGL(copy_tab_k<bf16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else if (dt == PN2_F32) hipLaunchKernelGGL(copy_tab_k<float>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
+    return with_storage_dtype(dt, [&](auto ty) {
+        return pn2_launch<copy_tab_k<type_of<decltype(ty)>>>(dim3(total_blocks), dim3(256), 0, 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
+    });
 }
 
 int pn2_nchw_to_nhwc(int dt_out, const float* x, void* y, int ld_y, int N, int C, int HW, int Cp, void* stream) {
     if (!x || !y) return -1;
-    PN2_TOO_MANY((size_t)N * HW);
-    hipStream_t st = (hipStream_t)stream;
-    if (dt_out == PN2_BF16) hipLaunchKernelGGL(nchw_to_nhwc_k<bf16_t>, dim3(grid_for((size_t)N * HW)), dim3(256), 0, st, x, (bf16_t*)y, ld_y, N, C, HW, Cp);
-    else if (dt_out == PN2_F32) hipLaunchKernelGGL(nchw_to_nhwc_k<float>, dim3(grid_for((size_t)N * HW)), dim3(256), 0, st, x, (float*)y, ld_y, N, C, HW, Cp);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const size_t total = (size_t)N * HW;
+    if (too_many(total)) return -2;
+    return with_storage_dtype(dt_out, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<nchw_to_nhwc_k<T>>(dim3(grid_for(total, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, x, (T*)y, ld_y, N, C, HW, Cp);
+    });
 }
 
 int pn2_bias_grad(const float* dy, int M, int K, float* db, int accumulate, void* stream) {
     if (!dy || !db) return -1;
-    hipLaunchKernelGGL(bias_grad_k, dim3(K), dim3(1024), 0, (hipStream_t)stream, dy, M, K, db, accumulate);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<bias_grad_k>(dim3(K), dim3(1024), 0, 0, (hipStream_t)stream, dy, M, K, db, accumulate);
 }
 
 }  // extern "C"

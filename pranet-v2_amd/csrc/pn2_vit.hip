@@ -1237,18 +1237,11 @@ __global__ __launch_bounds__(256) void scale_samples_k(const T* __restrict__ x, 
     }
 }
 
-inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-inline int grid_for(size_t total) { size_t g = (total + 255) / 256; return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g)); }
+using namespace pn2_host;
+constexpr int GRID_CAP = 16384;
 
-}  // namespace
-
-#define VIT_DISPATCH(dt, BODY) \
-    if ((dt) == PN2_BF16) { typedef bf16_t T; BODY } else if ((dt) == PN2_F32) { typedef float T; BODY } else return -3;
-
-extern "C" {
-
-static int ln_lpr(int dt, int C) {
-    const int V = dt == PN2_F32 ? 4 : 8;
+inline int ln_lpr(int dt, int C) {
+    const int V = vec_of(dt);
     if (C % V) return -1;
     int lpr = pow2ceil(C / V);
     if (lpr < 8) lpr = 8;
@@ -1256,103 +1249,32 @@ static int ln_lpr(int dt, int C) {
     return ((C / V + lpr - 1) / lpr <= LN_NV) ? lpr : -1;
 }
 
-int pn2_layernorm_fwd(int dt, const void* x, int ld_x, void* y, int ld_y, int M, int C, const float* gamma, const float* beta, float eps,
-                      float* mean, float* rstd, void* stream) {
-    if (!x || !y || !gamma || !beta || !mean || !rstd || M < 1) return -1;
-    const int lpr = ln_lpr(dt, C);
-    if (lpr < 0) return -2;
-    const int rows_per_blk = 4 * (64 / lpr);
-    VIT_DISPATCH(dt, { hipLaunchKernelGGL(ln_fwd_k<T>, dim3((M + rows_per_blk - 1) / rows_per_blk), dim3(256), 0, (hipStream_t)stream, (const T*)x, ld_x, (T*)y, ld_y, M, C,
-                                          gamma, beta, eps, mean, rstd, lpr); })
-    PN2_CHECK_LAUNCH();
-    return 0;
-}
-
-static int rows_for(int M, int unit) {          /* rows per block of the column-sum style reductions: ~ROWS_TARGET blocks, a multiple of `unit` */
+inline int rows_for(int M, int unit) {          /* rows per block of the column-sum style reductions: ~ROWS_TARGET blocks, a multiple of `unit` */
     constexpr int target = 512;   // 2 workgroups per CU measured best (256: -1.7 %, 1024: -1.1 % on config 4)
     int rows = (M + target - 1) / target;
     rows = ((rows + unit - 1) / unit) * unit;
     return rows < unit ? unit : rows;
 }
 
-int pn2_rows_blocks(int M, int unit) { if (M < 1 || unit < 1) return -1; const int rows = rows_for(M, unit); return (M + rows - 1) / rows; }
-
-int pn2_layernorm_bwd(int dt, const void* dy, int ld_dy, const void* x, int ld_x, int M, int C, const float* gamma, const float* mean, const float* rstd,
-                      void* dx, int ld_dx, int accumulate_dx, float* pg, float* pb, int nblk, void* stream) {
-    if (!dy || !x || !gamma || !mean || !rstd || !dx || !pg || !pb || M < 1 || nblk < 1) return -1;
-    const int lpr = ln_lpr(dt, C);
-    if (lpr < 0) return -2;
-    const int nslot = 4 * (64 / lpr);
-    const int rows = rows_for(M, nslot);
-    if ((M + rows - 1) / rows != nblk) return -2;          // nblk must be pn2_rows_blocks(M, pn2_ln_slots(dt, C))
-    const size_t lds = (size_t)2 * nslot * C * 4;
-    if (lds > 64 * 1024) return -2;
-    const bool nv1 = C / (dt == PN2_F32 ? 4 : 8) <= lpr;          // one channel vector per lane (C <= 512 bf16 / 256 fp32): the lean instantiation
-    VIT_DISPATCH(dt, { if (nv1) hipLaunchKernelGGL((ln_bwd_k<T, 1>), dim3(nblk), dim3(256), lds, (hipStream_t)stream, (const T*)dy, ld_dy, (const T*)x, ld_x, M, C, gamma, mean, rstd,
-                                          (T*)dx, ld_dx, accumulate_dx, pg, pb, rows, lpr);
-                       else hipLaunchKernelGGL((ln_bwd_k<T, LN_NV>), dim3(nblk), dim3(256), lds, (hipStream_t)stream, (const T*)dy, ld_dy, (const T*)x, ld_x, M, C, gamma, mean, rstd,
-                                          (T*)dx, ld_dx, accumulate_dx, pg, pb, rows, lpr); })
-    PN2_CHECK_LAUNCH();
-    return 0;
-}
-
-int pn2_ln_slots(int dt, int C) { const int lpr = ln_lpr(dt, C); return lpr < 0 ? -1 : 4 * (64 / lpr); }
-
-int pn2_colsum_finalize(const float* partial, int nblk, int C, int ld, float* out, int accumulate, void* stream) {
-    if (!partial || !out || nblk < 1 || C < 1) return -1;
-    hipLaunchKernelGGL(colsum_finalize_k, dim3((C + 31) / 32), dim3(256), 0, (hipStream_t)stream, partial, nblk, C, ld, out, accumulate);
-    PN2_CHECK_LAUNCH();
-    return 0;
-}
-
-int pn2_colsum_finalize_blocks(int C) { return C < 1 ? -1 : (C + 31) / 32; }
-
-int pn2_colsum_finalize_multi(const pn2_colsum_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    hipLaunchKernelGGL(colsum_finalize_multi_k, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
-}
-
-int pn2_colsum(int dt, const void* dy, int ld, int M, int C, float* partial, int nblk, void* stream) {
-    if (!dy || !partial || M < 1 || nblk < 1) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+// column sums of a [M][C] tensor: cvp channel vectors x 256 / cvp row lanes per block, `rows` rows per block.  pn2_colsum and pn2_colsum_job_blocks
+struct ColsumPlan { int cvp, rows, nblk; };
+inline int colsum_plan(int dt, int M, int C, int ld, ColsumPlan& p) {
+    const int V = vec_of(dt);
     if (C % V || ld % V) return -2;
-    int cvp = pow2ceil(C / V); if (cvp > 256) cvp = 256;
-    const int rows = rows_for(M, 256 / cvp);
-    if ((M + rows - 1) / rows != nblk) return -2;          // nblk must be pn2_rows_blocks(M, pn2_colsum_unit(dt, C))
-    VIT_DISPATCH(dt, { hipLaunchKernelGGL(colsum_k<T>, dim3(nblk), dim3(256), 256 * TT<T>::VEC * 4, (hipStream_t)stream, (const T*)dy, ld, M, C, partial, rows, cvp); })
-    PN2_CHECK_LAUNCH();
+    p.cvp = pow2ceil(C / V); if (p.cvp > 256) p.cvp = 256;
+    p.rows = rows_for(M, 256 / p.cvp);
+    p.nblk = (M + p.rows - 1) / p.rows;
     return 0;
 }
-
-/* fills rows / cvp of a job for pn2_colsum_multi and returns its workgroup count (= rows of its partial buffer, as pn2_rows_blocks gives) */
-int pn2_colsum_job_blocks(int dt, pn2_colsum_in_job* j) {
-    if (!j || !j->dy || !j->partial || j->M < 1) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
-    if (j->C % V || j->ld % V) return -2;
-    int cvp = pow2ceil(j->C / V); if (cvp > 256) cvp = 256;
-    j->cvp = cvp; j->rows = rows_for(j->M, 256 / cvp);
-    return (j->M + j->rows - 1) / j->rows;
-}
-
-int pn2_colsum_multi(int dt, const pn2_colsum_in_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
-    if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    VIT_DISPATCH(dt, { hipLaunchKernelGGL(colsum_multi_k<T>, dim3(total_blocks), dim3(256), 256 * TT<T>::VEC * 4, (hipStream_t)stream, jobs_dev, block_start_dev, njobs); })
-    PN2_CHECK_LAUNCH();
-    return 0;
-}
-
-int pn2_colsum_unit(int dt, int C) { const int V = dt == PN2_F32 ? 4 : 8; int cvp = pow2ceil(C / V); if (cvp > 256) cvp = 256; return 256 / cvp; }
 
 // channels per thread (VT) and segment length of the depth-wise walks, from a sweep on MI355X (tools/dw_micro.py):
 // kind 0 = conv + GELU (ALU-heavier: 8-byte vectors, more waves), 1 = plain conv / data gradient (16-byte vectors while there are threads to
 // spare), 2 = weight gradient (80 accumulators per 8 channels: 2 channels per thread keeps 8 waves per SIMD).  Short segments for small tensors.
 // PN2_DW_WIN=0: the round-3 walks (dwconv3x3_row_k / dwconv3x3_wgrad_row_k) instead of the window kernels (A/B; bf16 only - fp32 always takes them)
-static int dw_win() { static const int v = [] { const char* e = getenv("PN2_DW_WIN"); return e ? atoi(e) : 1; }(); return v; }
+inline int dw_win() { static const int v = [] { const char* e = getenv("PN2_DW_WIN"); return e ? atoi(e) : 1; }(); return v; }
 
-static void dw_row_geometry(int dt, int kind, int N, int H, int W, int C, int& VT, int& SEG, int& SPR) {
-    const int vmax = dt == PN2_F32 ? 4 : 8;
+inline void dw_row_geometry(int dt, int kind, int N, int H, int W, int C, int& VT, int& SEG, int& SPR) {
+    const int vmax = vec_of(dt);
     auto threads = [&](int vt, int target) { return (long long)N * H * ((W + target - 1) / target) * (C / vt); };
     // window kernels: a segment costs ~150 instructions and two memory latencies before its first output (weights, the first five columns); 32-pixel segments
     // where the tensor still gives 4 resident waves per SIMD twice over (stage 1 of PVTv2-B2 at 352^2: 117 -> 108 us conv + GELU, 71 -> 62 us data gradient)
@@ -1368,111 +1290,207 @@ static void dw_row_geometry(int dt, int kind, int N, int H, int W, int C, int& V
     SPR = (W + target - 1) / target; SEG = (W + SPR - 1) / SPR;
 }
 
-#define DW_VT(VT, BODY) switch (VT) { case 8: { constexpr int VT_ = 8; BODY } break; case 4: { constexpr int VT_ = 4; BODY } break; default: { constexpr int VT_ = 2; BODY } }
+// the bf16 window kernels (dwconv3x3_win_k / dwconv3x3_wgrad_win_k) address the tensor with 32-bit byte offsets
+inline bool dw_use_win(int dt, int N, int H, int W, int C) { return dt == PN2_BF16 && dw_win() && (long long)N * H * W * C * 2 < 0x7fff0000LL; }
 
-static int dwconv3x3_impl(int dt, const void* x, const float* w, const float* b, void* z, void* y_gelu, int N, int H, int W, int C, int flip, int accumulate, float* cpart, int cblk,
-                          void* stream) {
-    if (!x || !w || !z) return -1;
-    if (C % 2 || (dt == PN2_BF16 && C % 2) || N < 1 || H < 1 || W < 1) return -2;
-    int VT, SEG, SPR; dw_row_geometry(dt, y_gelu ? 0 : 1, N, H, W, C, VT, SEG, SPR);
-    const int CV = C / VT, lanes = (dt == PN2_F32 ? 256 : 512) / VT;     // channel groups per block: 1 KB of one pixel
-    const int cvp = CV >= lanes ? lanes : pow2ceil(CV), R = 256 / cvp, nseg = N * H * SPR;
-    const int walign = ((uintptr_t)w & 15) == 0;
-    const dim3 grid((nseg + R - 1) / R, (CV + cvp - 1) / cvp);
-    if (dt == PN2_BF16 && dw_win() && !accumulate && (long long)N * H * W * C * 2 < 0x7fff0000LL) {          // the window walk (4 or 2 channels per thread)
-        const int vt = C % 4 == 0 ? 4 : 2, cv4 = C / vt, ln = 512 / vt;
-        const int cvp4 = cv4 >= ln ? ln : pow2ceil(cv4), R4 = 256 / cvp4;
-        const dim3 g4((nseg + R4 - 1) / R4, (cv4 + cvp4 - 1) / cvp4);
-#define PN2_DW_WIN(VT_, G_, CS_) hipLaunchKernelGGL((dwconv3x3_win_k<VT_, G_, CS_>), g4, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, w, b, (bf16_t*)z, (bf16_t*)y_gelu, N, H, W, C, flip, SEG, SPR, cvp4, walign, cpart)
-        if (cblk == -1) return (int)g4.x;          // (pn2_dwconv3x3_colsum_blocks: rows of cpart)
-        if (cpart) {
-            if (y_gelu || cblk != (int)g4.x) return -2;
-            if (vt == 4) PN2_DW_WIN(4, false, true); else PN2_DW_WIN(2, false, true);
-        } else if (vt == 4) { if (y_gelu) PN2_DW_WIN(4, true, false); else PN2_DW_WIN(4, false, false); }
-        else { if (y_gelu) PN2_DW_WIN(2, true, false); else PN2_DW_WIN(2, false, false); }
-#undef PN2_DW_WIN
-        PN2_CHECK_LAUNCH();
-        return 0;
-    }
-    if (cpart || cblk == -1) return -2;          // column sums only ride on the window kernels
-    if (dt == PN2_BF16) { DW_VT(VT, { hipLaunchKernelGGL((dwconv3x3_row_k<bf16_t, VT_>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, w, b, (bf16_t*)z, (bf16_t*)y_gelu,
-                                                      N, H, W, C, flip, accumulate, SEG, SPR, cvp, walign); }) }
-    else if (dt == PN2_F32) {
-        if (VT == 4) hipLaunchKernelGGL((dwconv3x3_row_k<float, 4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, w, b, (float*)z, (float*)y_gelu, N, H, W, C, flip, accumulate, SEG, SPR, cvp, walign);
-        else hipLaunchKernelGGL((dwconv3x3_row_k<float, 2>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, w, b, (float*)z, (float*)y_gelu, N, H, W, C, flip, accumulate, SEG, SPR, cvp, walign);
-    } else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+// the built row walks dwconv3x3_row_k / dwconv3x3_wgrad_row_k: VT = 8 (bf16 only), 4, and 2 for everything else
+template <typename T, typename F>
+int with_dw_vt(int VT, F f) {
+    if constexpr (sizeof(T) == 2) { if (VT == 8) return f(Int<8>{}); }
+    return VT == 4 ? f(Int<4>{}) : f(Int<2>{});
 }
 
+// launch plan of pn2_dwconv3x3 / pn2_dwconv3x3_colsum: one lane per row segment; a block spans 1 KB of one pixel
+struct DwPlan { bool win; int VT, SEG, SPR, cvp; dim3 grid; };
+inline DwPlan dw_plan(int dt, bool gelu, bool accumulate, int N, int H, int W, int C) {
+    DwPlan p;
+    dw_row_geometry(dt, gelu ? 0 : 1, N, H, W, C, p.VT, p.SEG, p.SPR);
+    p.win = !accumulate && dw_use_win(dt, N, H, W, C);
+    if (p.win) p.VT = C % 4 == 0 ? 4 : 2;          // the window walk: 4 or 2 channels per thread
+    const int CV = C / p.VT, lanes = (dt == PN2_F32 ? 256 : 512) / p.VT;
+    p.cvp = CV >= lanes ? lanes : pow2ceil(CV);
+    const int R = 256 / p.cvp, nseg = N * H * p.SPR;
+    p.grid = dim3((nseg + R - 1) / R, (CV + p.cvp - 1) / p.cvp);
+    return p;
+}
+
+int dwconv3x3_launch(int dt, const void* x, const float* w, const float* b, void* z, void* y_gelu, int N, int H, int W, int C, int flip, int accumulate, float* cpart, int cblk,
+                     hipStream_t st) {
+    if (!x || !w || !z) return -1;
+    if (C % 2 || N < 1 || H < 1 || W < 1) return -2;
+    const DwPlan p = dw_plan(dt, y_gelu != nullptr, accumulate != 0, N, H, W, C);
+    const int walign = ((uintptr_t)w & 15) == 0;
+    if (p.win) {
+        if (cpart && (y_gelu || cblk != (int)p.grid.x)) return -2;
+        auto win = [&](auto vt, auto gelu, auto cs) {
+            return pn2_launch<dwconv3x3_win_k<decltype(vt)::value, decltype(gelu)::value, decltype(cs)::value>>(p.grid, dim3(256), 0, 0, st, (const bf16_t*)x, w, b, (bf16_t*)z, (bf16_t*)y_gelu,
+                                                                                                                 N, H, W, C, flip, p.SEG, p.SPR, p.cvp, walign, cpart);
+        };
+        auto win_vt = [&](auto vt) { return cpart ? win(vt, Bool<false>{}, Bool<true>{}) : (y_gelu ? win(vt, Bool<true>{}, Bool<false>{}) : win(vt, Bool<false>{}, Bool<false>{})); };
+        return p.VT == 4 ? win_vt(Int<4>{}) : win_vt(Int<2>{});
+    }
+    if (cpart) return -2;          // column sums only ride on the window kernels
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return with_dw_vt<T>(p.VT, [&](auto vt) {
+            return pn2_launch<dwconv3x3_row_k<T, decltype(vt)::value>>(p.grid, dim3(256), 0, 0, st, (const T*)x, w, b, (T*)z, (T*)y_gelu, N, H, W, C, flip, accumulate, p.SEG, p.SPR, p.cvp, walign);
+        });
+    });
+}
+
+// launch plan of pn2_dwconv3x3_wgrad: a block spans 256 contiguous bytes of one pixel and takes SPC segments; ~1536 workgroups over (chunks x channel groups)
+struct DwWgradPlan { bool win; int VT, SEG, SPR, SPC, cvp, nchunk, gy; };
+inline DwWgradPlan dw_wgrad_plan(int dt, int N, int H, int W, int C) {
+    DwWgradPlan p;
+    dw_row_geometry(dt, 2, N, H, W, C, p.VT, p.SEG, p.SPR);
+    p.win = dw_use_win(dt, N, H, W, C);
+    if (p.win) p.VT = C % 4 == 0 ? 4 : 2;          // window kernel: 4 channels per thread (20 packed accumulators)
+    const int CV = C / p.VT, lanes = (dt == PN2_F32 ? 32 : 64) / p.VT * 2;
+    p.cvp = CV >= lanes ? lanes : pow2ceil(CV);
+    const int R = 256 / p.cvp, nseg = N * H * p.SPR;
+    p.gy = (CV + p.cvp - 1) / p.cvp;
+    int want = 1536 / p.gy; if (want < 1) want = 1;
+    p.SPC = (nseg + want - 1) / want;
+    p.SPC = ((p.SPC + R - 1) / R) * R;
+    p.nchunk = (nseg + p.SPC - 1) / p.SPC;
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pn2_layernorm_fwd(int dt, const void* x, int ld_x, void* y, int ld_y, int M, int C, const float* gamma, const float* beta, float eps,
+                      float* mean, float* rstd, void* stream) {
+    if (!x || !y || !gamma || !beta || !mean || !rstd || M < 1) return -1;
+    const int lpr = ln_lpr(dt, C);
+    if (lpr < 0) return -2;
+    const int rows_per_blk = 4 * (64 / lpr);
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<ln_fwd_k<T>>(dim3((M + rows_per_blk - 1) / rows_per_blk), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, ld_x, (T*)y, ld_y, M, C, gamma, beta, eps, mean, rstd, lpr);
+    });
+}
+
+int pn2_rows_blocks(int M, int unit) { if (M < 1 || unit < 1) return -1; const int rows = rows_for(M, unit); return (M + rows - 1) / rows; }
+
+int pn2_layernorm_bwd(int dt, const void* dy, int ld_dy, const void* x, int ld_x, int M, int C, const float* gamma, const float* mean, const float* rstd,
+                      void* dx, int ld_dx, int accumulate_dx, float* pg, float* pb, int nblk, void* stream) {
+    if (!dy || !x || !gamma || !mean || !rstd || !dx || !pg || !pb || M < 1 || nblk < 1) return -1;
+    const int lpr = ln_lpr(dt, C);
+    if (lpr < 0) return -2;
+    const int nslot = 4 * (64 / lpr);
+    const int rows = rows_for(M, nslot);
+    if ((M + rows - 1) / rows != nblk) return -2;          // nblk must be pn2_rows_blocks(M, pn2_ln_slots(dt, C))
+    const size_t lds = (size_t)2 * nslot * C * 4;
+    if (lds > 64 * 1024) return -2;
+    const bool nv1 = C / vec_of(dt) <= lpr;          // one channel vector per lane (C <= 512 bf16 / 256 fp32): the lean instantiation
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        auto launch = [&](auto nv) {
+            return pn2_launch<ln_bwd_k<T, decltype(nv)::value>>(dim3(nblk), dim3(256), lds, 0, (hipStream_t)stream, (const T*)dy, ld_dy, (const T*)x, ld_x, M, C, gamma, mean, rstd,
+                                                                (T*)dx, ld_dx, accumulate_dx, pg, pb, rows, lpr);
+        };
+        return nv1 ? launch(Int<1>{}) : launch(Int<LN_NV>{});
+    });
+}
+
+int pn2_ln_slots(int dt, int C) { const int lpr = ln_lpr(dt, C); return lpr < 0 ? -1 : 4 * (64 / lpr); }
+
+int pn2_colsum_finalize(const float* partial, int nblk, int C, int ld, float* out, int accumulate, void* stream) {
+    if (!partial || !out || nblk < 1 || C < 1) return -1;
+    return pn2_launch<colsum_finalize_k>(dim3((C + 31) / 32), dim3(256), 0, 0, (hipStream_t)stream, partial, nblk, C, ld, out, accumulate);
+}
+
+int pn2_colsum_finalize_blocks(int C) { return C < 1 ? -1 : (C + 31) / 32; }
+
+int pn2_colsum_finalize_multi(const pn2_colsum_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
+    return pn2_launch<colsum_finalize_multi_k>(dim3(total_blocks), dim3(256), 0, 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
+}
+
+int pn2_colsum(int dt, const void* dy, int ld, int M, int C, float* partial, int nblk, void* stream) {
+    if (!dy || !partial || M < 1 || nblk < 1) return -1;
+    ColsumPlan p;
+    if (int rc = colsum_plan(dt, M, C, ld, p)) return rc;
+    if (p.nblk != nblk) return -2;          // nblk must be pn2_rows_blocks(M, pn2_colsum_unit(dt, C))
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<colsum_k<T>>(dim3(nblk), dim3(256), 256 * TT<T>::VEC * 4, 0, (hipStream_t)stream, (const T*)dy, ld, M, C, partial, p.rows, p.cvp);
+    });
+}
+
+/* fills rows / cvp of a job for pn2_colsum_multi and returns its workgroup count (= rows of its partial buffer, as pn2_rows_blocks gives) */
+int pn2_colsum_job_blocks(int dt, pn2_colsum_in_job* j) {
+    if (!j || !j->dy || !j->partial || j->M < 1) return -1;
+    ColsumPlan p;
+    if (int rc = colsum_plan(dt, j->M, j->C, j->ld, p)) return rc;
+    j->cvp = p.cvp; j->rows = p.rows;
+    return p.nblk;
+}
+
+int pn2_colsum_multi(int dt, const pn2_colsum_in_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
+    if (!table_ok(jobs_dev, block_start_dev, njobs, total_blocks)) return -1;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<colsum_multi_k<T>>(dim3(total_blocks), dim3(256), 256 * TT<T>::VEC * 4, 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
+    });
+}
+
+int pn2_colsum_unit(int dt, int C) { int cvp = pow2ceil(C / vec_of(dt)); if (cvp > 256) cvp = 256; return 256 / cvp; }
+
 int pn2_dwconv3x3(int dt, const void* x, const float* w, const float* b, void* z, void* y_gelu, int N, int H, int W, int C, int flip, int accumulate, void* stream) {
-    return dwconv3x3_impl(dt, x, w, b, z, y_gelu, N, H, W, C, flip, accumulate, nullptr, 0, stream);
+    return dwconv3x3_launch(dt, x, w, b, z, y_gelu, N, H, W, C, flip, accumulate, nullptr, 0, (hipStream_t)stream);
 }
 /* rows of `cpart` for pn2_dwconv3x3_colsum at this geometry (< 0: that entry does not serve it - run pn2_dwconv3x3 and a column-sum pass) */
 int pn2_dwconv3x3_colsum_blocks(int dt, int N, int H, int W, int C) {
     if (dt != PN2_BF16 || C % 2 || N < 1 || H < 1 || W < 1) return -1;
-    static const float dummy = 0.f;
-    const int r = dwconv3x3_impl(dt, &dummy, &dummy, nullptr, (void*)&dummy, nullptr, N, H, W, C, 0, 0, nullptr, -1, nullptr);
-    return r > 0 ? r : -1;
+    const DwPlan p = dw_plan(dt, false, false, N, H, W, C);
+    return p.win && p.grid.x > 0 ? (int)p.grid.x : -1;
 }
 /* pn2_dwconv3x3 (no GELU, no accumulate) that also leaves cpart[nblk][C]: per-workgroup column sums of the stored result */
 int pn2_dwconv3x3_colsum(int dt, const void* x, const float* w, const float* b, void* z, int N, int H, int W, int C, int flip, float* cpart, int nblk, void* stream) {
     if (!cpart || nblk < 1) return -1;
-    return dwconv3x3_impl(dt, x, w, b, z, nullptr, N, H, W, C, flip, 0, cpart, nblk, stream);
+    return dwconv3x3_launch(dt, x, w, b, z, nullptr, N, H, W, C, flip, 0, cpart, nblk, (hipStream_t)stream);
 }
 
 int pn2_gelu_bwd(int dt, const void* dy, const void* z, void* dz, long long n, void* stream) {
     if (!dy || !z || !dz) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (n % V) return -2;
-    VIT_DISPATCH(dt, { hipLaunchKernelGGL(gelu_bwd_k<T>, dim3(grid_for((size_t)n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)z, (T*)dz, (size_t)n / V); })
-    PN2_CHECK_LAUNCH();
-    return 0;
-}
-
-static void dw_wgrad_geometry(int dt, int N, int H, int W, int C, int& VT, int& SEG, int& SPR, int& SPC, int& cvp, int& nchunk) {
-    dw_row_geometry(dt, 2, N, H, W, C, VT, SEG, SPR);
-    const bool win = dt == PN2_BF16 && dw_win() && (long long)N * H * W * C * 2 < 0x7fff0000LL;
-    if (win) VT = C % 4 == 0 ? 4 : 2;          // window kernel: 4 channels per thread (20 packed accumulators), still 256 contiguous bytes of a pixel per block
-    const int CV = C / VT, lanes = (dt == PN2_F32 ? 32 : 64) / VT * 2;          // 256 contiguous bytes of one pixel per block
-    cvp = CV >= lanes ? lanes : pow2ceil(CV);
-    const int R = 256 / cvp, gy = (CV + cvp - 1) / cvp, nseg = N * H * SPR;
-    int want = 1536 / gy; if (want < 1) want = 1;            // ~1536 workgroups over (chunks x channel groups)
-    SPC = (nseg + want - 1) / want;
-    SPC = ((SPC + R - 1) / R) * R;
-    nchunk = (nseg + SPC - 1) / SPC;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<gelu_bwd_k<T>>(dim3(grid_for((size_t)n / V, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dy, (const T*)z, (T*)dz, (size_t)n / V);
+    });
 }
 
 int pn2_dwconv3x3_wgrad_blocks(int dt, int N, int H, int W, int C) {
     if ((dt != PN2_F32 && dt != PN2_BF16) || C % 2 || N < 1 || H < 1 || W < 1) return -1;
-    int VT, SEG, SPR, SPC, cvp, nchunk; dw_wgrad_geometry(dt, N, H, W, C, VT, SEG, SPR, SPC, cvp, nchunk);
-    return nchunk;
+    return dw_wgrad_plan(dt, N, H, W, C).nchunk;
 }
 
 int pn2_dwconv3x3_wgrad(int dt, const void* dz, const void* x, float* partial, int nblk, int N, int H, int W, int C, const void* zpre, void* dz_out, void* stream) {
     if (!dz || !x || !partial || nblk < 1 || (zpre && !dz_out)) return -1;
     if (C % 2) return -2;
-    int VT, SEG, SPR, SPC, cvp, nchunk; dw_wgrad_geometry(dt, N, H, W, C, VT, SEG, SPR, SPC, cvp, nchunk);
-    if (nchunk != nblk) return -2;                           // nblk must be pn2_dwconv3x3_wgrad_blocks(dt, N, H, W, C)
-    const int CV = C / VT;
-    const dim3 grid(nchunk, (CV + cvp - 1) / cvp);
-    const size_t lds = (size_t)256 * VT * 4;
-    if (dt == PN2_BF16 && dw_win() && (long long)N * H * W * C * 2 < 0x7fff0000LL) {
-#define PN2_DW_WG(VT_, Z_) hipLaunchKernelGGL((dwconv3x3_wgrad_win_k<VT_, Z_>), grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dz, (const bf16_t*)x, partial, N, H, W, C, SEG, SPR, SPC, cvp, (const bf16_t*)zpre, (bf16_t*)dz_out)
-        if (VT == 4) { if (zpre) PN2_DW_WG(4, true); else PN2_DW_WG(4, false); }
-        else { if (zpre) PN2_DW_WG(2, true); else PN2_DW_WG(2, false); }
-#undef PN2_DW_WG
-        PN2_CHECK_LAUNCH();
-        return 0;
+    const DwWgradPlan p = dw_wgrad_plan(dt, N, H, W, C);
+    if (p.nchunk != nblk) return -2;                           // nblk must be pn2_dwconv3x3_wgrad_blocks(dt, N, H, W, C)
+    const dim3 grid(p.nchunk, p.gy);
+    const size_t lds = (size_t)256 * p.VT * 4;
+    hipStream_t st = (hipStream_t)stream;
+    if (p.win) {
+        auto win = [&](auto vt, auto z) {
+            return pn2_launch<dwconv3x3_wgrad_win_k<decltype(vt)::value, decltype(z)::value>>(grid, dim3(256), lds, 0, st, (const bf16_t*)dz, (const bf16_t*)x, partial, N, H, W, C, p.SEG, p.SPR, p.SPC, p.cvp,
+                                                                                               (const bf16_t*)zpre, (bf16_t*)dz_out);
+        };
+        auto win_vt = [&](auto vt) { return zpre ? win(vt, Bool<true>{}) : win(vt, Bool<false>{}); };
+        return p.VT == 4 ? win_vt(Int<4>{}) : win_vt(Int<2>{});
     }
-    if (dt == PN2_BF16) { DW_VT(VT, { hipLaunchKernelGGL((dwconv3x3_wgrad_row_k<bf16_t, VT_>), grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dz, (const bf16_t*)x, partial,
-                                                      N, H, W, C, SEG, SPR, SPC, cvp, (const bf16_t*)zpre, (bf16_t*)dz_out); }) }
-    else if (dt == PN2_F32) {
-        if (VT == 4) hipLaunchKernelGGL((dwconv3x3_wgrad_row_k<float, 4>), grid, dim3(256), lds, (hipStream_t)stream, (const float*)dz, (const float*)x, partial, N, H, W, C, SEG, SPR, SPC, cvp, (const float*)zpre, (float*)dz_out);
-        else hipLaunchKernelGGL((dwconv3x3_wgrad_row_k<float, 2>), grid, dim3(256), lds, (hipStream_t)stream, (const float*)dz, (const float*)x, partial, N, H, W, C, SEG, SPR, SPC, cvp, (const float*)zpre, (float*)dz_out);
-    } else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return with_dw_vt<T>(p.VT, [&](auto vt) {
+            return pn2_launch<dwconv3x3_wgrad_row_k<T, decltype(vt)::value>>(grid, dim3(256), lds, 0, st, (const T*)dz, (const T*)x, partial, N, H, W, C, p.SEG, p.SPR, p.SPC, p.cvp, (const T*)zpre, (T*)dz_out);
+        });
+    });
 }
 
 static int attn_geom(int Nkv, int heads, int head_dim) { return ((head_dim == 32 || head_dim == 64) && Nkv >= 1 && Nkv <= 64 * AT_MAXK && heads >= 1) ? 0 : -2; }
@@ -1507,7 +1525,7 @@ static int attn_fwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld
         if (NK == 1) PN2_ATTN_FWD_M(1) else if (NK == 2) PN2_ATTN_FWD_M(2) else PN2_ATTN_FWD_M(4)
 #undef PN2_ATTN_FWD_M
     }
-    VIT_DISPATCH(dt, { if (NK == 1) PN2_ATTN_FWD(1) else if (NK == 2) PN2_ATTN_FWD(2) else if (NK == 3) PN2_ATTN_FWD(3) else PN2_ATTN_FWD(4) })
+    return with_storage_dtype(dt, [&](auto ty) { using T = type_of<decltype(ty)>; if (NK == 1) PN2_ATTN_FWD(1) else if (NK == 2) PN2_ATTN_FWD(2) else if (NK == 3) PN2_ATTN_FWD(3) else PN2_ATTN_FWD(4) });
 #undef PN2_ATTN_FWD
 }
 
@@ -1548,14 +1566,14 @@ static int attn_bwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld
     const dim3 grid(nqb, heads, B);
 #define PN2_ATTN_BWD(NKV, QBV) rc = pn2_launch<attn_bwd_k<T, NKV, QBV, HD>>(grid, dim3(256), lds, (int)lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (const T*)dout, ld_do, lse, (T*)dq, ld_dq, \
                                                                           partial, Nq, Nkv, heads, scale);
-    int rc;
-    VIT_DISPATCH(dt, {
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        int rc;
         if (NK == 1) PN2_ATTN_BWD(1, AT_QB) else if (NK == 2) PN2_ATTN_BWD(2, AT_QB) else if (NK == 3) PN2_ATTN_BWD(3, AT_QB) else PN2_ATTN_BWD(4, 2)
         if (rc) return rc;
-        hipLaunchKernelGGL((attn_bwd_kv_reduce_k<T, HD>), dim3(Nkv, heads, B), dim3(HD), 0, st, partial, (T*)dkv, ld_dkv, Nkv, NP, heads, nqb); })
+        return pn2_launch<attn_bwd_kv_reduce_k<T, HD>>(dim3(Nkv, heads, B), dim3(HD), 0, 0, st, partial, (T*)dkv, ld_dkv, Nkv, NP, heads, nqb);
+    });
 #undef PN2_ATTN_BWD
-    PN2_CHECK_LAUNCH();
-    return 0;
 }
 
 extern "C" {
@@ -1583,12 +1601,13 @@ int pn2_attn_bwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, con
 
 int pn2_scale_samples(int dt, const void* x, void* y, const float* scale, const void* res, int N, long long per_sample, void* stream) {
     if (!x || !y || !scale || N < 1) return -1;
-    const int V = dt == PN2_F32 ? 4 : 8;
+    const int V = vec_of(dt);
     if (per_sample % V) return -2;
-    VIT_DISPATCH(dt, { hipLaunchKernelGGL(scale_samples_k<T>, dim3(grid_for((size_t)N * per_sample / V)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, scale, (const T*)res,
-                                          (size_t)per_sample / V, (size_t)N * per_sample / V); })
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<scale_samples_k<T>>(dim3(grid_for((size_t)N * per_sample / V, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, (T*)y, scale, (const T*)res,
+                                              (size_t)per_sample / V, (size_t)N * per_sample / V);
+    });
 }
 
 }  // extern "C"
