@@ -476,6 +476,20 @@ int pn2_mutation_loss_fwd(const float* const* fg, const float* const* bg, const 
 int pn2_mutation_loss_bwd(const float* const* fg, const float* const* bg, float* const* dfg, float* const* dbg, const long long* label, const float* bg_mask,
                           int N, long long HW, int K, float lc1, float lc2, float lc3, const float* sums, float gscale, void* stream);
 
+/* EMCAD/trainer.py:141-153 (single supervision, EMCADNet with dual=False) with utils/utils.py:102-138 (DiceLoss, softmax=True): sum over the SELECTED
+ * non-empty subsets s of the 4 maps of   w_ce * CrossEntropy(sum_{i in s} P_i, label) + w_dice * DiceLoss(softmax(sum_{i in s} P_i), label).
+ * subsets: 15-bit mask, bit s-1 selects subset s, bit i of s means map i is in the sum - trainer.py:114-119: 'mutation' 0x7FFF (powerset),
+ * 'deep_supervision' 0x008B ([[0],[1],[2],[3]]), the fallback [[-1]] (last map only) 0x0080.  An unselected subset contributes exactly 0.
+ * maps[4] (host array of device pointers): [N][H][W][K] fp32, 2 <= K <= 9; label [N][H][W] int64.
+ * partial [pn2_mutation_loss_blocks(N*HW)][pn2_seg_loss_width(K)] scratch; sums [width] kept for the backward; loss[1].
+ * Backward: dmaps[i] = gscale * d loss / d maps[i], same layout (written, not accumulated; exact zeros for a map in no selected subset).
+ * pn2_seg_loss_width: -1 outside 2 <= K <= 9.  -2: subsets == 0, bits above 15, K outside 2..9 (nothing is launched). */
+int pn2_seg_loss_width(int K);
+int pn2_seg_loss_fwd(const float* const* maps, unsigned subsets, const long long* label, int N, long long HW, int K,
+                     float w_ce, float w_dice, float* partial, float* sums, float* loss, void* stream);
+int pn2_seg_loss_bwd(const float* const* maps, float* const* dmaps, unsigned subsets, const long long* label, int N, long long HW, int K,
+                     float w_ce, float w_dice, const float* sums, float gscale, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- element-wise / layout */
 int pn2_binary(int dt, int op /*0 add,1 mul*/, const void* a, int ld_a, const void* b, int ld_b, void* out, int ld_out, int M, int C, int accumulate, void* stream);
 /* backward of out = a * b in one pass (autograd of the aggregation's products x2_1 = conv_upsample1(up(x1)) * x2 ..., pranet.py:111-119): ga (+)= g * b, gb (+)= g * a -

@@ -851,6 +851,189 @@ __global__ __launch_bounds__(256) void mloss_bwd_k(ml_maps m, const long long* _
     }
 }
 
+// ------------------------------------------------------------------------------------------ single-supervision CE + Dice loss (EMCADNet, dual=False)
+// EMCAD/trainer.py:141-153 with utils/utils.py:102-138 (DiceLoss, softmax=True):
+//   loss = sum over the SELECTED non-empty subsets s of the 4 maps of  w_ce * CE(sum_{i in s} P_i, label) + w_dice * Dice(softmax(sum P_i), onehot(label))
+// `subsets` is a 15-bit mask, bit s-1 selects subset s (bit i of s: map i is in the sum): 0x7FFF 'mutation', 0x008B 'deep_supervision', 0x0080 the last map.
+// The foreground half of mloss_*_k as kernels of their own (the dual kernels keep their code and registers), K = 2..9 classes.  The subset loop is rolled:
+// `s` and the mask live in scalar registers, an unselected subset is one scalar branch - no transcendentals, nothing added to any sum or gradient.
+// A map's logits enter a subset sum through a select, not a multiply by 0: a map outside every selected subset cannot leak a NaN / inf into the loss.
+template <int K> struct SLW { static constexpr int W = 1 + 2 * K, NV = ML_NS * W + K; };      // values per subset: CE, I[K], Z[K]; then the label histogram T[K]
+
+struct sl_maps { const float* m[4]; float* d[4]; };
+
+template <int K>
+__global__ __launch_bounds__(256) void sloss_fwd_k(sl_maps m, unsigned subsets, const long long* __restrict__ label, size_t NP, float* __restrict__ partial) {
+    constexpr int W = SLW<K>::W, NV = SLW<K>::NV;
+    __shared__ float red[16][NV];          // the 16 DPP-row partials of the block (see mloss_fwd_k)
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, rrow = wid * 4 + (lane >> 4);
+    const bool rlead = (lane & 15) == 0;
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = p < NP;
+    float f[4][K];
+    int lab = -1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < K; ++k) f[i][k] = 0.f;
+    if (ok) {
+        lab = (int)label[p];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int k = 0; k < K; ++k) f[i][k] = m.m[i][p * K + k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {          // label histogram (sum of target^2 per class), once
+        const float t = row16_sum((ok && lab == k) ? 1.f : 0.f);
+        if (rlead) red[rrow][ML_NS * W + k] = t;
+    }
+#pragma unroll 1
+    for (int s = 1; s <= ML_NS; ++s) {
+        if (!(subsets >> (s - 1) & 1)) continue;
+        const bool b0 = s & 1, b1 = s & 2, b2 = s & 4, b3 = s & 8;
+        float z[K], v[W];
+#pragma unroll
+        for (int k = 0; k < K; ++k) z[k] = (((b0 ? f[0][k] : 0.f) + (b1 ? f[1][k] : 0.f)) + (b2 ? f[2][k] : 0.f)) + (b3 ? f[3][k] : 0.f);
+        float mx = z[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
+        float se = 0.f, e[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) { e[k] = __expf(z[k] - mx); se += e[k]; }
+        const float inv = __builtin_amdgcn_rcpf(se), lse = mx + __logf(se);
+        float ce = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float pk = e[k] * inv;
+            if (lab == k) ce = lse - z[k];
+            v[1 + k] = (lab == k) ? pk : 0.f;
+            v[1 + K + k] = pk * pk;
+        }
+        v[0] = ce;
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[j] = row16_sum(ok ? v[j] : 0.f);
+        if (rlead) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) red[rrow][(s - 1) * W + j] = v[j];
+        }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < NV; j += 256) {
+        const int s0 = j / W;          // == ML_NS for the histogram columns
+        float t = 0.f;
+        if (s0 >= ML_NS || (subsets >> s0 & 1)) {          // an unselected subset's columns were never written: exact zeros
+#pragma unroll
+            for (int i = 0; i < 16; ++i) t += red[i][j];
+        }
+        partial[(size_t)blockIdx.x * NV + j] = t;
+    }
+}
+
+// partial rows -> group rows in double, as mloss_reduce_k (row width at run time: not hot)
+__global__ __launch_bounds__(256) void sloss_reduce_k(const float* __restrict__ partial, int nblk, int NV, double* __restrict__ grp) {
+    const int rb = (nblk + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * rb, r1 = min(nblk, r0 + rb);
+    for (int j = threadIdx.x; j < NV; j += 256) {
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        int r = r0;
+        for (; r + 3 < r1; r += 4) {
+            a0 += (double)partial[(size_t)r * NV + j]; a1 += (double)partial[(size_t)(r + 1) * NV + j];
+            a2 += (double)partial[(size_t)(r + 2) * NV + j]; a3 += (double)partial[(size_t)(r + 3) * NV + j];
+        }
+        for (; r < r1; ++r) a0 += (double)partial[(size_t)r * NV + j];
+        grp[(size_t)blockIdx.x * NV + j] = (a0 + a1) + (a2 + a3);
+    }
+}
+
+// sums[15 * (1 + 2K) + K] (double-accumulated over the group rows) and the scalar loss over the selected subsets
+__global__ void sloss_finalize_k(const double* __restrict__ grp, int ngrp, int K, unsigned subsets, float* __restrict__ sums, float* __restrict__ loss, double npix,
+                                 float w_ce, float w_dice) {
+    const int W = 1 + 2 * K, NV = ML_NS * W + K;
+    __shared__ double sh[SLW<9>::NV];
+    for (int j = threadIdx.x; j < NV; j += blockDim.x) {
+        double a = 0.0;
+        for (int r = 0; r < ngrp; ++r) a += grp[(size_t)r * NV + j];
+        sh[j] = a; sums[j] = (float)a;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int s = 0; s < ML_NS; ++s) {
+            if (!(subsets >> s & 1)) continue;
+            double dice = 0.0;
+            for (int k = 0; k < K; ++k) dice += 1.0 - (2.0 * sh[s * W + 1 + k] + 1e-5) / (sh[s * W + 1 + K + k] + sh[ML_NS * W + k] + 1e-5);
+            tot += w_ce * (sh[s * W] / npix) + w_dice * dice / K;
+        }
+        loss[0] = (float)tot;
+    }
+}
+
+// gradients of the four maps (recomputed softmaxes, Dice coefficients once per block in LDS - see mloss_bwd_k); a map in no selected subset gets exact zeros, written
+template <int K>
+__global__ __launch_bounds__(256) void sloss_bwd_k(sl_maps m, unsigned subsets, const long long* __restrict__ label, size_t NP, const float* __restrict__ sums,
+                                                   float gscale, float w_ce, float w_dice) {
+    constexpr int W = SLW<K>::W;
+    __shared__ float tA[ML_NS * K], tB[ML_NS * K];
+    const float wdice = gscale * w_dice / K;
+    for (int j = threadIdx.x; j < ML_NS * K; j += 256) {
+        const int s0 = j / K, k = j - s0 * K;
+        const float* S = sums + s0 * W;
+        // d dice_k / d p_k = -(2 t / D - (2 I + eps) 2 p / D^2),  D = Z + T + eps
+        const float D = S[1 + K + k] + sums[ML_NS * W + k] + 1e-5f;
+        tA[j] = wdice * 2.f / D; tB[j] = wdice * (2.f * S[1 + k] + 1e-5f) * 2.f / (D * D);
+    }
+    __syncthreads();
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= NP) return;
+    const int lab = (int)label[p];
+    const float wce = gscale * w_ce / (float)NP;
+    float f[4][K], gf[4][K];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < K; ++k) { f[i][k] = m.m[i][p * K + k]; gf[i][k] = 0.f; }
+#pragma unroll 1
+    for (int s = 1; s <= ML_NS; ++s) {
+        if (!(subsets >> (s - 1) & 1)) continue;
+        const bool b0 = s & 1, b1 = s & 2, b2 = s & 4, b3 = s & 8;
+        float z[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) z[k] = (((b0 ? f[0][k] : 0.f) + (b1 ? f[1][k] : 0.f)) + (b2 ? f[2][k] : 0.f)) + (b3 ? f[3][k] : 0.f);
+        float mx = z[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
+        float se = 0.f, pr[K], g[K], dot = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) { pr[k] = __expf(z[k] - mx); se += pr[k]; }
+        const float inv = __builtin_amdgcn_rcpf(se);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            pr[k] *= inv;
+            g[k] = -((lab == k ? tA[(s - 1) * K + k] : 0.f) - tB[(s - 1) * K + k] * pr[k]);
+            dot += g[k] * pr[k];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float dz = wce * (pr[k] - (lab == k ? 1.f : 0.f)) + pr[k] * (g[k] - dot);
+            gf[0][k] += b0 ? dz : 0.f; gf[1][k] += b1 ? dz : 0.f; gf[2][k] += b2 ? dz : 0.f; gf[3][k] += b3 ? dz : 0.f;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < K; ++k) m.d[i][p * K + k] = gf[i][k];
+}
+
+// the built class counts of the single-supervision loss: f(Int<K>) for 2 <= K <= 9, -2 for any other
+template <typename F>
+int with_seg_classes(int K, F f) {
+    switch (K) {
+        case 2: return f(Int<2>{}); case 3: return f(Int<3>{}); case 4: return f(Int<4>{}); case 5: return f(Int<5>{});
+        case 6: return f(Int<6>{}); case 7: return f(Int<7>{}); case 8: return f(Int<8>{}); case 9: return f(Int<9>{});
+    }
+    return -2;
+}
+
 // the built depth-wise walks (K x K window, VT channels per thread): f(Int<K>, Int<VT>) for a built pair, -2 for any other.  bf16 packs two channels
 // per register and has no VT = 1; fp32 has no VT = 8; wider windows take fewer channels per thread (registers)
 template <typename T, typename F>
@@ -1134,6 +1317,43 @@ int pn2_mutation_loss_bwd(const float* const* fg, const float* const* bg, float*
     for (int i = 0; i < 4; ++i) { m.fg[i] = fg[i]; m.bg[i] = bg[i]; m.dfg[i] = dfg[i]; m.dbg[i] = dbg[i]; if (!fg[i] || !bg[i] || !dfg[i] || !dbg[i]) return -1; }
     const size_t NP = (size_t)N * HW;
     return pn2_launch<mloss_bwd_k<9>>(dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, m, label, bg_mask, NP, (size_t)HW, sums, gscale, lc1, lc2, lc3);
+}
+
+int pn2_seg_loss_width(int K) { return K >= 2 && K <= 9 ? ML_NS * (1 + 2 * K) + K : -1; }
+
+static bool seg_loss_args_ok(unsigned subsets, int N, long long HW, int K) { return subsets != 0 && subsets <= 0x7FFFu && K >= 2 && K <= 9 && N >= 1 && HW >= 1; }
+
+/* EMCAD/trainer.py:141-153 (single supervision): sum over the subsets selected by `subsets` of w_ce*CE + w_dice*Dice(softmax) on the summed maps.
+ * maps[4]: [N][H][W][K] fp32 (2 <= K <= 9); label [N][H][W] int64.  partial: [pn2_mutation_loss_blocks][pn2_seg_loss_width] scratch; sums
+ * [pn2_seg_loss_width] is kept for the backward; loss[1]. */
+int pn2_seg_loss_fwd(const float* const* maps, unsigned subsets, const long long* label, int N, long long HW, int K, float w_ce, float w_dice,
+                     float* partial, float* sums, float* loss, void* stream) {
+    if (!maps || !label || !partial || !sums || !loss) return -1;
+    if (!seg_loss_args_ok(subsets, N, HW, K)) return -2;
+    sl_maps m;
+    for (int i = 0; i < 4; ++i) { m.m[i] = maps[i]; m.d[i] = nullptr; if (!maps[i]) return -1; }
+    const size_t NP = (size_t)N * HW;
+    const int nblk = ml_blocks((long long)NP), NV = pn2_seg_loss_width(K);
+    const int ngrp = nblk < 8 * ML_RG ? (nblk + 7) / 8 : ML_RG;
+    double* grp = reinterpret_cast<double*>(partial + (((size_t)nblk * NV + 1) & ~(size_t)1));          // 8-byte aligned, after the block rows
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = with_seg_classes(K, [&](auto k) {
+            return pn2_launch<sloss_fwd_k<decltype(k)::value>>(dim3(nblk), dim3(256), 0, 0, st, m, subsets, label, NP, partial); })) return rc;
+    if (int rc = pn2_launch<sloss_reduce_k>(dim3(ngrp), dim3(256), 0, 0, st, partial, nblk, NV, grp)) return rc;
+    return pn2_launch<sloss_finalize_k>(dim3(1), dim3(256), 0, 0, st, grp, ngrp, K, subsets, sums, loss, (double)NP, w_ce, w_dice);
+}
+
+int pn2_seg_loss_bwd(const float* const* maps, float* const* dmaps, unsigned subsets, const long long* label, int N, long long HW, int K, float w_ce, float w_dice,
+                     const float* sums, float gscale, void* stream) {
+    if (!maps || !dmaps || !label || !sums) return -1;
+    if (!seg_loss_args_ok(subsets, N, HW, K)) return -2;
+    sl_maps m;
+    for (int i = 0; i < 4; ++i) { m.m[i] = maps[i]; m.d[i] = dmaps[i]; if (!maps[i] || !dmaps[i]) return -1; }
+    const size_t NP = (size_t)N * HW;
+    return with_seg_classes(K, [&](auto k) {
+        return pn2_launch<sloss_bwd_k<decltype(k)::value>>(dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, m, subsets, label, NP, sums,
+                                                           gscale, w_ce, w_dice);
+    });
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-"""EMCAD decoder with dual-supervised K-class heads (reference: multiclass_seg/EMCAD/lib/decoders.py) on the gfx950 kernels.
+"""EMCAD decoder, plain and with dual-supervised K-class heads (reference: multiclass_seg/EMCAD/lib/decoders.py) on the gfx950 kernels.
 
 Same class names, constructor signatures and parameter names (state_dict keys) as the reference; the computation is expressed in
 engine ops (pn2/engine.py + ops_*.py): 1x1 / 3x3 / 7x7 convs on the implicit-GEMM kernels, BatchNorm on pn2_bn_*, and the depth-wise, grouped,
@@ -189,12 +189,11 @@ class SAB(nn.Module):
         return eng.sigmoid_gate(x, pre, 1)
 
 
-class EMCAD_dual(nn.Module):
-    """EMCAD decoder with the dual-supervised reverse-attention heads (:407-526)."""
+class _EMCADStages(nn.Module):
+    """What EMCAD and EMCAD_dual share: the MSCAM stages (CAB, SAB, MSCB), the EUCB up-convolutions and the LGAG gates, registered in the reference's order
+    (decoders.py:334-353 = :411-430), and the steps of their forward passes."""
 
-    def __init__(self, channels=[512, 320, 128, 64], kernel_sizes=[1, 3, 5], expansion_factor=6, dw_parallel=True, add=True, lgag_ks=3, activation='relu6', num_class=None):
-        super().__init__()
-        assert num_class is not None
+    def _register_stages(self, channels, kernel_sizes, expansion_factor, dw_parallel, add, lgag_ks, activation):
         eucb_ks = 3
         mk = lambda c: MSCBLayer(c, c, n=1, stride=1, kernel_sizes=kernel_sizes, expansion_factor=expansion_factor, dw_parallel=dw_parallel, add=add, activation=activation)
         self.mscb4 = mk(channels[0])
@@ -205,15 +204,47 @@ class EMCAD_dual(nn.Module):
         for i, lvl in enumerate((4, 3, 2, 1)):
             setattr(self, f"cab{lvl}", CAB(channels[i]))
         self.sab = SAB()
+
+    def _stage(self, eng, d, lvl):
+        """MSCAM: channel gate, spatial gate, multi-scale convolution block"""
+        d = getattr(self, f"cab{lvl}")._build_gated(eng, d)
+        d = self.sab._build_gated(eng, d)
+        return getattr(self, f"mscb{lvl}")[0]._build(eng, d)
+
+    def _gated_stage(self, eng, d, lvl, skip):
+        """additive aggregation of the up-convolved map with its LGAG-gated skip, then the MSCAM stage"""
+        d = eng.add(d, getattr(self, f"lgag{lvl}")._build(eng, d, skip))
+        return self._stage(eng, d, lvl)
+
+
+class EMCAD(_EMCADStages):
+    """EMCAD decoder (:330-405): the four stage outputs; EMCADNet puts its out_head convs on them."""
+
+    def __init__(self, channels=[512, 320, 128, 64], kernel_sizes=[1, 3, 5], expansion_factor=6, dw_parallel=True, add=True, lgag_ks=3, activation='relu6'):
+        super().__init__()
+        self._register_stages(channels, kernel_sizes, expansion_factor, dw_parallel, add, lgag_ks, activation)
+
+    def _build(self, eng, x, skips):
+        """forward :356-405 -> [d4, d3, d2, d1]"""
+        d = self._stage(eng, x, 4)
+        ds = [d]
+        for lvl, skip in ((3, skips[0]), (2, skips[1]), (1, skips[2])):
+            d = self._gated_stage(eng, getattr(self, f"eucb{lvl}")._build(eng, d), lvl, skip)
+            ds.append(d)
+        return ds
+
+
+class EMCAD_dual(_EMCADStages):
+    """EMCAD decoder with the dual-supervised reverse-attention heads (:407-526)."""
+
+    def __init__(self, channels=[512, 320, 128, 64], kernel_sizes=[1, 3, 5], expansion_factor=6, dw_parallel=True, add=True, lgag_ks=3, activation='relu6', num_class=None):
+        super().__init__()
+        assert num_class is not None
+        self._register_stages(channels, kernel_sizes, expansion_factor, dw_parallel, add, lgag_ks, activation)
         for i, lvl in enumerate((4, 3, 2, 1)):
             k, p = (1, 0) if lvl == 4 else (3, 1)
             setattr(self, f"ConvBlock{lvl}_fg", BasicConv2d(channels[i], num_class, kernel_size=k, padding=p))
             setattr(self, f"ConvBlock{lvl}_bg", BasicConv2d(channels[i], num_class, kernel_size=k, padding=p))
-
-    def _stage(self, eng, d, lvl):
-        d = getattr(self, f"cab{lvl}")._build_gated(eng, d)
-        d = self.sab._build_gated(eng, d)
-        return getattr(self, f"mscb{lvl}")[0]._build(eng, d)
 
     def _build(self, eng, x, skips):
         """forward :441-526 -> [d4_fg, d3_fg, d2_fg, d1_fg, d4_bg, d3_bg, d2_bg, d1_bg] (low-resolution K-channel fp32 maps)"""
@@ -223,8 +254,7 @@ class EMCAD_dual(nn.Module):
         for lvl, skip in ((3, skips[0]), (2, skips[1]), (1, skips[2])):
             d = getattr(self, f"eucb{lvl}")._build(eng, d)
             up_fg, up_bg = eng.resize_to(fg, d.H, d.W), eng.resize_to(bg, d.H, d.W)
-            d = eng.add(d, getattr(self, f"lgag{lvl}")._build(eng, d, skip))
-            d = self._stage(eng, d, lvl)
+            d = self._gated_stage(eng, d, lvl, skip)
             fg, bg = getattr(self, f"ConvBlock{lvl}_fg")._build(eng, d), getattr(self, f"ConvBlock{lvl}_bg")._build(eng, d)
             fg = eng.dsra_fuse(fg, up_fg, up_bg, True)
             fgs.append(fg); bgs.append(bg)

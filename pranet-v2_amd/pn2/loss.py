@@ -265,3 +265,85 @@ def mutation_loss(outs, label, bg_mask, lc=(0.5, 0.7, 0.3)):
     """sum over the 15 non-empty subsets s of the 4 scales of lc1*CE(sum fg) + lc2*Dice(softmax(sum fg)) + lc3*BCEWithLogits(sum bg, bg_mask)
     (EMCAD/trainer.py:106-140, supervision='mutation', dual): outs = the 8 maps EMCADNet returns, label (N,H,W) int, bg_mask (N,K,H,W)."""
     return _MutationLoss.apply(label, bg_mask, tuple(float(v) for v in lc), *outs)
+
+
+# subsets of the 4 maps the single-supervision trainer scores (EMCAD/trainer.py:114-119) as the kernels' 15-bit mask: bit s-1 selects subset s,
+# bit i of s means map i is in the sum.  'last' is the reference's fallback ss = [[-1]] (any other string there).
+SEG_SUBSETS = {"mutation": 0x7FFF, "deep_supervision": 0x008B, "last": 0x0080}
+
+
+def _seg_subsets(supervision):
+    if supervision not in SEG_SUBSETS:
+        raise ValueError(f"unknown supervision {supervision!r} (one of {sorted(SEG_SUBSETS)})")
+    return SEG_SUBSETS[supervision]
+
+
+def _seg_width(K):
+    wd = call.pn2_seg_loss_width(K)
+    if wd < 0:
+        raise RuntimeError(f"pn2.seg_loss is built for 2 <= K <= 9 classes (got {K})")
+    return wd
+
+
+class _SegLoss(torch.autograd.Function):
+    """The single-supervision CE + Dice loss of EMCAD/trainer.py:141-153 as two kernels (pn2_seg_loss_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, label, subsets, w, *maps):
+        if not maps[0].is_cuda:
+            raise RuntimeError("pn2.seg_loss needs GPU tensors (no CPU fallback)")
+        if len(maps) != 4:
+            raise ValueError(f"pn2.seg_loss takes the 4 maps of EMCADNet (got {len(maps)})")
+        N, K, H, W = maps[0].shape
+        wd = _seg_width(K)
+        nhwc = [m.permute(0, 2, 3, 1).float().contiguous() for m in maps]          # no copy for the engine's K-channel output maps
+        lab = label.long().contiguous()
+        dev = maps[0].device
+        partial = torch.empty((call.pn2_mutation_loss_blocks(N * H * W), wd), dtype=torch.float32, device=dev)
+        sums = torch.empty(wd, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        PA = C.c_void_p * 4
+        call.pn2_seg_loss_fwd(PA(*[t.data_ptr() for t in nhwc]), subsets, _p(lab), N, H * W, K, w[0], w[1], _p(partial), _p(sums), _p(loss), _stream())
+        ctx.save_for_backward(lab, sums, *nhwc)
+        ctx.meta = (N, K, H, W, subsets, w)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lab, sums, *nhwc = ctx.saved_tensors
+        N, K, H, W, subsets, w = ctx.meta
+        grads = [torch.empty_like(t) for t in nhwc]
+        PA = C.c_void_p * 4
+        call.pn2_seg_loss_bwd(PA(*[t.data_ptr() for t in nhwc]), PA(*[t.data_ptr() for t in grads]), subsets, _p(lab), N, H * W, K, w[0], w[1], _p(sums), 1.0, _stream())
+        return (None, None, None, *[(gr * g).permute(0, 3, 1, 2) for gr in grads])
+
+
+def seg_forward_backward(eng, outs, label, supervision="mutation", weights=(0.3, 0.7), gscale=1.0):
+    """Trainer path of seg_loss: `outs` are the engine's 4 fp32 [N][H][W][K] maps; the loss kernel reads them in place and the backward kernel writes
+    their gradients straight into the activations' gradient buffers (exact zeros for a map outside every subset).  Returns loss[1]."""
+    subsets = _seg_subsets(supervision)
+    if len(outs) != 4:
+        raise ValueError(f"pn2.seg_loss takes the 4 maps of EMCADNet (got {len(outs)})")
+    N, H, W, K = outs[0].N, outs[0].H, outs[0].W, outs[0].C
+    for o in outs:
+        assert o.dt == F32 and o.ld == K and (o.N, o.H, o.W, o.C) == (N, H, W, K)
+    wd = _seg_width(K)
+    lab = label.long().contiguous()
+    partial, sums, loss = eng.fbuf(call.pn2_mutation_loss_blocks(N * H * W), wd), eng.fbuf(wd), eng.fbuf(1)
+    PA = C.c_void_p * 4
+    maps = PA(*[o.t.data_ptr() for o in outs])
+    st = _stream()
+    call.pn2_seg_loss_fwd(maps, subsets, _p(lab), N, H * W, K, float(weights[0]), float(weights[1]), _p(partial), _p(sums), _p(loss), st)
+    dmaps = PA(*[o.grad_buf().data_ptr() for o in outs])
+    call.pn2_seg_loss_bwd(maps, dmaps, subsets, _p(lab), N, H * W, K, float(weights[0]), float(weights[1]), _p(sums), float(gscale), st)
+    for o in outs:
+        o.grad_written = True
+    eng.keep_alive = (lab,)
+    return loss
+
+
+def seg_loss(outs, label, supervision="mutation", weights=(0.3, 0.7)):
+    """sum over the subsets s that `supervision` selects of weights[0]*CE(sum_{i in s} outs[i]) + weights[1]*Dice(softmax(sum_{i in s} outs[i]))
+    (EMCAD/trainer.py:141-153): outs = the 4 maps a single-supervision EMCADNet returns (N,K,H,W), 2 <= K <= 9; label (N,H,W) int.
+    supervision: 'mutation' (all 15 non-empty subsets), 'deep_supervision' (each map on its own), 'last' (the last map only)."""
+    return _SegLoss.apply(label, _seg_subsets(supervision), tuple(float(v) for v in weights), *outs)

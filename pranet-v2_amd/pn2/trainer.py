@@ -45,17 +45,29 @@ _CAP_GROUPS = {}          # main process group -> (communicator for captured col
 
 class Trainer:
     def __init__(self, model, lr=1e-4, clip=0.5, betas=(0.9, 0.999), eps=1e-8, dtype=None, process_group=None, bucket_bytes=100 << 20,
-                 loss="structure", loss_weights=(0.5, 0.7, 0.3), weight_decay=0.0, hot=None, force_dp=False):
+                 loss="structure", loss_weights=None, weight_decay=0.0, hot=None, force_dp=False, supervision="mutation"):
         """loss: "structure" - the 4-pair structure loss of MyTrain_med.py:78-82 on (images, masks), Adam + clip_gradient (binary_seg);
                  "mutation"  - the 15-subset CE + Dice + BCE loss of EMCAD/trainer.py:106-140 on (images, (label, bg_mask)) with the 8 maps of a
-                               dual EMCADNet; pass clip=None and weight_decay=1e-4 for its AdamW (trainer.py:75).
+                               dual EMCADNet; pass clip=None and weight_decay=1e-4 for its AdamW (trainer.py:75).  With a single-supervision
+                               EMCADNet (dual=False): the CE + Dice loss of trainer.py:141-153 on (images, label) with its 4 maps (a
+                               (label, bg_mask) pair is accepted, bg_mask is not used).
+        loss_weights: (lc1, lc2, lc3) of the dual loss, default (0.5, 0.7, 0.3); (w_ce, w_dice) of the single-supervision loss, default (0.3, 0.7).
+        supervision: which subsets of the 4 maps the single-supervision loss scores - "mutation" (all 15), "deep_supervision" (each map alone),
+                 "last" (the last map); the dual loss is built for "mutation" only.
         hot: the parameters the step trains (default model.hot_parameters()).
         force_dp: run the data-parallel machinery (bucket hooks, graph segments, asynchronous all-reduce) even on a 1-rank process group - how the
                  RCCL path is exercised on a single GPU (tests/test_gpu_dp.py, bench.py --dp1; also PN2_DP_FORCE=1)."""
         self.model = model
-        self.loss_kind, self.loss_weights, self.weight_decay = loss, tuple(float(v) for v in loss_weights), float(weight_decay)
         if loss not in ("structure", "mutation"):
             raise ValueError(f"unknown loss {loss!r}")
+        self.single = loss == "mutation" and getattr(model, "dual", True) is False          # a single-supervision EMCADNet: 4 maps, CE + Dice
+        if supervision not in L.SEG_SUBSETS:
+            raise ValueError(f"unknown supervision {supervision!r} (one of {sorted(L.SEG_SUBSETS)})")
+        if supervision != "mutation" and not self.single:
+            raise ValueError(f"supervision={supervision!r} needs loss='mutation' and a single-supervision EMCADNet (dual=False): the dual loss is built for 'mutation' only")
+        if loss_weights is None:
+            loss_weights = (0.3, 0.7) if self.single else (0.5, 0.7, 0.3)
+        self.loss_kind, self.supervision, self.loss_weights, self.weight_decay = loss, supervision, tuple(float(v) for v in loss_weights), float(weight_decay)
         clip = 3.0e38 if clip is None else clip
         self.lr, self.clip, self.betas, self.eps = lr, clip, betas, eps
         self.dtype = get_compute_dtype() if dtype is None else dtype          # compute mode (BF16 / F32 / F32F / F32X3), kept for the object's life
@@ -188,6 +200,10 @@ class Trainer:
             x = eng.from_nchw(images)
         outs = self.model._build(eng, x)
         eng.finish_forward()
+        if self.single:
+            label = gts[0] if isinstance(gts, (tuple, list)) else gts
+            loss = L.seg_forward_backward(eng, outs, label, self.supervision, self.loss_weights)
+            return self._backward(eng, st, loss, None, reduce_hook)
         if self.loss_kind == "mutation":
             label, bg_mask = gts
             loss = L.mutation_forward_backward(eng, outs, label, bg_mask, self.loss_weights)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """BASELINE config 5 on one GPU: EMCADNet(dual, K=9, pvt_v2_b2) forward + the reference trainer's 15-subset loss (torch ops, as trainer.py:106-140
-runs them) + backward + optimizer step through the nn.Module surface.  Usage: [EMCAD_ENCODER=pvt_v2_b0] emcad_bench.py [batch] [size] [steps]"""
+runs them) + backward + optimizer step through the nn.Module surface.  Usage: [EMCAD_ENCODER=pvt_v2_b0] emcad_bench.py [batch] [size] [steps]
+EMCAD_DUAL=0: the single-supervision model (EMCADNet(dual=False), 4 maps, CE + Dice of trainer.py:141-153); EMCAD_SUPERVISION = mutation | deep_supervision | last
+and EMCAD_CLASSES = 2..9 then apply."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "pranet-v2_amd"))
@@ -18,45 +20,53 @@ pn2.set_compute_dtype("bf16")
 torch.manual_seed(0)
 ENCODER = os.environ.get("EMCAD_ENCODER", "pvt_v2_b2")     # config 5 is pvt_v2_b2; pvt_v2_b0 is the small encoder (head_dim 32)
 ENC = "" if ENCODER == "pvt_v2_b2" else f" {ENCODER}"
-model = EMCADNet(num_classes=9, kernel_sizes=[1, 3, 5], expansion_factor=2, activation="relu6", encoder=ENCODER, pretrain=False, dual=True).cuda().train()
+DUAL = os.environ.get("EMCAD_DUAL", "1") != "0"
+SUP = os.environ.get("EMCAD_SUPERVISION", "mutation")
+K = int(os.environ.get("EMCAD_CLASSES", "9"))
+if DUAL and (SUP != "mutation" or K != 9):
+    sys.exit("EMCAD_SUPERVISION / EMCAD_CLASSES apply to the single-supervision model (EMCAD_DUAL=0)")
+TAG = "dual K=9" if DUAL else f"single ({SUP}) K={K}"
+model = EMCADNet(num_classes=K, kernel_sizes=[1, 3, 5], expansion_factor=2, activation="relu6", encoder=ENCODER, pretrain=False, dual=DUAL).cuda().train()
 GRAPH = os.environ.get("EMCAD_GRAPH", "0") == "1"          # replay the whole step (forward, loss, backward, AdamW) from one hipGraph
 opt = torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=1e-4, capturable=GRAPH)
 x = torch.randn(bs, 1, size, size, device="cuda")
-label = torch.randint(0, 9, (bs, size // 16, size // 16), device="cuda")
+label = torch.randint(0, K, (bs, size // 16, size // 16), device="cuda")
 label = F.interpolate(label[:, None].float(), size=(size, size), mode="nearest")[:, 0].long()
-bg = torch.stack([(label != k).float() for k in range(9)], 1)
+bg = torch.stack([(label != k).float() for k in range(K)], 1)
 subsets = [s for s in __import__("itertools").chain.from_iterable(__import__("itertools").combinations(range(4), r) for r in range(1, 5))]
+if not DUAL:
+    subsets = {"mutation": subsets, "deep_supervision": [(i,) for i in range(4)], "last": [(3,)]}[SUP]
 
 
 def dice(logits, target):
     prob = torch.softmax(logits, 1); loss = 0.0
-    for i in range(9):
+    for i in range(K):
         t = (target == i).float(); s = prob[:, i]
         loss = loss + (1 - (2 * (s * t).sum() + 1e-5) / ((s * s).sum() + (t * t).sum() + 1e-5))
-    return loss / 9
+    return loss / K
 
 
 FUSED = os.environ.get("EMCAD_TORCH_LOSS", "0") != "1"
-from pn2.loss import mutation_loss
+from pn2.loss import mutation_loss, seg_loss
 
 
 TRAINER = os.environ.get("EMCAD_TRAINER", "0") == "1"      # pn2.trainer.Trainer(loss="mutation"): arena, deferred table launches, AdamW kernel, hipGraph
 if TRAINER:
     from pn2.trainer import Trainer
-    tr = Trainer(model, lr=1e-4, clip=None, weight_decay=1e-4, loss="mutation", hot=model.hot_parameters(True))
+    tr = Trainer(model, lr=1e-4, clip=None, weight_decay=1e-4, loss="mutation", hot=model.hot_parameters(True), supervision=SUP)
     for _ in range(3):
         l = tr.step(x, (label, bg))
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(steps):
         l = tr.step(x, (label, bg))
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
-    print(f"EMCADNet dual K=9{ENC} bs={bs} {size}x{size} bf16 (Trainer, eager): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l[0]):.3f}")
+    print(f"EMCADNet {TAG}{ENC} bs={bs} {size}x{size} bf16 (Trainer, eager): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l[0]):.3f}")
     tr.capture(x, (label, bg), warmup=2)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(steps):
         l = tr.replay()
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
-    print(f"EMCADNet dual K=9{ENC} bs={bs} {size}x{size} bf16 (Trainer, hipGraph replay): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l[0]):.3f}")
+    print(f"EMCADNet {TAG}{ENC} bs={bs} {size}x{size} bf16 (Trainer, hipGraph replay): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l[0]):.3f}")
     with Recorder() as rec:
         tr.step(x, (label, bg))
     agg = rec.summary()
@@ -73,7 +83,12 @@ if TRAINER:
 def step():
     P = model(x, mode="train")
     if FUSED:
-        loss = mutation_loss(P, label, bg)
+        loss = mutation_loss(P, label, bg) if DUAL else seg_loss(P, label, SUP)
+    elif not DUAL:
+        loss = 0.0
+        for s in subsets:
+            iout = sum(P[i] for i in s)
+            loss = loss + 0.3 * F.cross_entropy(iout, label) + 0.7 * dice(iout, label)
     else:
         loss = 0.0
         for s in subsets:
@@ -102,7 +117,7 @@ for _ in range(steps):
     r = run()
     l = l if GRAPH else r
 torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
-print(f"EMCADNet dual K=9{ENC} bs={bs} {size}x{size} bf16 ({'fused pn2.loss.mutation_loss' if FUSED else 'torch loss'}{', hipGraph replay' if GRAPH else ''}): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l.detach()):.3f}")
+print(f"EMCADNet {TAG}{ENC} bs={bs} {size}x{size} bf16 ({'fused pn2.loss kernels' if FUSED else 'torch loss'}{', hipGraph replay' if GRAPH else ''}): {1e3 * dt:.1f} ms/step  {bs / dt:.1f} img/s  loss {float(l.detach()):.3f}")
 if GRAPH:
     sys.exit(0)
 with Recorder() as rec:
