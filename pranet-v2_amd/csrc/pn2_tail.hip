@@ -1321,24 +1321,18 @@ int pn2_ra_gate_post_bwd(int dt, const void* raw, int ld_raw, const float* crop,
     return 0;
 }
 
-int pn2_loss_weights(const float* mask, float* weit, int N, int H, int W, int ksize, void* stream) {
-    if (!mask || !weit) return -1;
-    if (ksize < 1 || !(ksize & 1) || ksize > 63) return -2;
-    const int TSY = LTY + ksize - 1, TSX = (LTX + ksize - 1) | 1;
-    const size_t lds = (size_t)(TSY * TSX + TSY * (LTX + 1)) * 4;
-    hipLaunchKernelGGL(loss_weights_k, dim3((W + LTX - 1) / LTX, (H + LTY - 1) / LTY, N), dim3(256), lds, (hipStream_t)stream, mask, weit, H, W, ksize);
-    PN2_CHECK_LAUNCH();
-    return 0;
-}
+// tile + row sums of loss_weights_k in bytes: 38.8 KiB at ks = 31, above the default 64 KiB of dynamic LDS from ks = 59 on (70.5 KiB at 63), hence the opt-in
+static constexpr size_t loss_weights_lds(int ks) { return (size_t)((LTY + ks - 1) * ((LTX + ks - 1) | 1) + (LTY + ks - 1) * (LTX + 1)) * 4; }
 
 int pn2_loss_weights_clear(const float* mask, float* weit, int N, int H, int W, int ksize, long long* clear, int nclear, void* stream) {
     if (!mask || !weit || (nclear > 0 && !clear) || nclear < 0) return -1;
     if (ksize < 1 || !(ksize & 1) || ksize > 63) return -2;
-    const int TSY = LTY + ksize - 1, TSX = (LTX + ksize - 1) | 1;
-    const size_t lds = (size_t)(TSY * TSX + TSY * (LTX + 1)) * 4;
-    hipLaunchKernelGGL(loss_weights_k, dim3((W + LTX - 1) / LTX, (H + LTY - 1) / LTY, N), dim3(256), lds, (hipStream_t)stream, mask, weit, H, W, ksize, clear, nclear);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<loss_weights_k>(dim3((W + LTX - 1) / LTX, (H + LTY - 1) / LTY, N), dim3(256), loss_weights_lds(ksize), (int)loss_weights_lds(63), (hipStream_t)stream,
+                                      mask, weit, H, W, ksize, clear, nclear);
+}
+
+int pn2_loss_weights(const float* mask, float* weit, int N, int H, int W, int ksize, void* stream) {
+    return pn2_loss_weights_clear(mask, weit, N, H, W, ksize, nullptr, 0, stream);
 }
 
 int pn2_loss_blocks(int HW) { int b = (HW + 4095) / 4096; return b > 64 ? 64 : (b < 1 ? 1 : b); }
