@@ -532,6 +532,24 @@ int pn2_eval_region_sums(const unsigned char* pred_u8, const float* gt, int H, i
 int pn2_eval_wfm_blocks(int H, int W);
 int pn2_eval_wfm(const unsigned char* pred_u8, const float* gt, int H, int W, const double* K49, double c5, int* work_i, double* work_d, double* part, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- multi-class volume evaluation (csrc/pn2_seg.hip)
+ * test_single_volume / val_single_volume of multiclass_seg/EMCAD/utils/utils.py:140-301 (pn2/voleval.py).  Every entry validates its arguments first and launches
+ * nothing when it returns non-zero (-1: null pointer / empty size, -2: outside the built range).
+ * pn2_seg_labels: out u8 [N][H][W] = argmax over k of the combined logits of `nmaps` contiguous NCHW fp32 maps [N][K][H][W], 2 <= K <= 16, lowest index on a tie.
+ *   `maps` is a HOST array of nmaps device pointers.  mode 0 "last": maps[nmaps-1];  mode 1 "sum_fg": 0.0 + maps[0] + maps[1] + ... (1..8 maps);
+ *   mode 2 "sum_fg_minus_bg": 0.0 + (maps[0] - maps[h]) + (maps[1] - maps[h+1]) + ..., h = nmaps / 2 (nmaps even).  fp32, in this order, nothing reassociated.
+ *   The argmax is taken of the logits, not of their fp32 softmax (the two differ only where softmax rounds two distinct logits to one probability).
+ * pn2_seg_counts: counts u64 [K][3] = { |pred = c|, |gt = c|, |pred = c and gt = c| } of two u8 label volumes of n voxels, 1 <= K <= 256 (overwritten).
+ * pn2_seg_surface_hist: for class `cls` of the u8 label volumes A, B [D][H][W] (ndim 3: six face neighbours; ndim 2: D = 1, four), border = voxels of the class
+ *   with a face neighbour outside it (outside the volume counts): hist[d2] = number of border voxels of A whose nearest border voxel of B lies at squared
+ *   Euclidean distance d2 (exact, in voxels); hist has pn2_seg_surface_hist_len(D, H, W) = (D-1)^2 + (H-1)^2 + (W-1)^2 + 1 entries, counts2 = { border voxels of A,
+ *   of B }; both overwritten.  Every axis <= 1024.  work: pn2_seg_surface_workspace(...) bytes of scratch.  A class missing from B leaves the histogram empty. */
+int pn2_seg_labels(const float* const* maps, int nmaps, int mode, int N, int K, int H, int W, unsigned char* out, void* stream);
+int pn2_seg_counts(const unsigned char* pred, const unsigned char* gt, long long n, int K, unsigned long long* counts, void* stream);
+int pn2_seg_surface_workspace(int D, int H, int W, int ndim, long long* bytes);
+int pn2_seg_surface_hist_len(int D, int H, int W);          /* value; -1 outside the range */
+int pn2_seg_surface_hist(const unsigned char* A, const unsigned char* B, int D, int H, int W, int cls, int ndim, unsigned* hist, unsigned* counts2, void* work, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- input transform
  * binary_seg/utils/dataloader.py:104-111 (PolypDataset) / :176-181 (test_dataset): transforms.Resize((S, S)) on the decoded PIL image
  * (= PIL.Image.resize(BILINEAR): separable antialiased triangle filter, uint8 after each pass, 22-bit fixed-point taps; Pillow Resample.c),

@@ -1,0 +1,262 @@
+// pn2_seg.hip — the multi-class volume evaluation of the reference's test_single_volume / val_single_volume (multiclass_seg/EMCAD/utils/utils.py:140-301) on the GPU:
+//   label map        argmax over the K channels of the combined logits of 1..8 maps               -> pn2_seg_labels
+//   dc / jc          |pred = c|, |gt = c|, |pred = c and gt = c| for every class                  -> pn2_seg_counts
+//   hd95 / assd      medpy's __surface_distances: for every border voxel of A the exact squared Euclidean distance to the nearest border voxel of B,
+//                    as a histogram over d^2                                                        -> pn2_seg_surface_hist
+// pn2_seg_labels takes the argmax of the combined LOGITS; the reference takes argmax(softmax(logits)) (utils.py:195,273).  softmax is monotone, so the two differ
+// only where fp32 softmax rounds two distinct logits to one probability (then the reference returns the lower index and this kernel the larger logit).
+// Everything that decides a metric is an integer (labels, voxel counts, squared distances in voxels) accumulated with integer atomics: exact and independent of
+// the order of execution.  The host finishes in float64 with medpy's expressions (pn2/voleval.py).
+//
+// Surface distances, for class c and label volumes A, B [D][H][W]:
+//   border(V) = voxels with label c that have a face neighbour without it, outside the volume counting as "without" (mask ^ binary_erosion(mask) with
+//               generate_binary_structure(ndim, 1), border value 0); ndim = 2 ignores the z neighbours.
+//   seg_bbox_k   bounding boxes of the class-c voxels of A and of B (integer atomicMin / atomicMax): B's border lies inside B's box, A's inside A's
+//   seg_rows_k   f1[z][y][x] = (x - x')^2 to the nearest border voxel x' of B in row (z, y); only rows inside B's box, only x inside A's box; counts B's border
+//   seg_cols_k   f2[z][y][x] = min over y' in B's box of f1[z][y'][x] + (y - y')^2; only z inside B's box, only (y, x) inside A's box
+//   seg_hist_k   at every border voxel of A: d^2 = min over z' in B's box of f2[z'][y][x] + (z - z')^2 -> hist[d^2] += 1; counts A's border
+// int32 throughout: SEG_INF + 2 * 1023^2 < 2^31.  The boxes are read from device memory by every kernel: no host round trip.
+#include "pn2_common.h"
+#include "../../include/pn2.h"
+
+namespace {
+
+typedef unsigned long long u64;
+typedef unsigned char u8;
+constexpr int SEG_INF = 1 << 29;
+constexpr int SEG_MAX_AXIS = 1024;
+
+struct SegMaps { const float* p[8]; };
+
+// one thread per pixel; channel k of map m at (n, k, p) is m[(n*K + k)*HW + p]: consecutive lanes read consecutive floats of one channel plane
+template <int MODE>
+__global__ __launch_bounds__(256) void seg_labels_k(SegMaps maps, int nmaps, int N, int K, long long HW, u8* __restrict__ out) {
+    const long long total = (long long)N * HW;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long n = i / HW, p = i - n * HW;
+        const size_t base = (size_t)n * K * HW + p;
+        float best = 0.f; int bk = 0;
+        for (int k = 0; k < K; ++k) {
+            const size_t o = base + (size_t)k * HW;
+            float v;
+            if (MODE == 0) v = maps.p[nmaps - 1][o];
+            else if (MODE == 1) { v = 0.0f; for (int m = 0; m < nmaps; ++m) v += maps.p[m][o]; }
+            else { const int h = nmaps / 2; v = 0.0f; for (int m = 0; m < h; ++m) v += (maps.p[m][o] - maps.p[h + m][o]); }
+            // torch.argmax: first maximum, a NaN counts as the maximum
+            if (k == 0 || v > best || (v != v && best == best)) { best = v; bk = k; }
+        }
+        out[i] = (u8)bk;
+    }
+}
+
+// cnt[c][0..2] += |pred = c|, |gt = c|, |pred = c and gt = c|: LDS counters per block, then one atomic per non-zero counter
+__global__ __launch_bounds__(256) void seg_counts_k(const u8* __restrict__ pred, const u8* __restrict__ gt, long long n, int K, u64* __restrict__ cnt) {
+    __shared__ unsigned sh[256 * 3];
+    for (int j = threadIdx.x; j < K * 3; j += 256) sh[j] = 0;
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int a = pred[i], b = gt[i];
+        if (a < K) atomicAdd(&sh[a * 3], 1u);
+        if (b < K) atomicAdd(&sh[b * 3 + 1], 1u);
+        if (a == b && a < K) atomicAdd(&sh[a * 3 + 2], 1u);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < K * 3; j += 256) if (sh[j]) atomicAdd(cnt + j, (u64)sh[j]);
+}
+
+// meta[0..5] = A's box {zmin, zmax, ymin, ymax, xmin, xmax}, meta[6..11] = B's; an empty box has min > max
+__global__ void seg_meta_init_k(int* __restrict__ meta) {
+    if (threadIdx.x < 12) meta[threadIdx.x] = ((threadIdx.x & 1) ? -1 : 0x7fffffff);
+}
+
+__device__ __forceinline__ void wave_box(int* meta, bool on, int z, int y, int x) {
+    int v[6] = { on ? z : 0x7fffffff, on ? z : -1, on ? y : 0x7fffffff, on ? y : -1, on ? x : 0x7fffffff, on ? x : -1 };
+    if (!__any(on)) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) { const int t = __shfl_xor(v[j], o); v[j] = (j & 1) ? max(v[j], t) : min(v[j], t); }
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) { if (j & 1) atomicMax(meta + j, v[j]); else atomicMin(meta + j, v[j]); }
+}
+
+__global__ __launch_bounds__(256) void seg_bbox_k(const u8* __restrict__ A, const u8* __restrict__ B, int D, int H, int W, int c, int* __restrict__ meta) {
+    const long long n = (long long)D * H * W, HWl = (long long)H * W;
+    const long long span = (long long)gridDim.x * 256;
+    for (long long i0 = (long long)blockIdx.x * 256; i0 < n; i0 += span) {          // whole waves enter wave_box together
+        const long long i = i0 + threadIdx.x;
+        const bool in = i < n;
+        const int z = in ? (int)(i / HWl) : 0;
+        const long long r = in ? i - (long long)z * HWl : 0;
+        const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+        wave_box(meta, in && A[i] == c, z, y, x);
+        wave_box(meta + 6, in && B[i] == c, z, y, x);
+    }
+}
+
+__device__ __forceinline__ bool seg_border(const u8* __restrict__ V, int D, int H, int W, int c, int ndim, int z, int y, int x) {
+    const size_t HWs = (size_t)H * W, i = (size_t)z * HWs + (size_t)y * W + x;
+    if (V[i] != c) return false;
+    if (x == 0 || x == W - 1 || y == 0 || y == H - 1) return true;
+    if (V[i - 1] != c || V[i + 1] != c || V[i - W] != c || V[i + W] != c) return true;
+    if (ndim == 3) {
+        if (z == 0 || z == D - 1) return true;
+        if (V[i - HWs] != c || V[i + HWs] != c) return true;
+    }
+    return false;
+}
+
+// one block per row (z, y) of B's box: the row's border bits as sixteen 64-bit words in LDS (one ballot per wave and 256 columns), then per column the nearest
+// set bit on either side
+__global__ __launch_bounds__(256) void seg_rows_k(const u8* __restrict__ B, int D, int H, int W, int c, int ndim, const int* __restrict__ meta, int* __restrict__ f1,
+                                                  unsigned* __restrict__ counts) {
+    __shared__ u64 bits[SEG_MAX_AXIS / 64];
+    const int y = blockIdx.x, z = blockIdx.y;
+    if (z < meta[6] || z > meta[7] || y < meta[8] || y > meta[9]) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned nb = 0;
+    for (int x0 = 0; x0 < W; x0 += 256) {
+        const int x = x0 + threadIdx.x;
+        const u64 m = __ballot(x < W && seg_border(B, D, H, W, c, ndim, z, y, x));
+        if (lane == 0) { bits[(x0 >> 6) + wv] = m; nb += (unsigned)__popcll(m); }
+    }
+    if (lane == 0 && nb) atomicAdd(counts + 1, nb);
+    __syncthreads();
+    const int nw = (W + 63) >> 6, xa = meta[4], xb = meta[5];
+    if (xa > xb) return;                                       // A has no voxel of the class: nothing will ask for a distance
+    int* __restrict__ row = f1 + ((size_t)z * H + y) * W;
+    for (int x = xa + (int)threadIdx.x; x <= xb; x += 256) {
+        const int w0 = x >> 6, b = x & 63;
+        int best = SEG_INF;
+        u64 m = bits[w0] & (~0ULL >> (63 - b));                // bits at or below x
+        for (int w = w0; ; ) {
+            if (m) { const int d = x - ((w << 6) + 63 - __clzll((long long)m)); best = d * d; break; }
+            if (--w < 0) break;
+            m = bits[w];
+        }
+        m = bits[w0] & (~0ULL << b);                           // bits at or above x
+        for (int w = w0; ; ) {
+            if (m) { const int d = ((w << 6) + __ffsll((long long)m) - 1) - x; best = min(best, d * d); break; }
+            if (++w >= nw) break;
+            m = bits[w];
+        }
+        row[x] = best;
+    }
+}
+
+// a block = 64 columns x 64 output rows of one slice z: thread (tx, ty) keeps the 16 outputs y0 + ty + 4k in registers and walks the candidate rows y' of B's box;
+// the 64 lanes of a wave read 64 consecutive f1 values of one candidate row
+__global__ __launch_bounds__(256) void seg_cols_k(int H, int W, const int* __restrict__ meta, const int* __restrict__ f1, int* __restrict__ f2) {
+    const int z = blockIdx.z;
+    const int ya = meta[2], yb = meta[3], xa = meta[4], xb = meta[5];
+    if (z < meta[6] || z > meta[7] || xa > xb) return;
+    const int x0 = blockIdx.x * 64, y0 = blockIdx.y * 64;
+    if (x0 > xb || x0 + 63 < xa || y0 > yb || y0 + 63 < ya) return;
+    const int x = x0 + (threadIdx.x & 63), ty = threadIdx.x >> 6;
+    if (x < xa || x > xb) return;
+    int best[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) best[k] = SEG_INF;
+    const int* __restrict__ src = f1 + (size_t)z * H * W + x;
+    const int cb = meta[9];
+    for (int yc = meta[8]; yc <= cb; ++yc) {
+        const int v = src[(size_t)yc * W];
+        const int d0 = y0 + ty - yc;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { const int d = d0 + 4 * k; best[k] = min(best[k], v + d * d); }
+    }
+    int* __restrict__ dst = f2 + (size_t)z * H * W + x;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { const int y = y0 + ty + 4 * k; if (y >= ya && y <= yb) dst[(size_t)y * W] = best[k]; }
+}
+
+// every voxel of A's box: a border voxel takes the min-plus over the slices of B's box and adds one to its histogram bin
+__global__ __launch_bounds__(256) void seg_hist_k(const u8* __restrict__ A, int D, int H, int W, int c, int ndim, const int* __restrict__ meta, const int* __restrict__ f2,
+                                                  unsigned* __restrict__ hist, int nhist, unsigned* __restrict__ counts) {
+    const int za = meta[0], zb = meta[1], ya = meta[2], yb = meta[3], xa = meta[4], xb = meta[5];
+    if (za > zb) return;
+    const long long bw = xb - xa + 1, bh = yb - ya + 1, n = bw * bh * (zb - za + 1);
+    const int sa = meta[6], sb = meta[7];
+    const size_t HWs = (size_t)H * W;
+    unsigned na = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int z = za + (int)(i / (bw * bh));
+        const long long r = i - (long long)(z - za) * bw * bh;
+        const int y = ya + (int)(r / bw), x = xa + (int)(r - (long long)(y - ya) * bw);
+        if (!seg_border(A, D, H, W, c, ndim, z, y, x)) continue;
+        ++na;
+        int best = SEG_INF;
+        const int* __restrict__ col = f2 + (size_t)y * W + x;
+        for (int zc = sa; zc <= sb; ++zc) { const int d = z - zc; best = min(best, col[(size_t)zc * HWs] + d * d); }
+        if (best < nhist) atomicAdd(hist + best, 1u);          // (B without a border: nothing to measure, the bins stay empty)
+    }
+    for (int o = 32; o > 0; o >>= 1) na += __shfl_xor(na, o);
+    if ((threadIdx.x & 63) == 0 && na) atomicAdd(counts, na);
+}
+
+bool seg_dims_ok(int D, int H, int W, int ndim) {
+    return D >= 1 && H >= 1 && W >= 1 && D <= SEG_MAX_AXIS && H <= SEG_MAX_AXIS && W <= SEG_MAX_AXIS && (ndim == 3 || (ndim == 2 && D == 1));
+}
+
+}  // namespace
+
+extern "C" {
+
+int pn2_seg_labels(const float* const* maps, int nmaps, int mode, int N, int K, int H, int W, unsigned char* out, void* stream) {
+    if (!maps || !out || N < 1 || H < 1 || W < 1) return -1;
+    if (K < 2 || K > 16 || nmaps < 1 || nmaps > 8 || mode < 0 || mode > 2 || (mode == 2 && (nmaps & 1))) return -2;
+    SegMaps m;
+    for (int i = 0; i < 8; ++i) { m.p[i] = i < nmaps ? maps[i] : nullptr; if (i < nmaps && !maps[i]) return -1; }
+    const long long HW = (long long)H * W;
+    const dim3 g(pn2_host::grid_for((size_t)N * HW, 65536));
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 0) hipLaunchKernelGGL(seg_labels_k<0>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
+    else if (mode == 1) hipLaunchKernelGGL(seg_labels_k<1>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
+    else hipLaunchKernelGGL(seg_labels_k<2>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+int pn2_seg_counts(const unsigned char* pred, const unsigned char* gt, long long n, int K, unsigned long long* counts, void* stream) {
+    if (!pred || !gt || !counts || n < 1) return -1;
+    if (K < 1 || K > 256) return -2;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, (size_t)K * 3 * sizeof(unsigned long long), st) != hipSuccess) return -4;
+    hipLaunchKernelGGL(seg_counts_k, dim3(pn2_host::grid_for((size_t)((n + 15) / 16), 2048)), dim3(256), 0, st, pred, gt, n, K, counts);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+int pn2_seg_surface_workspace(int D, int H, int W, int ndim, long long* bytes) {
+    if (!bytes) return -1;
+    if (!seg_dims_ok(D, H, W, ndim)) return -2;
+    *bytes = 64 + 2LL * D * H * W * (long long)sizeof(int);
+    return 0;
+}
+
+int pn2_seg_surface_hist_len(int D, int H, int W) {
+    if (!seg_dims_ok(D, H, W, 3)) return -1;
+    return (D - 1) * (D - 1) + (H - 1) * (H - 1) + (W - 1) * (W - 1) + 1;
+}
+
+int pn2_seg_surface_hist(const unsigned char* A, const unsigned char* B, int D, int H, int W, int cls, int ndim, unsigned* hist, unsigned* counts2, void* work, void* stream) {
+    if (!A || !B || !hist || !counts2 || !work) return -1;
+    if (!seg_dims_ok(D, H, W, ndim) || cls < 0 || cls > 255) return -2;
+    hipStream_t st = (hipStream_t)stream;
+    const int nhist = pn2_seg_surface_hist_len(D, H, W);
+    const size_t n = (size_t)D * H * W;
+    int* meta = (int*)work;
+    int* f1 = meta + 16;
+    int* f2 = f1 + n;
+    if (hipMemsetAsync(hist, 0, (size_t)nhist * sizeof(unsigned), st) != hipSuccess || hipMemsetAsync(counts2, 0, 2 * sizeof(unsigned), st) != hipSuccess) return -4;
+    hipLaunchKernelGGL(seg_meta_init_k, dim3(1), dim3(64), 0, st, meta);
+    hipLaunchKernelGGL(seg_bbox_k, dim3(pn2_host::grid_for((n + 15) / 16, 2048)), dim3(256), 0, st, A, B, D, H, W, cls, meta);
+    hipLaunchKernelGGL(seg_rows_k, dim3(H, D), dim3(256), 0, st, B, D, H, W, cls, ndim, meta, f1, counts2);
+    hipLaunchKernelGGL(seg_cols_k, dim3((W + 63) / 64, (H + 63) / 64, D), dim3(256), 0, st, H, W, meta, f1, f2);
+    hipLaunchKernelGGL(seg_hist_k, dim3(pn2_host::grid_for((n + 3) / 4, 8192)), dim3(256), 0, st, A, D, H, W, cls, ndim, meta, f2, hist, nhist, counts2);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"

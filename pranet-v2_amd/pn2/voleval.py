@@ -1,0 +1,198 @@
+"""Multi-class volume evaluation of the reference's test_synapse.py / trainer.py:inference on the GPU (multiclass_seg/EMCAD/utils/utils.py:140-301):
+label maps from the K-channel logits, per-class voxel counts, and medpy's surface distances as exact histograms over the squared voxel distance
+(csrc/pn2_seg.hip).  The four reported numbers - Dice, HD95, Jaccard, ASD - are finished on the host in float64 from those integers with the
+expressions of medpy.metric.binary (dc, hd95, jc, assd).  GPU tensors only: there is no CPU fallback."""
+import ctypes as C
+
+import torch
+
+from .capi import call
+from .core import _p, _stream
+
+MODES = {"last": 0, "sum_fg": 1, "sum_fg_minus_bg": 2}
+MAX_AXIS = 1024
+
+
+def _need_gpu(*ts):
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("pn2.voleval needs GPU tensors (no CPU fallback)")
+
+
+def predict_labels(outs, mode):
+    """outs: 1..8 NCHW fp32 maps [N][K][H][W] as the model returns them, 2 <= K <= 16.  Returns uint8 [N][H][W]: the argmax over K of
+      'last'             outs[-1]                                                   (utils.py:193,271)
+      'sum_fg'           0.0 + outs[0] + outs[1] + ...                              (:188-190; pass the foreground maps)
+      'sum_fg_minus_bg'  0.0 + (outs[0] - outs[h]) + (outs[1] - outs[h+1]) + ...    (:265-267; foreground maps, then as many background maps)
+    in fp32 in this order; the lowest index wins a tie, as in torch.argmax.  The argmax is taken of the logits, not of their fp32 softmax."""
+    if mode not in MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(MODES)}")
+    outs = list(outs)
+    _need_gpu(*outs)
+    if not 1 <= len(outs) <= 8 or (mode == "sum_fg_minus_bg" and len(outs) % 2):
+        raise ValueError("1..8 maps (an even number for sum_fg_minus_bg)")
+    shape = tuple(outs[0].shape)
+    if len(shape) != 4 or not 2 <= shape[1] <= 16 or any(tuple(o.shape) != shape or o.dtype != torch.float32 for o in outs):
+        raise ValueError("maps must be fp32 [N][K][H][W] of one shape with 2 <= K <= 16")
+    outs = [o.detach().contiguous() for o in outs]
+    N, K, H, W = shape
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=outs[0].device)
+    ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+    call.pn2_seg_labels(ptrs, len(outs), MODES[mode], N, K, H, W, _p(out), _stream())
+    return out
+
+
+def _volumes(pred, label, classes):
+    _need_gpu(pred, label)
+    if pred.shape != label.shape or pred.dim() not in (2, 3):
+        raise ValueError("pred and label must be [D][H][W] or [H][W] label volumes of one shape")
+    if not 2 <= int(classes) <= 256:
+        raise ValueError("2 <= classes <= 256")
+    if max(pred.shape) > MAX_AXIS:
+        raise ValueError(f"volume {tuple(pred.shape)}: every axis must be <= {MAX_AXIS}")
+    return pred.to(torch.uint8).contiguous(), label.to(torch.uint8).contiguous()
+
+
+def class_counts(pred, label, classes):
+    """int64 ndarray [classes][3] = |pred = c|, |label = c|, |pred = c and label = c| (one kernel, one copy to the host)."""
+    p, g = _volumes(pred, label, classes)
+    cnt = torch.empty((int(classes), 3), dtype=torch.int64, device=p.device)
+    call.pn2_seg_counts(_p(p), _p(g), p.numel(), int(classes), _p(cnt), _stream())
+    return cnt.cpu().numpy()
+
+
+def surface_histograms(pred, label, cls_list):
+    """For every class c of cls_list both directions of medpy's __surface_distances as histograms over the squared distance:
+    -> {c: (hist pred->label, hist label->pred, border voxels of pred, border voxels of label)} with int64 ndarrays.  All launches first, one copy to the host."""
+    import numpy as np
+    p, g = _volumes(pred, label, 256)
+    ndim = p.dim()
+    D, H, W = (1,) * (3 - ndim) + tuple(p.shape)
+    cls_list = list(cls_list)
+    if not cls_list:
+        return {}
+    L = int(call.pn2_seg_surface_hist_len(D, H, W))
+    nbytes = C.c_longlong(0)
+    call.pn2_seg_surface_workspace(D, H, W, ndim, C.byref(nbytes))
+    work = torch.empty(int(nbytes.value), dtype=torch.uint8, device=p.device)
+    hist = torch.empty((len(cls_list), 2, L), dtype=torch.int32, device=p.device)
+    cnt = torch.empty((len(cls_list), 2, 2), dtype=torch.int32, device=p.device)
+    st = _stream()
+    for i, c in enumerate(cls_list):
+        call.pn2_seg_surface_hist(_p(p), _p(g), D, H, W, int(c), ndim, _p(hist[i, 0]), _p(cnt[i, 0]), _p(work), st)
+        call.pn2_seg_surface_hist(_p(g), _p(p), D, H, W, int(c), ndim, _p(hist[i, 1]), _p(cnt[i, 1]), _p(work), st)
+    h, n = hist.cpu().numpy().astype(np.int64), cnt.cpu().numpy().astype(np.int64)
+    out = {}
+    for i, c in enumerate(cls_list):
+        out[c] = (h[i, 0], h[i, 1], int(n[i, 0, 0]), int(n[i, 0, 1]))
+    return out
+
+
+def _hd95_asd(h_ab, h_ba):
+    """medpy's hd95 = numpy.percentile(hstack(d(A->B), d(B->A)), 95) (linear interpolation) and assd = mean(mean d(A->B), mean d(B->A)) from the two
+    d^2 histograms: the sorted distances are the bins of the merged histogram repeated by their counts, each value sqrt(float64(d^2)) as
+    scipy's distance_transform_edt returns it."""
+    import numpy as np
+    merged = h_ab + h_ba
+    bins = np.nonzero(merged)[0]
+    cum = np.cumsum(merged[bins])
+    n = int(cum[-1])
+    vals = np.sqrt(bins.astype(np.float64))
+    pos = np.float64(95) / 100 * (n - 1)                 # numpy's 'linear' method: virtual index q * (n - 1)
+    lo = int(np.floor(pos))
+    t = pos - lo
+    a = vals[np.searchsorted(cum, lo, side="right")]
+    b = vals[np.searchsorted(cum, min(lo + 1, n - 1), side="right")]
+    hd95 = a + (b - a) * t if t < 0.5 else b - (b - a) * (1 - t)          # numpy's _lerp
+    means = []
+    for h in (h_ab, h_ba):
+        k = np.nonzero(h)[0]
+        means.append(float((h[k] * np.sqrt(k.astype(np.float64))).sum()) / int(h.sum()))
+    return float(hd95), float(np.mean(means))
+
+
+def volume_metrics(pred, label, classes):
+    """calculate_metric_percase(pred == c, label == c) for c = 1 .. classes-1 (utils.py:140-152, :232-234): a list of (dice, hd95, jaccard, asd).
+    pred has voxels and label none -> (1, 0, 1, 0); pred empty -> (0, 0, 0, 0); no distance pass runs for those classes."""
+    cnt = class_counts(pred, label, classes)
+    live = [c for c in range(1, int(classes)) if cnt[c, 0] > 0 and cnt[c, 1] > 0]
+    hists = surface_histograms(pred, label, live)
+    out = []
+    for c in range(1, int(classes)):
+        p, g, i = (int(v) for v in cnt[c])
+        if p > 0 and g > 0:
+            hd95, asd = _hd95_asd(hists[c][0], hists[c][1])
+            out.append((2. * i / float(p + g), hd95, float(i) / float(p + g - i), asd))
+        elif p > 0:
+            out.append((1, 0, 1, 0))
+        else:
+            out.append((0, 0, 0, 0))
+    return out
+
+
+def volume_dice(pred, label, classes):
+    """calculate_dice_percase(pred == c, label == c) for c = 1 .. classes-1 (utils.py:154-163, :298-300): needs the voxel counts only."""
+    cnt = class_counts(pred, label, classes)
+    out = []
+    for c in range(1, int(classes)):
+        p, g, i = (int(v) for v in cnt[c])
+        out.append(2. * i / float(p + g) if p > 0 and g > 0 else (1 if p > 0 else 0))
+    return out
+
+
+def _zoom():
+    try:
+        from scipy.ndimage import zoom
+    except ImportError as e:
+        raise RuntimeError("slices whose size differs from patch_size are resampled on the host with scipy.ndimage.zoom: scipy is not importable") from e
+    return zoom
+
+
+def _predict_volume(image, net, patch_size, mode, batch_size):
+    """The slices of image [D][H][W] (or one [H][W] image) through net.eval() under no_grad in batches -> uint8 label volume of the same shape.
+    `mode(outs)` picks the maps and the combination for predict_labels."""
+    _need_gpu(image)
+    net.eval()
+    x = image.float()
+    if x.dim() == 2:
+        with torch.no_grad():
+            return mode(net(x[None, None].contiguous()), True)[0]
+    D, H, W = x.shape
+    ph, pw = int(patch_size[0]), int(patch_size[1])
+    resample = (H, W) != (ph, pw)
+    if resample:          # utils.py:179-181,197-198: order 3 going in, order 0 coming out, on the host as the reference does
+        import numpy as np
+        zoom = _zoom()
+        xs = x.cpu().numpy()
+        x = torch.from_numpy(np.stack([zoom(s, (ph / H, pw / W), order=3) for s in xs])).float().to(image.device)
+    preds = []
+    with torch.no_grad():
+        for i in range(0, D, batch_size):
+            preds.append(mode(net(x[i:i + batch_size, None].contiguous()), False))
+    pred = torch.cat(preds)
+    if resample:
+        ps = pred.cpu().numpy()
+        pred = torch.from_numpy(np.stack([zoom(s, (H / ph, W / pw), order=0) for s in ps])).to(image.device)
+    return pred
+
+
+def test_single_volume(image, label, net, classes, patch_size=[256, 256], use_dual=None, batch_size=16):
+    """utils.py:165-246 without the plotting / saving arguments: image, label [1][D][H][W] (or [1][H][W]) GPU tensors -> the list of
+    (dice, hd95, jaccard, asd) for the classes 1 .. classes-1.  Dual models are combined as sum of the four foreground maps, others take the last map;
+    a single 2-D image takes the last map whatever use_dual says, as the reference does (:224-231).  One net call per batch of slices."""
+    image, label = image.squeeze(0), label.squeeze(0)
+
+    def mode(outs, single_image):
+        return predict_labels(outs[:4], "sum_fg") if use_dual and not single_image else predict_labels(outs[-1:], "last")
+    pred = _predict_volume(image, net, patch_size, mode, batch_size)
+    return volume_metrics(pred, label, classes)
+
+
+def val_single_volume(image, label, net, classes, patch_size=[256, 256], use_dual=False, batch_size=16):
+    """utils.py:248-301: the in-training validation -> the list of Dice values for the classes 1 .. classes-1.  Dual models are combined as
+    sum of (foreground - background) over the four map pairs, others take the last map."""
+    image, label = image.squeeze(0), label.squeeze(0)
+
+    def mode(outs, single_image):
+        return predict_labels(list(outs[:4]) + list(outs[-4:]), "sum_fg_minus_bg") if use_dual else predict_labels(outs[-1:], "last")
+    pred = _predict_volume(image, net, patch_size, mode, batch_size)
+    return volume_dice(pred, label, classes)
