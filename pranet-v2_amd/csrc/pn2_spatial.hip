@@ -49,8 +49,11 @@ __global__ __launch_bounds__(256) void maxpool_fwd_k(const T* __restrict__ x, in
         const int cv = (int)(idx % CV); unsigned p = idx / CV;
         const int ox = (int)(p % OW); p /= OW; const int oy = (int)(p % OH); const int n = (int)(p / OH);
         float best[W]; int bi[W];
+        // a window whose in-image taps are all -inf keeps this index: its first in-image tap, as torch names it (tap 0 lies outside the image in the
+        // top row and left column of windows, and the backward would drop that window's gradient)
+        const int first = (oy == 0 ? 3 : 0) + (ox == 0 ? 1 : 0);
 #pragma unroll
-        for (int e = 0; e < W; ++e) { best[e] = -INFINITY; bi[e] = 0; }
+        for (int e = 0; e < W; ++e) { best[e] = -INFINITY; bi[e] = first; }
         for (int r = 0; r < 3; ++r) {
             const int iy = oy * 2 - 1 + r; if ((unsigned)iy >= (unsigned)H) continue;
             for (int s = 0; s < 3; ++s) {

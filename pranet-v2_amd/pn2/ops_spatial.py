@@ -112,6 +112,16 @@ class SpatialOps:
             rows_ok = x.dt == F32 and x.Cp <= 16 and gy.stride(2) == x.Cp and OW * x.Cp <= 8192 and os.environ.get('PN2_BL_ROWS', '1') == '1'
             if OH >= 4 * H and OW >= 4 * W and x.Cp >= (4 if x.dt == F32 else 8) and not rows_ok:
                 # separable adjoint: reduce along x first, then along y (keeps per-thread loops short)
+                if x.dt == BF16:
+                    # the pair runs in fp32 and rounds once at the end: a bf16 intermediate is summed again over ~scale rows whose weights add up to the scale,
+                    # and where those rows cancel its rounding was tens of bf16 ulps of the result (no shipped model takes this route: the magnified maps are
+                    # the fp32 K-channel heads)
+                    g32, tmp, d32 = self.empty(N, OH, OW, x.Cp, F32), self.empty(N, OH, W, x.Cp, F32), self.empty(N, H, W, x.Cp, F32)
+                    call.pn2_copy(BF16, _p(gy), gy.stride(2), F32, _p(g32), x.Cp, N * OH * OW, x.Cp, 0, st)
+                    call.pn2_bilinear_bwd(F32, _p(g32), x.Cp, _p(tmp), x.Cp, N, OH, W, x.Cp, OH, OW, ac, 1.0, rw, 0, st)
+                    call.pn2_bilinear_bwd(F32, _p(tmp), x.Cp, _p(d32), x.Cp, N, H, W, x.Cp, OH, W, ac, rh, 1.0, 0, st)
+                    call.pn2_copy(F32, _p(d32), x.Cp, BF16, _p(gx), gx.stride(2), N * H * W, x.Cp, acc, st)
+                    return
                 tmp = self.empty(N, OH, W, x.Cp, x.dt)
                 call.pn2_bilinear_bwd(x.dt, _p(gy), gy.stride(2), _p(tmp), x.Cp, N, OH, W, x.Cp, OH, OW, ac, 1.0, rw, 0, st)
                 call.pn2_bilinear_bwd(x.dt, _p(tmp), x.Cp, _p(gx), gx.stride(2), N, H, W, x.Cp, OH, W, ac, rh, 1.0, acc, st)
