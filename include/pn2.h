@@ -561,6 +561,28 @@ int pn2_resize_u8_pass(const unsigned char* src, unsigned char* dst, int H, int 
                        const int* xmin_dev, const int* count_dev, const int* kk_dev, int ksize, void* stream);
 int pn2_u8_to_tensor(const unsigned char* src, float* dst_chw, int H, int W, int C, const float* mean_dev, const float* std_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- Synapse slice transform
+ * multiclass_seg/EMCAD/utils/dataset_synapse.py:12-47 (RandomGenerator) and utils/utils.py:179-181,197-198 (test_single_volume) on device [N][H][W] batches,
+ * bit for bit with scipy.ndimage at its defaults (mode='constant', cval=0, prefilter=True, grid_mode=False).  Every axis <= 1024 (-2 beyond).
+ * pn2_zoom_tables is HOST code: the tables of one axis in double as ni_interpolation.c computes them - order 3: idx[nout][4] (taps folded by mirror),
+ *   w[nout][4], valid[nout]; order 0: idx[nout], valid[nout] (w unused).  valid = 0 where the coordinate o * ((nin-1)/(nout-1)) exceeds nin-1: scipy writes cval
+ *   there (the last row and column of 512 -> 224).  pn2_zoom_pole_pow is HOST code too: z^(n-1) of the cubic pole with the C library's pow.
+ * pn2_zoom_prefilter: fp32 [N][H][W] -> the float64 B-spline coefficients [N][H][W] at the start of `work` (pn2_zoom_workspace bytes), axis 0 then axis 1.
+ * pn2_zoom3_gather: coefficients + DEVICE copies of the order-3 tables of both axes -> fp32 [N][OH][OW].  pn2_zoom0: nearest sample with the order-0 tables.
+ * pn2_rotate0: ndimage.rotate(order=0, reshape=False); m6_dev [N][6] doubles = { m00, m01, m10, m11, off0, off1 } of every sample.
+ * pn2_rot_flip: np.flip(np.rot90(a, k), axis) of square [S][S] samples, kaxis_dev [N][2] ints = { k, axis } (axis -1: no flip).
+ * elem: bytes per element, 1 (uint8) or 4 (fp32); -3 otherwise. */
+int pn2_zoom_tables(int nin, int nout, int order, int* idx, double* w, int* valid);
+int pn2_zoom_pole_pow(int n, double* zn);
+int pn2_zoom_workspace(int N, int H, int W, long long* bytes);
+int pn2_zoom_prefilter(const float* src, int N, int H, int W, void* work, void* stream);
+int pn2_zoom3_gather(const double* coef, int N, int H, int W, int OH, int OW, const int* iy_dev, const double* wy_dev, const int* vy_dev, const int* ix_dev,
+                     const double* wx_dev, const int* vx_dev, float* out, void* stream);
+int pn2_zoom0(int elem, const void* src, int N, int H, int W, int OH, int OW, const int* iy_dev, const int* vy_dev, const int* ix_dev, const int* vx_dev, void* out,
+              void* stream);
+int pn2_rotate0(int elem, const void* src, int N, int H, int W, const double* m6_dev, void* out, void* stream);
+int pn2_rot_flip(int elem, const void* src, int N, int S, const int* kaxis_dev, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -270,6 +270,14 @@ SIGNATURES = {
     "pn2_seg_surface_workspace": [I, I, I, I, C.POINTER(LL)],
     "pn2_seg_surface_hist_len": [I, I, I],
     "pn2_seg_surface_hist": [P, P, I, I, I, I, I, P, P, P, P],
+    "pn2_zoom_tables": [I, I, I, P, P, P],
+    "pn2_zoom_pole_pow": [I, P],
+    "pn2_zoom_workspace": [I, I, I, C.POINTER(LL)],
+    "pn2_zoom_prefilter": [P, I, I, I, P, P],
+    "pn2_zoom3_gather": [P, I, I, I, I, I, P, P, P, P, P, P, P, P],
+    "pn2_zoom0": [I, P, I, I, I, I, I, P, P, P, P, P, P],
+    "pn2_rotate0": [I, P, I, I, I, P, P, P],
+    "pn2_rot_flip": [I, P, I, I, P, P, P],
 }
 # entry points that return a value rather than a status
 _VALUE_FUNCS = {"pn2_copy_job_blocks", "pn2_conv_gemm_tile", "pn2_conv_gemm_job_blocks", "pn2_bn_finalize_job_blocks", "pn2_affine_job_blocks", "pn2_bn_bwd_finalize_job_blocks",

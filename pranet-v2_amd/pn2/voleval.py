@@ -8,6 +8,7 @@ import torch
 
 from .capi import call
 from .core import _p, _stream
+from .volinput import zoom
 
 MODES = {"last": 0, "sum_fg": 1, "sum_fg_minus_bg": 2}
 MAX_AXIS = 1024
@@ -139,17 +140,10 @@ def volume_dice(pred, label, classes):
     return out
 
 
-def _zoom():
-    try:
-        from scipy.ndimage import zoom
-    except ImportError as e:
-        raise RuntimeError("slices whose size differs from patch_size are resampled on the host with scipy.ndimage.zoom: scipy is not importable") from e
-    return zoom
-
-
 def _predict_volume(image, net, patch_size, mode, batch_size):
     """The slices of image [D][H][W] (or one [H][W] image) through net.eval() under no_grad in batches -> uint8 label volume of the same shape.
-    `mode(outs)` picks the maps and the combination for predict_labels."""
+    `mode(outs)` picks the maps and the combination for predict_labels.  Slices whose size differs from patch_size are resampled as the reference does
+    (utils.py:179-181,197-198) - scipy's zoom of order 3 going in, of order 0 coming out - on the device, batch by batch (pn2/volinput.py)."""
     _need_gpu(image)
     net.eval()
     x = image.float()
@@ -158,21 +152,12 @@ def _predict_volume(image, net, patch_size, mode, batch_size):
             return mode(net(x[None, None].contiguous()), True)[0]
     D, H, W = x.shape
     ph, pw = int(patch_size[0]), int(patch_size[1])
-    resample = (H, W) != (ph, pw)
-    if resample:          # utils.py:179-181,197-198: order 3 going in, order 0 coming out, on the host as the reference does
-        import numpy as np
-        zoom = _zoom()
-        xs = x.cpu().numpy()
-        x = torch.from_numpy(np.stack([zoom(s, (ph / H, pw / W), order=3) for s in xs])).float().to(image.device)
     preds = []
     with torch.no_grad():
         for i in range(0, D, batch_size):
-            preds.append(mode(net(x[i:i + batch_size, None].contiguous()), False))
-    pred = torch.cat(preds)
-    if resample:
-        ps = pred.cpu().numpy()
-        pred = torch.from_numpy(np.stack([zoom(s, (H / ph, W / pw), order=0) for s in ps])).to(image.device)
-    return pred
+            xb = zoom(x[i:i + batch_size], (ph, pw), 3)
+            preds.append(zoom(mode(net(xb[:, None].contiguous()), False), (H, W), 0))
+    return torch.cat(preds)
 
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], use_dual=None, batch_size=16):
