@@ -109,6 +109,15 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+template <int CTRL> __device__ __forceinline__ float dpp_f(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+// sum over the 16 lanes of a DPP row by rotations (row_ror:8/4/2/1 fold into v_add_f32_dpp - no LDS permutes); every lane gets the total
+__device__ __forceinline__ float row16_sum(float v) {
+    v += dpp_f<0x128>(v); v += dpp_f<0x124>(v); v += dpp_f<0x122>(v); v += dpp_f<0x121>(v);
+    return v;
+}
+
 // PyTorch upsample_bilinear2d index math (area_pixel_compute_source_index), shared by pn2_spatial.hip and the fused DSRA tail:
 //   align_corners: src = r*dst ; else src = max(r*(dst+0.5)-0.5, 0) ; i0 = (int)src ; i1 = i0 + (i0 < In-1) ; l1 = src - i0.
 __device__ __forceinline__ void bl_src(int o, float r, int ac, int In, int& i0, int& i1, float& l0, float& l1) {

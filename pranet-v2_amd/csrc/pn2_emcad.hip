@@ -620,15 +620,73 @@ __global__ __launch_bounds__(256) void sigmoid_bwd_k(const float* __restrict__ d
 // One pass over the 8 K-channel maps (NHWC fp32): a thread keeps its pixel's 8*K logits in registers and walks the 15 subsets; the per-subset
 // sums (CE, BCE, per-class intersect and sum p^2) are reduced per wave and written as partial rows.  The backward recomputes the softmaxes.
 constexpr int ML_NS = 15;
-template <int CTRL> __device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+// row layouts of `partial` / `sums`: W values per subset, then the label histogram T[K]
+template <int K> struct MLW { static constexpr int W = 2 + 2 * K, NV = ML_NS * W + K; };      // dual: CE, BCE, I[K], Z[K]
+template <int K> struct SLW { static constexpr int W = 1 + 2 * K, NV = ML_NS * W + K; };      // single supervision: CE, I[K], Z[K]
+
+// ---- the softmax CE + Dice core of one subset at one pixel, shared by the dual (mloss_*) and the single-supervision (sloss_*) kernels.  z: the subset's summed logits
+// mx = max_k z[k], e[k] = exp(z[k] - mx); returns sum_k e[k]
+template <int K>
+__device__ __forceinline__ float exp_shifted(const float (&z)[K], float (&e)[K], float& mx) {
+    mx = z[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
+    float se = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { e[k] = __expf(z[k] - mx); se += e[k]; }
+    return se;
 }
-// sum over the 16 lanes of a DPP row by rotations (row_ror:8/4/2/1 fold into v_add_f32_dpp - no LDS permutes); every lane gets the total
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_f<0x128>(v); v += dpp_f<0x124>(v); v += dpp_f<0x122>(v); v += dpp_f<0x121>(v);
-    return v;
+
+// forward: returns CE at the label; I[k] = p_k at the label (else 0), Z[k] = p_k^2
+template <int K>
+__device__ __forceinline__ float ce_dice_fwd(const float (&z)[K], int lab, float* I, float* Z) {
+    float mx, e[K];
+    const float se = exp_shifted<K>(z, e, mx);
+    const float inv = __builtin_amdgcn_rcpf(se), lse = mx + __logf(se);
+    float ce = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float pk = e[k] * inv;
+        if (lab == k) ce = lse - z[k];
+        I[k] = (lab == k) ? pk : 0.f;
+        Z[k] = pk * pk;
+    }
+    return ce;
 }
-template <int K> struct MLW { static constexpr int W = 2 + 2 * K; };      // values per subset: CE, BCE, I[K], Z[K]
+
+// the Dice coefficients of every (subset, class) - uniform over the pixels - once per block in LDS (as 270 global loads per thread the compiler hoisted them all
+// to the top of a fully unrolled subset loop: 256 + 256 registers and scratch).  W: values per subset of `sums`, oI: column of I[0] (Z follows I); the caller syncs
+template <int K>
+__device__ __forceinline__ void dice_coef(const float* __restrict__ sums, int W, int oI, float wdice, float* tA, float* tB) {
+    for (int j = threadIdx.x; j < ML_NS * K; j += 256) {
+        const int s0 = j / K, k = j - s0 * K;
+        const float* S = sums + s0 * W + oI;
+        // d dice_k / d p_k = -(2 t / D - (2 I + eps) 2 p / D^2),  D = Z + T + eps
+        const float D = S[K + k] + sums[ML_NS * W + k] + 1e-5f;
+        tA[j] = wdice * 2.f / D; tB[j] = wdice * (2.f * S[k] + 1e-5f) * 2.f / (D * D);
+    }
+}
+
+// backward, per class: d Dice / d p_k from the subset's Dice coefficients (a: tA at the label, else 0; b: tB), then dz_k = d(wce * CE + Dice) / d z_k through the
+// softmax Jacobian (dot = sum_k g_k p_k).  The loop over the classes stays in the kernels: with its conditional LDS reads inside a helper the compiler contracts
+// other multiply-adds and the kernels take 2 - 12 registers more
+__device__ __forceinline__ float dice_dp(float a, float b, float p) { return -(a - b * p); }
+__device__ __forceinline__ float ce_dice_dz(float p, bool hit, float g, float dot, float wce) { return wce * (p - (hit ? 1.f : 0.f)) + p * (g - dot); }
+
+// group rows -> sh[NV] (double) and sums[NV], by the finalize kernels' one block; the caller syncs
+__device__ __forceinline__ void group_sums(const double* __restrict__ grp, int ngrp, int NV, double* sh, float* __restrict__ sums) {
+    for (int j = threadIdx.x; j < NV; j += blockDim.x) {
+        double a = 0.0;
+        for (int r = 0; r < ngrp; ++r) a += grp[(size_t)r * NV + j];
+        sh[j] = a; sums[j] = (float)a;
+    }
+}
+// sum over the classes of the Dice loss of one subset; oI, oZ: the subset's columns of sh, oT: the label histogram's
+__device__ __forceinline__ double dice_sum(const double* sh, int K, int oI, int oZ, int oT) {
+    double dice = 0.0;
+    for (int k = 0; k < K; ++k) dice += 1.0 - (2.0 * sh[oI + k] + 1e-5) / (sh[oZ + k] + sh[oT + k] + 1e-5);
+    return dice;
+}
 
 struct ml_maps { const float* fg[4]; const float* bg[4]; float* dfg[4]; float* dbg[4]; };
 
@@ -670,22 +728,7 @@ __global__ __launch_bounds__(256) void mloss_fwd_k(ml_maps m, const long long* _
 #pragma unroll
             for (int i = 0; i < 4; ++i) if (s >> i & 1) z[k] += f[i][k];
         }
-        float mx = z[0];
-#pragma unroll
-        for (int k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
-        float se = 0.f, e[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) { e[k] = __expf(z[k] - mx); se += e[k]; }
-        const float inv = __builtin_amdgcn_rcpf(se), lse = mx + __logf(se);
-        float ce = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float pk = e[k] * inv;
-            if (lab == k) ce = lse - z[k];
-            v[2 + k] = (lab == k) ? pk : 0.f;
-            v[2 + K + k] = pk * pk;
-        }
-        v[0] = ce; v[1] = 0.f;
+        v[0] = ce_dice_fwd<K>(z, lab, v + 2, v + 2 + K); v[1] = 0.f;
 #pragma unroll
         for (int j = 0; j < W; ++j) if (j != 1) v[j] = row16_sum(ok ? v[j] : 0.f);
         if (rlead) {
@@ -728,11 +771,10 @@ __global__ __launch_bounds__(256) void mloss_fwd_k(ml_maps m, const long long* _
     }
 }
 
-// partial rows -> ML_RG group rows in double (every group sums a contiguous range of block rows, 4 independent chains per thread)
+// partial rows of either loss -> up to ML_RG group rows in double (every group sums a contiguous range of block rows, 4 independent chains per thread; the row
+// width comes at run time: not hot)
 constexpr int ML_RG = 128;
-template <int K>
-__global__ __launch_bounds__(256) void mloss_reduce_k(const float* __restrict__ partial, int nblk, double* __restrict__ grp) {
-    constexpr int NV = ML_NS * MLW<K>::W + K;
+__global__ __launch_bounds__(256) void loss_reduce_k(const float* __restrict__ partial, int nblk, int NV, double* __restrict__ grp) {
     const int rb = (nblk + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * rb, r1 = min(nblk, r0 + rb);
     for (int j = threadIdx.x; j < NV; j += 256) {
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
@@ -749,20 +791,15 @@ __global__ __launch_bounds__(256) void mloss_reduce_k(const float* __restrict__ 
 // sums[ML_NS*W + K] (double-accumulated over the group rows) and the scalar loss
 template <int K>
 __global__ void mloss_finalize_k(const double* __restrict__ grp, int ngrp, float* __restrict__ sums, float* __restrict__ loss, double npix, float lc1, float lc2, float lc3) {
-    constexpr int W = MLW<K>::W, NV = ML_NS * W + K;
+    constexpr int W = MLW<K>::W, NV = MLW<K>::NV;
     __shared__ double sh[NV];
-    for (int j = threadIdx.x; j < NV; j += blockDim.x) {
-        double a = 0.0;
-        for (int r = 0; r < ngrp; ++r) a += grp[(size_t)r * NV + j];
-        sh[j] = a; sums[j] = (float)a;
-    }
+    group_sums(grp, ngrp, NV, sh, sums);
     __syncthreads();
     if (threadIdx.x == 0) {
         double tot = 0.0;
         for (int s = 0; s < ML_NS; ++s) {
             const double ce = sh[s * W] / npix, bce = sh[s * W + 1] / (npix * K);
-            double dice = 0.0;
-            for (int k = 0; k < K; ++k) dice += 1.0 - (2.0 * sh[s * W + 2 + k] + 1e-5) / (sh[s * W + 2 + K + k] + sh[ML_NS * W + k] + 1e-5);
+            const double dice = dice_sum(sh, K, s * W + 2, s * W + 2 + K, ML_NS * W);
             tot += lc1 * ce + lc2 * dice / K + lc3 * bce;
         }
         loss[0] = (float)tot;
@@ -776,18 +813,8 @@ __global__ void mloss_finalize_k(const double* __restrict__ grp, int ngrp, float
 template <int K>
 __global__ __launch_bounds__(256) void mloss_bwd_k(ml_maps m, const long long* __restrict__ label, const float* __restrict__ bgm, size_t NP, size_t HW,
                                                    const float* __restrict__ sums, float gscale, float lc1, float lc2, float lc3) {
-    constexpr int W = MLW<K>::W;
-    // the Dice coefficients of every (subset, class) - uniform over the pixels - once per block in LDS: as 270 global loads per thread the compiler hoisted them
-    // all to the top of the fully unrolled subset loop (256 + 256 registers and scratch)
     __shared__ float tA[ML_NS * K], tB[ML_NS * K];
-    const float wdice = gscale * lc2 / K;
-    for (int j = threadIdx.x; j < ML_NS * K; j += 256) {
-        const int s0 = j / K, k = j - s0 * K;
-        const float* S = sums + s0 * W;
-        // d dice_k / d p_k = -(2 t / D - (2 I + eps) 2 p / D^2),  D = Z + T + eps
-        const float D = S[2 + K + k] + sums[ML_NS * W + k] + 1e-5f;
-        tA[j] = wdice * 2.f / D; tB[j] = wdice * (2.f * S[2 + k] + 1e-5f) * 2.f / (D * D);
-    }
+    dice_coef<K>(sums, MLW<K>::W, 2, gscale * lc2 / K, tA, tB);
     __syncthreads();
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= NP) return;
@@ -806,22 +833,17 @@ __global__ __launch_bounds__(256) void mloss_bwd_k(ml_maps m, const long long* _
             float z[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) z[k] = ((w0 * f[0][k] + w1 * f[1][k]) + w2 * f[2][k]) + w3 * f[3][k];
-            float mx = z[0];
-#pragma unroll
-            for (int k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
-            float se = 0.f, pr[K], g[K], dot = 0.f;
-#pragma unroll
-            for (int k = 0; k < K; ++k) { pr[k] = __expf(z[k] - mx); se += pr[k]; }
-            const float inv = __builtin_amdgcn_rcpf(se);
+            float mx, pr[K], g[K], dot = 0.f;
+            const float inv = __builtin_amdgcn_rcpf(exp_shifted<K>(z, pr, mx));
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 pr[k] *= inv;
-                g[k] = -((lab == k ? tA[(s - 1) * K + k] : 0.f) - tB[(s - 1) * K + k] * pr[k]);
+                g[k] = dice_dp(lab == k ? tA[(s - 1) * K + k] : 0.f, tB[(s - 1) * K + k], pr[k]);
                 dot += g[k] * pr[k];
             }
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                const float dz = wce * (pr[k] - (lab == k ? 1.f : 0.f)) + pr[k] * (g[k] - dot);
+                const float dz = ce_dice_dz(pr[k], lab == k, g[k], dot, wce);
                 gf[0][k] += w0 * dz; gf[1][k] += w1 * dz; gf[2][k] += w2 * dz; gf[3][k] += w3 * dz;
             }
         }
@@ -855,11 +877,9 @@ __global__ __launch_bounds__(256) void mloss_bwd_k(ml_maps m, const long long* _
 // EMCAD/trainer.py:141-153 with utils/utils.py:102-138 (DiceLoss, softmax=True):
 //   loss = sum over the SELECTED non-empty subsets s of the 4 maps of  w_ce * CE(sum_{i in s} P_i, label) + w_dice * Dice(softmax(sum P_i), onehot(label))
 // `subsets` is a 15-bit mask, bit s-1 selects subset s (bit i of s: map i is in the sum): 0x7FFF 'mutation', 0x008B 'deep_supervision', 0x0080 the last map.
-// The foreground half of mloss_*_k as kernels of their own (the dual kernels keep their code and registers), K = 2..9 classes.  The subset loop is rolled:
+// The foreground half of mloss_*_k (the same ce_dice_* core, reduce kernel and Dice term) around kernels of its own, K = 2..9 classes.  The subset loop is rolled:
 // `s` and the mask live in scalar registers, an unselected subset is one scalar branch - no transcendentals, nothing added to any sum or gradient.
 // A map's logits enter a subset sum through a select, not a multiply by 0: a map outside every selected subset cannot leak a NaN / inf into the loss.
-template <int K> struct SLW { static constexpr int W = 1 + 2 * K, NV = ML_NS * W + K; };      // values per subset: CE, I[K], Z[K]; then the label histogram T[K]
-
 struct sl_maps { const float* m[4]; float* d[4]; };
 
 template <int K>
@@ -895,22 +915,7 @@ __global__ __launch_bounds__(256) void sloss_fwd_k(sl_maps m, unsigned subsets, 
         float z[K], v[W];
 #pragma unroll
         for (int k = 0; k < K; ++k) z[k] = (((b0 ? f[0][k] : 0.f) + (b1 ? f[1][k] : 0.f)) + (b2 ? f[2][k] : 0.f)) + (b3 ? f[3][k] : 0.f);
-        float mx = z[0];
-#pragma unroll
-        for (int k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
-        float se = 0.f, e[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) { e[k] = __expf(z[k] - mx); se += e[k]; }
-        const float inv = __builtin_amdgcn_rcpf(se), lse = mx + __logf(se);
-        float ce = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float pk = e[k] * inv;
-            if (lab == k) ce = lse - z[k];
-            v[1 + k] = (lab == k) ? pk : 0.f;
-            v[1 + K + k] = pk * pk;
-        }
-        v[0] = ce;
+        v[0] = ce_dice_fwd<K>(z, lab, v + 1, v + 1 + K);
 #pragma unroll
         for (int j = 0; j < W; ++j) v[j] = row16_sum(ok ? v[j] : 0.f);
         if (rlead) {
@@ -930,58 +935,30 @@ __global__ __launch_bounds__(256) void sloss_fwd_k(sl_maps m, unsigned subsets, 
     }
 }
 
-// partial rows -> group rows in double, as mloss_reduce_k (row width at run time: not hot)
-__global__ __launch_bounds__(256) void sloss_reduce_k(const float* __restrict__ partial, int nblk, int NV, double* __restrict__ grp) {
-    const int rb = (nblk + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * rb, r1 = min(nblk, r0 + rb);
-    for (int j = threadIdx.x; j < NV; j += 256) {
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        int r = r0;
-        for (; r + 3 < r1; r += 4) {
-            a0 += (double)partial[(size_t)r * NV + j]; a1 += (double)partial[(size_t)(r + 1) * NV + j];
-            a2 += (double)partial[(size_t)(r + 2) * NV + j]; a3 += (double)partial[(size_t)(r + 3) * NV + j];
-        }
-        for (; r < r1; ++r) a0 += (double)partial[(size_t)r * NV + j];
-        grp[(size_t)blockIdx.x * NV + j] = (a0 + a1) + (a2 + a3);
-    }
-}
-
 // sums[15 * (1 + 2K) + K] (double-accumulated over the group rows) and the scalar loss over the selected subsets
 __global__ void sloss_finalize_k(const double* __restrict__ grp, int ngrp, int K, unsigned subsets, float* __restrict__ sums, float* __restrict__ loss, double npix,
                                  float w_ce, float w_dice) {
     const int W = 1 + 2 * K, NV = ML_NS * W + K;
     __shared__ double sh[SLW<9>::NV];
-    for (int j = threadIdx.x; j < NV; j += blockDim.x) {
-        double a = 0.0;
-        for (int r = 0; r < ngrp; ++r) a += grp[(size_t)r * NV + j];
-        sh[j] = a; sums[j] = (float)a;
-    }
+    group_sums(grp, ngrp, NV, sh, sums);
     __syncthreads();
     if (threadIdx.x == 0) {
         double tot = 0.0;
         for (int s = 0; s < ML_NS; ++s) {
             if (!(subsets >> s & 1)) continue;
-            double dice = 0.0;
-            for (int k = 0; k < K; ++k) dice += 1.0 - (2.0 * sh[s * W + 1 + k] + 1e-5) / (sh[s * W + 1 + K + k] + sh[ML_NS * W + k] + 1e-5);
+            const double dice = dice_sum(sh, K, s * W + 1, s * W + 1 + K, ML_NS * W);
             tot += w_ce * (sh[s * W] / npix) + w_dice * dice / K;
         }
         loss[0] = (float)tot;
     }
 }
 
-// gradients of the four maps (recomputed softmaxes, Dice coefficients once per block in LDS - see mloss_bwd_k); a map in no selected subset gets exact zeros, written
+// gradients of the four maps (recomputed softmaxes, Dice coefficients once per block in LDS - see dice_coef); a map in no selected subset gets exact zeros, written
 template <int K>
 __global__ __launch_bounds__(256) void sloss_bwd_k(sl_maps m, unsigned subsets, const long long* __restrict__ label, size_t NP, const float* __restrict__ sums,
                                                    float gscale, float w_ce, float w_dice) {
-    constexpr int W = SLW<K>::W;
     __shared__ float tA[ML_NS * K], tB[ML_NS * K];
-    const float wdice = gscale * w_dice / K;
-    for (int j = threadIdx.x; j < ML_NS * K; j += 256) {
-        const int s0 = j / K, k = j - s0 * K;
-        const float* S = sums + s0 * W;
-        // d dice_k / d p_k = -(2 t / D - (2 I + eps) 2 p / D^2),  D = Z + T + eps
-        const float D = S[1 + K + k] + sums[ML_NS * W + k] + 1e-5f;
-        tA[j] = wdice * 2.f / D; tB[j] = wdice * (2.f * S[1 + k] + 1e-5f) * 2.f / (D * D);
-    }
+    dice_coef<K>(sums, SLW<K>::W, 1, gscale * w_dice / K, tA, tB);
     __syncthreads();
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= NP) return;
@@ -999,22 +976,17 @@ __global__ __launch_bounds__(256) void sloss_bwd_k(sl_maps m, unsigned subsets, 
         float z[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) z[k] = (((b0 ? f[0][k] : 0.f) + (b1 ? f[1][k] : 0.f)) + (b2 ? f[2][k] : 0.f)) + (b3 ? f[3][k] : 0.f);
-        float mx = z[0];
-#pragma unroll
-        for (int k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
-        float se = 0.f, pr[K], g[K], dot = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) { pr[k] = __expf(z[k] - mx); se += pr[k]; }
-        const float inv = __builtin_amdgcn_rcpf(se);
+        float mx, pr[K], g[K], dot = 0.f;
+        const float inv = __builtin_amdgcn_rcpf(exp_shifted<K>(z, pr, mx));
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             pr[k] *= inv;
-            g[k] = -((lab == k ? tA[(s - 1) * K + k] : 0.f) - tB[(s - 1) * K + k] * pr[k]);
+            g[k] = dice_dp(lab == k ? tA[(s - 1) * K + k] : 0.f, tB[(s - 1) * K + k], pr[k]);
             dot += g[k] * pr[k];
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const float dz = wce * (pr[k] - (lab == k ? 1.f : 0.f)) + pr[k] * (g[k] - dot);
+            const float dz = ce_dice_dz(pr[k], lab == k, g[k], dot, wce);
             gf[0][k] += b0 ? dz : 0.f; gf[1][k] += b1 ? dz : 0.f; gf[2][k] += b2 ? dz : 0.f; gf[3][k] += b3 ? dz : 0.f;
         }
     }
@@ -1288,7 +1260,16 @@ int pn2_sigmoid_bwd(int dt_out, const float* dy, const float* y, void* dx, int l
 static int ml_blocks(long long npix) { return (int)((npix + 255) / 256); }
 /* rows of the `partial` scratch: one per 256 pixels + the double-precision group rows of the second reduction level */
 int pn2_mutation_loss_blocks(long long npix) { return npix < 1 ? -1 : ml_blocks(npix) + 2 * ML_RG + 1; }
-int pn2_mutation_loss_width(int K) { return K == 9 ? ML_NS * MLW<9>::W + 9 : -1; }
+int pn2_mutation_loss_width(int K) { return K == 9 ? MLW<9>::NV : -1; }
+int pn2_seg_loss_width(int K) { const int wd = with_seg_classes(K, [](auto k) { return SLW<decltype(k)::value>::NV; }); return wd > 0 ? wd : -1; }
+
+/* second reduction level of both losses: the ml_blocks(NP) block rows of `partial` (NV floats each) -> ngrp group rows in double at grp, behind the block rows */
+static int loss_reduce(float* partial, size_t NP, int NV, hipStream_t st, double*& grp, int& ngrp) {
+    const int nblk = ml_blocks((long long)NP);
+    ngrp = nblk < 8 * ML_RG ? (nblk + 7) / 8 : ML_RG;
+    grp = reinterpret_cast<double*>(partial + (((size_t)nblk * NV + 1) & ~(size_t)1));          // 8-byte aligned
+    return pn2_launch<loss_reduce_k>(dim3(ngrp), dim3(256), 0, 0, st, partial, nblk, NV, grp);
+}
 
 /* EMCAD/trainer.py:106-140: sum over the 15 non-empty subsets of the 4 scales of lc1*CE + lc2*Dice(softmax) + lc3*BCEWithLogits on the summed maps.
  * fg[4], bg[4]: [N][H][W][K] fp32 maps (K = 9); label [N][H][W] int64; bg_mask [N][K][H][W] fp32.  partial: [pn2_mutation_loss_blocks][pn2_mutation_loss_width]
@@ -1300,12 +1281,10 @@ int pn2_mutation_loss_fwd(const float* const* fg, const float* const* bg, const 
     ml_maps m;
     for (int i = 0; i < 4; ++i) { m.fg[i] = fg[i]; m.bg[i] = bg[i]; m.dfg[i] = nullptr; m.dbg[i] = nullptr; if (!fg[i] || !bg[i]) return -1; }
     const size_t NP = (size_t)N * HW;
-    const int nblk = ml_blocks((long long)NP), NV = ML_NS * MLW<9>::W + 9;
-    const int ngrp = nblk < 8 * ML_RG ? (nblk + 7) / 8 : ML_RG;
-    double* grp = reinterpret_cast<double*>(partial + (((size_t)nblk * NV + 1) & ~(size_t)1));          // 8-byte aligned, after the block rows
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = pn2_launch<mloss_fwd_k<9>>(dim3(nblk), dim3(256), 0, 0, st, m, label, bg_mask, NP, (size_t)HW, partial)) return rc;
-    if (int rc = pn2_launch<mloss_reduce_k<9>>(dim3(ngrp), dim3(256), 0, 0, st, partial, nblk, grp)) return rc;
+    double* grp; int ngrp;
+    if (int rc = pn2_launch<mloss_fwd_k<9>>(dim3(ml_blocks((long long)NP)), dim3(256), 0, 0, st, m, label, bg_mask, NP, (size_t)HW, partial)) return rc;
+    if (int rc = loss_reduce(partial, NP, MLW<9>::NV, st, grp, ngrp)) return rc;
     return pn2_launch<mloss_finalize_k<9>>(dim3(1), dim3(256), 0, 0, st, grp, ngrp, sums, loss, (double)NP, lc1, lc2, lc3);
 }
 
@@ -1319,8 +1298,6 @@ int pn2_mutation_loss_bwd(const float* const* fg, const float* const* bg, float*
     return pn2_launch<mloss_bwd_k<9>>(dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, m, label, bg_mask, NP, (size_t)HW, sums, gscale, lc1, lc2, lc3);
 }
 
-int pn2_seg_loss_width(int K) { return K >= 2 && K <= 9 ? ML_NS * (1 + 2 * K) + K : -1; }
-
 static bool seg_loss_args_ok(unsigned subsets, int N, long long HW, int K) { return subsets != 0 && subsets <= 0x7FFFu && K >= 2 && K <= 9 && N >= 1 && HW >= 1; }
 
 /* EMCAD/trainer.py:141-153 (single supervision): sum over the subsets selected by `subsets` of w_ce*CE + w_dice*Dice(softmax) on the summed maps.
@@ -1333,13 +1310,11 @@ int pn2_seg_loss_fwd(const float* const* maps, unsigned subsets, const long long
     sl_maps m;
     for (int i = 0; i < 4; ++i) { m.m[i] = maps[i]; m.d[i] = nullptr; if (!maps[i]) return -1; }
     const size_t NP = (size_t)N * HW;
-    const int nblk = ml_blocks((long long)NP), NV = pn2_seg_loss_width(K);
-    const int ngrp = nblk < 8 * ML_RG ? (nblk + 7) / 8 : ML_RG;
-    double* grp = reinterpret_cast<double*>(partial + (((size_t)nblk * NV + 1) & ~(size_t)1));          // 8-byte aligned, after the block rows
     hipStream_t st = (hipStream_t)stream;
+    double* grp; int ngrp;
     if (int rc = with_seg_classes(K, [&](auto k) {
-            return pn2_launch<sloss_fwd_k<decltype(k)::value>>(dim3(nblk), dim3(256), 0, 0, st, m, subsets, label, NP, partial); })) return rc;
-    if (int rc = pn2_launch<sloss_reduce_k>(dim3(ngrp), dim3(256), 0, 0, st, partial, nblk, NV, grp)) return rc;
+            return pn2_launch<sloss_fwd_k<decltype(k)::value>>(dim3(ml_blocks((long long)NP)), dim3(256), 0, 0, st, m, subsets, label, NP, partial); })) return rc;
+    if (int rc = loss_reduce(partial, NP, pn2_seg_loss_width(K), st, grp, ngrp)) return rc;
     return pn2_launch<sloss_finalize_k>(dim3(1), dim3(256), 0, 0, st, grp, ngrp, K, subsets, sums, loss, (double)NP, w_ce, w_dice);
 }
 

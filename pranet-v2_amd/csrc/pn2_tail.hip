@@ -462,15 +462,6 @@ __device__ __forceinline__ float hw_rcp(float x) { return __builtin_amdgcn_rcpf(
 struct tail_band_aux { int poff[PN2_TAIL_MAX_MAPS]; int ptot; int R; int nbn; };
 constexpr int TBM = 2;          // maps per band block: 24 slot accumulators in the backward, every block the same weight
 
-template <int CTRL> __device__ __forceinline__ float tdpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-// sum over the 16 lanes of a DPP row (row_ror:8/4/2/1 fold into v_add_f32_dpp, no LDS permutes); every lane gets the total
-__device__ __forceinline__ float row16_sum(float v) {
-    v += tdpp<0x128>(v); v += tdpp<0x124>(v); v += tdpp<0x122>(v); v += tdpp<0x121>(v);
-    return v;
-}
-
 // XCD-aware work order: workgroup i runs on XCD i % 8, so the groups of one (band, image) take consecutive slots of ONE XCD and share
 // its L2 for the mask / weit rows.  Returns false for the padding blocks of the last 8-wide stripe.
 __device__ __forceinline__ bool tail_band_ids(int ng, int nbn, int nb, int& g, int& band, int& n) {

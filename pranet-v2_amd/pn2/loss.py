@@ -199,6 +199,48 @@ def structure_loss(pred, pred_bg, mask_fg, mask_bg=None):
     return structure_loss_multi([pred], [pred_bg], mask_fg)
 
 
+_PA = C.c_void_p * 4
+
+
+def _ptrs(ts):
+    return _PA(*[t.data_ptr() for t in ts])
+
+
+def _nhwc(maps):
+    return [m.permute(0, 2, 3, 1).float().contiguous() for m in maps]          # no copy for the engine's K-channel output maps
+
+
+def _loss_scratch(npix, wd, new):
+    """partial, sums, loss of one loss launch; new(*shape) allocates fp32: eng.fbuf or _empty_on(device)."""
+    return new(call.pn2_mutation_loss_blocks(npix), wd), new(wd), new(1)
+
+
+def _empty_on(dev):
+    return lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _engine_maps(outs):
+    N, H, W, K = outs[0].N, outs[0].H, outs[0].W, outs[0].C
+    for o in outs:
+        assert o.dt == F32 and o.ld == K and (o.N, o.H, o.W, o.C) == (N, H, W, K)
+    return N, H, W, K
+
+
+def _grad_ptrs(outs):
+    """The maps' gradient buffers, marked as written: the backward kernel fills them."""
+    ptrs = _ptrs([o.grad_buf() for o in outs])
+    for o in outs:
+        o.grad_written = True
+    return ptrs
+
+
+def _mutation_width(K):
+    wd = call.pn2_mutation_loss_width(K)
+    if wd < 0:
+        raise RuntimeError(f"pn2.mutation_loss is built for K = 9 classes (got {K})")
+    return wd
+
+
 class _MutationLoss(torch.autograd.Function):
     """The multi-class dual-supervision loss of EMCAD/trainer.py:106-140 as two kernels (pn2_mutation_loss_fwd / _bwd)."""
 
@@ -207,19 +249,11 @@ class _MutationLoss(torch.autograd.Function):
         if not maps[0].is_cuda:
             raise RuntimeError("pn2.mutation_loss needs GPU tensors (no CPU fallback)")
         N, K, H, W = maps[0].shape
-        nhwc = [m.permute(0, 2, 3, 1).float().contiguous() for m in maps]          # no copy for the engine's K-channel output maps
+        nhwc = _nhwc(maps)
         lab = label.long().contiguous()
         bgm = bg_mask.float().contiguous()
-        nb, wd = call.pn2_mutation_loss_blocks(N * H * W), call.pn2_mutation_loss_width(K)
-        if wd < 0:
-            raise RuntimeError(f"pn2.mutation_loss is built for K = 9 classes (got {K})")
-        dev = maps[0].device
-        partial = torch.empty((nb, wd), dtype=torch.float32, device=dev)
-        sums = torch.empty(wd, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        PA = C.c_void_p * 4
-        fg, bg = PA(*[t.data_ptr() for t in nhwc[:4]]), PA(*[t.data_ptr() for t in nhwc[4:]])
-        call.pn2_mutation_loss_fwd(fg, bg, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(partial), _p(sums), _p(loss), _stream())
+        partial, sums, loss = _loss_scratch(N * H * W, _mutation_width(K), _empty_on(maps[0].device))
+        call.pn2_mutation_loss_fwd(_ptrs(nhwc[:4]), _ptrs(nhwc[4:]), _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(partial), _p(sums), _p(loss), _stream())
         ctx.save_for_backward(lab, bgm, sums, *nhwc)
         ctx.meta = (N, K, H, W, lc)
         return loss[0]
@@ -229,34 +263,24 @@ class _MutationLoss(torch.autograd.Function):
         lab, bgm, sums, *nhwc = ctx.saved_tensors
         N, K, H, W, lc = ctx.meta
         grads = [torch.empty_like(t) for t in nhwc]
-        PA = C.c_void_p * 4
-        fg, bg = PA(*[t.data_ptr() for t in nhwc[:4]]), PA(*[t.data_ptr() for t in nhwc[4:]])
-        dfg, dbg = PA(*[t.data_ptr() for t in grads[:4]]), PA(*[t.data_ptr() for t in grads[4:]])
-        call.pn2_mutation_loss_bwd(fg, bg, dfg, dbg, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(sums), 1.0, _stream())
+        call.pn2_mutation_loss_bwd(_ptrs(nhwc[:4]), _ptrs(nhwc[4:]), _ptrs(grads[:4]), _ptrs(grads[4:]), _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2],
+                                   _p(sums), 1.0, _stream())
         return (None, None, None, *[(gr * g).permute(0, 3, 1, 2) for gr in grads])
 
 
 def mutation_forward_backward(eng, outs, label, bg_mask, lc=(0.5, 0.7, 0.3), gscale=1.0):
     """Trainer path of the same loss: `outs` are the engine's 8 fp32 [N][H][W][K] maps; the loss kernel reads them in place and the backward
     kernel writes their gradients straight into the activations' gradient buffers (no autograd bridge, no copies).  Returns loss[1]."""
-    N, H, W, K = outs[0].N, outs[0].H, outs[0].W, outs[0].C
-    for o in outs:
-        assert o.dt == F32 and o.ld == K and (o.N, o.H, o.W, o.C) == (N, H, W, K)
-    nb, wd = call.pn2_mutation_loss_blocks(N * H * W), call.pn2_mutation_loss_width(K)
-    if wd < 0:
-        raise RuntimeError(f"pn2.mutation_loss is built for K = 9 classes (got {K})")
+    N, H, W, K = _engine_maps(outs)
+    wd = _mutation_width(K)
     lab = label.long().contiguous()
     bgm = bg_mask.float().contiguous()
-    partial, sums, loss = eng.fbuf(nb, wd), eng.fbuf(wd), eng.fbuf(1)
-    PA = C.c_void_p * 4
-    fg, bg = PA(*[o.t.data_ptr() for o in outs[:4]]), PA(*[o.t.data_ptr() for o in outs[4:]])
+    partial, sums, loss = _loss_scratch(N * H * W, wd, eng.fbuf)
+    fg, bg = _ptrs([o.t for o in outs[:4]]), _ptrs([o.t for o in outs[4:]])
     st = _stream()
     call.pn2_mutation_loss_fwd(fg, bg, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(partial), _p(sums), _p(loss), st)
-    grads = [o.grad_buf() for o in outs]
-    dfg, dbg = PA(*[g.data_ptr() for g in grads[:4]]), PA(*[g.data_ptr() for g in grads[4:]])
+    dfg, dbg = _grad_ptrs(outs[:4]), _grad_ptrs(outs[4:])
     call.pn2_mutation_loss_bwd(fg, bg, dfg, dbg, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(sums), float(gscale), st)
-    for o in outs:
-        o.grad_written = True
     eng.keep_alive = (lab, bgm)
     return loss
 
@@ -296,14 +320,10 @@ class _SegLoss(torch.autograd.Function):
             raise ValueError(f"pn2.seg_loss takes the 4 maps of EMCADNet (got {len(maps)})")
         N, K, H, W = maps[0].shape
         wd = _seg_width(K)
-        nhwc = [m.permute(0, 2, 3, 1).float().contiguous() for m in maps]          # no copy for the engine's K-channel output maps
+        nhwc = _nhwc(maps)
         lab = label.long().contiguous()
-        dev = maps[0].device
-        partial = torch.empty((call.pn2_mutation_loss_blocks(N * H * W), wd), dtype=torch.float32, device=dev)
-        sums = torch.empty(wd, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        PA = C.c_void_p * 4
-        call.pn2_seg_loss_fwd(PA(*[t.data_ptr() for t in nhwc]), subsets, _p(lab), N, H * W, K, w[0], w[1], _p(partial), _p(sums), _p(loss), _stream())
+        partial, sums, loss = _loss_scratch(N * H * W, wd, _empty_on(maps[0].device))
+        call.pn2_seg_loss_fwd(_ptrs(nhwc), subsets, _p(lab), N, H * W, K, w[0], w[1], _p(partial), _p(sums), _p(loss), _stream())
         ctx.save_for_backward(lab, sums, *nhwc)
         ctx.meta = (N, K, H, W, subsets, w)
         return loss[0]
@@ -313,8 +333,7 @@ class _SegLoss(torch.autograd.Function):
         lab, sums, *nhwc = ctx.saved_tensors
         N, K, H, W, subsets, w = ctx.meta
         grads = [torch.empty_like(t) for t in nhwc]
-        PA = C.c_void_p * 4
-        call.pn2_seg_loss_bwd(PA(*[t.data_ptr() for t in nhwc]), PA(*[t.data_ptr() for t in grads]), subsets, _p(lab), N, H * W, K, w[0], w[1], _p(sums), 1.0, _stream())
+        call.pn2_seg_loss_bwd(_ptrs(nhwc), _ptrs(grads), subsets, _p(lab), N, H * W, K, w[0], w[1], _p(sums), 1.0, _stream())
         return (None, None, None, *[(gr * g).permute(0, 3, 1, 2) for gr in grads])
 
 
@@ -324,20 +343,14 @@ def seg_forward_backward(eng, outs, label, supervision="mutation", weights=(0.3,
     subsets = _seg_subsets(supervision)
     if len(outs) != 4:
         raise ValueError(f"pn2.seg_loss takes the 4 maps of EMCADNet (got {len(outs)})")
-    N, H, W, K = outs[0].N, outs[0].H, outs[0].W, outs[0].C
-    for o in outs:
-        assert o.dt == F32 and o.ld == K and (o.N, o.H, o.W, o.C) == (N, H, W, K)
+    N, H, W, K = _engine_maps(outs)
     wd = _seg_width(K)
     lab = label.long().contiguous()
-    partial, sums, loss = eng.fbuf(call.pn2_mutation_loss_blocks(N * H * W), wd), eng.fbuf(wd), eng.fbuf(1)
-    PA = C.c_void_p * 4
-    maps = PA(*[o.t.data_ptr() for o in outs])
+    partial, sums, loss = _loss_scratch(N * H * W, wd, eng.fbuf)
+    maps = _ptrs([o.t for o in outs])
     st = _stream()
     call.pn2_seg_loss_fwd(maps, subsets, _p(lab), N, H * W, K, float(weights[0]), float(weights[1]), _p(partial), _p(sums), _p(loss), st)
-    dmaps = PA(*[o.grad_buf().data_ptr() for o in outs])
-    call.pn2_seg_loss_bwd(maps, dmaps, subsets, _p(lab), N, H * W, K, float(weights[0]), float(weights[1]), _p(sums), float(gscale), st)
-    for o in outs:
-        o.grad_written = True
+    call.pn2_seg_loss_bwd(maps, _grad_ptrs(outs), subsets, _p(lab), N, H * W, K, float(weights[0]), float(weights[1]), _p(sums), float(gscale), st)
     eng.keep_alive = (lab,)
     return loss
 
