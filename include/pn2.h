@@ -545,6 +545,18 @@ int pn2_eval_wfm(const unsigned char* pred_u8, const float* gt, int H, int W, co
  *   Euclidean distance d2 (exact, in voxels); hist has pn2_seg_surface_hist_len(D, H, W) = (D-1)^2 + (H-1)^2 + (W-1)^2 + 1 entries, counts2 = { border voxels of A,
  *   of B }; both overwritten.  Every axis <= 1024.  work: pn2_seg_surface_workspace(...) bytes of scratch.  A class missing from B leaves the histogram empty. */
 int pn2_seg_labels(const float* const* maps, int nmaps, int mode, int N, int K, int H, int W, unsigned char* out, void* stream);
+/* pn2_seg_labels_up: the same labels straight from the LOW-RESOLUTION head maps - bilinear up-sampling, combination and argmax in one launch, nothing at output
+ *   resolution but the byte per pixel (pn2.infer.VolumePredictor).  `maps` is a HOST array of nmaps descriptors of NHWC fp32 maps [N][H][W][ld], ld >= K (the
+ *   channels K .. ld-1 are padding: never used); every map has its own size, with OH = H * s and OW = W * s for ONE integer s >= 1 per map (-2 otherwise, as for
+ *   ld < K, K outside 2..16, nmaps outside 1..8 or odd in mode 2, an unknown mode, N > 65535).  Each map is interpolated as pn2_bilinear_fwd does with
+ *   align_corners = 0 and rh = rw = 1 / s: the same source indices, weights and four-tap expression ly0*(lx0*a + lx1*b) + ly1*(lx0*c + lx1*d) (s = 1: weights 1
+ *   and 0), evaluated as fma(ly0, fma(lx0, a, lx1*b), ly1*fma(lx0, c, lx1*d)) for every channel.  Modes, order of the fp32 sums and the tie / NaN rule are those
+ *   of pn2_seg_labels.  Where the products of the expression are exact the output equals pn2_bilinear_fwd of every map followed by pn2_seg_labels byte for byte
+ *   (a NaN in a map spreads the same way in both); otherwise pn2_bilinear_fwd's value is the compiler's contraction of the expression, within its three
+ *   roundings of this one, and a label can differ where the two largest combined logits are that close.  The channels of a tap are read as 16-byte vectors
+ *   when every ld is a multiple of 4 and every base 16-byte aligned, as scalars otherwise: the same bits either way. */
+typedef struct { const float* p; int ld; int H, W; } pn2_seg_up_map;   /* NHWC fp32: channel k of pixel (n,y,x) at p[((n*H + y)*W + x)*ld + k], ld >= K */
+int pn2_seg_labels_up(const pn2_seg_up_map* maps, int nmaps, int mode, int N, int K, int OH, int OW, unsigned char* out /* [N][OH][OW] */, void* stream);
 int pn2_seg_counts(const unsigned char* pred, const unsigned char* gt, long long n, int K, unsigned long long* counts, void* stream);
 int pn2_seg_surface_workspace(int D, int H, int W, int ndim, long long* bytes);
 int pn2_seg_surface_hist_len(int D, int H, int W);          /* value; -1 outside the range */

@@ -49,6 +49,84 @@ __global__ __launch_bounds__(256) void seg_labels_k(SegMaps maps, int nmaps, int
     }
 }
 
+// ---- labels straight from the low-resolution head maps: bilinear up-sampling (align_corners = 0, scale s = OH / H per map), combination and argmax in one pass
+struct SegUpMaps { const float* p[8]; int ld[8], H[8], W[8]; float r[8]; };          // r = 1 / s, as Engine.bilinear hands it to bilinear_fwd_k
+
+// the four-tap value ly0*(lx0*a + lx1*b) + ly1*(lx0*c + lx1*d) of bilinear_fwd_k (pn2_spatial.hip).  There the compiler chooses which product of each sum is fused into
+// a multiply-add, and chooses differently per instantiation and, after it has packed pairs of channels into v_pk_fma_f32, per channel (its 16-byte and 12-byte forms
+// up-sample the same map to values one rounding apart; the scalar form leaves the outer sum as mul, mul, add) - so no way of writing the expression here reproduces
+// its bits for every map layout.  This kernel pins ONE form for every channel, read path and K: x = fma(lx0, a, lx1*b), y = fma(lx0, c, lx1*d), value =
+// fma(ly0, x, ly1*y).  Where every product and sum is exact all forms agree; elsewhere the value is within the three roundings of the expression of bilinear_fwd_k's.
+__device__ __forceinline__ float seg_tap4(float ly0, float ly1, float lx0, float lx1, float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    const float x = __builtin_fmaf(lx0, a, lx1 * b), y = __builtin_fmaf(lx0, c, lx1 * d);
+    return __builtin_fmaf(ly0, x, ly1 * y);
+}
+
+// v[0 .. 4*KV) = channels of map m at output pixel (n, oy, ox).  Tap offsets and weights once per map; VEC: the channels of a tap as 16-byte vectors (the
+// pad channels up to 4*KV <= ld are read and never used), else scalars below K only
+template <int KV, bool VEC>
+__device__ __forceinline__ void seg_up_pixel(const SegUpMaps& maps, int m, int n, int oy, int ox, int K, float* v) {
+    const int H = maps.H[m], W = maps.W[m], ld = maps.ld[m];
+    const float r = maps.r[m];
+    int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
+    bl_src(oy, r, 0, H, y0, y1, ly0, ly1); bl_src(ox, r, 0, W, x0, x1, lx0, lx1);
+    const float* b = maps.p[m] + (size_t)n * H * W * ld;
+    const float* pa = b + (size_t)(y0 * W + x0) * ld; const float* pb = b + (size_t)(y0 * W + x1) * ld;
+    const float* pc = b + (size_t)(y1 * W + x0) * ld; const float* pd = b + (size_t)(y1 * W + x1) * ld;
+#pragma unroll
+    for (int j = 0; j < KV; ++j) {
+        float ta[4], tb[4], tc[4], td[4];
+        if (VEC) {
+            const f32x4_t va = ((const f32x4_t*)pa)[j], vb = ((const f32x4_t*)pb)[j], vc = ((const f32x4_t*)pc)[j], vd = ((const f32x4_t*)pd)[j];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { ta[e] = va[e]; tb[e] = vb[e]; tc[e] = vc[e]; td[e] = vd[e]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int k = 4 * j + e;
+                const bool in = k < K;
+                ta[e] = in ? pa[k] : 0.f; tb[e] = in ? pb[k] : 0.f; tc[e] = in ? pc[k] : 0.f; td[e] = in ? pd[k] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[4 * j + e] = seg_tap4(ly0, ly1, lx0, lx1, ta[e], tb[e], tc[e], td[e]);
+    }
+}
+
+// one thread per output pixel, a wave = 64 consecutive x of one row, a block = 4 rows; 4*KV >= K running sums in registers, the maps as the outer loop so that every
+// channel adds them in the order of seg_labels_k.  The sums and differences are plain fp32 adds of the rounded up-sampled values (what the unfused path stores and
+// reads back): no contraction of an add into the four-tap expression
+template <int MODE, int KV, bool VEC>
+__global__ __launch_bounds__(256) void seg_labels_up_k(SegUpMaps maps, int nmaps, int K, int OH, int OW, u8* __restrict__ out) {
+    const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6), n = blockIdx.z;
+    if (ox >= OW || oy >= OH) return;
+    float acc[4 * KV];
+    if (MODE == 0) seg_up_pixel<KV, VEC>(maps, nmaps - 1, n, oy, ox, K, acc);
+    else {
+#pragma unroll
+        for (int k = 0; k < 4 * KV; ++k) acc[k] = 0.0f;
+        const int h = nmaps / 2;
+        for (int m = 0; m < (MODE == 1 ? nmaps : h); ++m) {
+            float f[4 * KV], g[4 * KV];
+            seg_up_pixel<KV, VEC>(maps, m, n, oy, ox, K, f);
+            if (MODE == 2) seg_up_pixel<KV, VEC>(maps, h + m, n, oy, ox, K, g);
+            {
+#pragma clang fp contract(off)
+#pragma unroll
+                for (int k = 0; k < 4 * KV; ++k) { if (MODE == 1) acc[k] += f[k]; else acc[k] += (f[k] - g[k]); }
+            }
+        }
+    }
+    float best = 0.f; int bk = 0;
+#pragma unroll
+    for (int k = 0; k < 4 * KV; ++k) {
+        const float v = acc[k];
+        if (k < K && (k == 0 || v > best || (v != v && best == best))) { best = v; bk = k; }
+    }
+    out[((size_t)n * OH + oy) * OW + ox] = (u8)bk;
+}
+
 // cnt[c][0..2] += |pred = c|, |gt = c|, |pred = c and gt = c|: LDS counters per block, then one atomic per non-zero counter
 __global__ __launch_bounds__(256) void seg_counts_k(const u8* __restrict__ pred, const u8* __restrict__ gt, long long n, int K, u64* __restrict__ cnt) {
     __shared__ unsigned sh[256 * 3];
@@ -214,6 +292,33 @@ int pn2_seg_labels(const float* const* maps, int nmaps, int mode, int N, int K, 
     if (mode == 0) hipLaunchKernelGGL(seg_labels_k<0>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
     else if (mode == 1) hipLaunchKernelGGL(seg_labels_k<1>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
     else hipLaunchKernelGGL(seg_labels_k<2>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+int pn2_seg_labels_up(const pn2_seg_up_map* maps, int nmaps, int mode, int N, int K, int OH, int OW, unsigned char* out, void* stream) {
+    if (!maps || !out || N < 1 || OH < 1 || OW < 1) return -1;
+    if (K < 2 || K > 16 || nmaps < 1 || nmaps > 8 || mode < 0 || mode > 2 || (mode == 2 && (nmaps & 1)) || N > 65535 || (OH + 3) / 4 > 65535) return -2;
+    SegUpMaps m = {};
+    bool vec = true;
+    for (int i = 0; i < nmaps; ++i) {
+        const pn2_seg_up_map& s = maps[i];
+        if (!s.p) return -1;
+        if (s.ld < K || s.H < 1 || s.W < 1 || OH % s.H || OW % s.W || OH / s.H != OW / s.W) return -2;
+        m.p[i] = s.p; m.ld[i] = s.ld; m.H[i] = s.H; m.W[i] = s.W;
+        m.r[i] = (float)(1.0 / (double)(OH / s.H));
+        vec = vec && s.ld % 4 == 0 && ((uintptr_t)s.p & 15) == 0;
+    }
+    const dim3 g((OW + 63) / 64, (OH + 3) / 4, N);
+    hipStream_t st = (hipStream_t)stream;
+    auto launch = [&](auto mo, auto kv, auto ve) {
+        hipLaunchKernelGGL((seg_labels_up_k<decltype(mo)::value, decltype(kv)::value, decltype(ve)::value>), g, dim3(256), 0, st, m, nmaps, K, OH, OW, out);
+    };
+    auto with_kv = [&](auto mo, auto ve) {
+        switch ((K + 3) / 4) { case 1: launch(mo, Int<1>{}, ve); break; case 2: launch(mo, Int<2>{}, ve); break; case 3: launch(mo, Int<3>{}, ve); break; default: launch(mo, Int<4>{}, ve); }
+    };
+    auto with_vec = [&](auto mo) { if (vec) with_kv(mo, Bool<true>{}); else with_kv(mo, Bool<false>{}); };
+    if (mode == 0) with_vec(Int<0>{}); else if (mode == 1) with_vec(Int<1>{}); else with_vec(Int<2>{});
     PN2_CHECK_LAUNCH();
     return 0;
 }

@@ -39,19 +39,23 @@ class EMCADNet(nn.Module):
         """Parameters forward() touches: the out_head* convs only serve the single-supervision branch."""
         return [p for n, p in self.named_parameters() if (not self.dual or not n.startswith('out_head')) and (one_channel or not n.startswith('conv.'))]
 
-    def _build(self, eng, x):
-        """forward :101-142: 8 maps (dual) or [p4, p3, p2, p1]"""
+    def _build_lowres(self, eng, x):
+        """forward :101-132 up to the K-class head maps at 1/32, 1/16, 1/8, 1/4 of the input: (the 8 decoder maps (dual) or [p4, p3, p2, p1], their scale factors)"""
         if x.C == 1:
             x = eng.conv_bn_act(x, self.conv[0], self.conv[1], relu=True, bias=self.conv[0].bias)
         x1, x2, x3, x4 = self.backbone._build_features(eng, x)
         outs = self.decoder._build(eng, x4, [x3, x2, x1])
         if self.dual:
-            return [eng.bilinear(o, s) for o, s in zip(outs, [32, 16, 8, 4] * 2)]
+            return outs, [32, 16, 8, 4] * 2
         # prediction heads :129-132: biased 1x1 convs, no BatchNorm, as K-channel fp32 maps (the form BasicConv2d._build gives the dual heads)
         heads = [self.out_head4, self.out_head3, self.out_head2, self.out_head1]
         K = heads[0].out_channels
-        ps = [eng.conv_bn_act(d, h, None, bias=h.bias, out_map=(K, (K + 7) // 8 * 8), y_dt=F32, y_C=K) for d, h in zip(outs, heads)]
-        return [eng.bilinear(p, s) for p, s in zip(ps, [32, 16, 8, 4])]
+        return [eng.conv_bn_act(d, h, None, bias=h.bias, out_map=(K, (K + 7) // 8 * 8), y_dt=F32, y_C=K) for d, h in zip(outs, heads)], [32, 16, 8, 4]
+
+    def _build(self, eng, x):
+        """forward :101-142: 8 maps (dual) or [p4, p3, p2, p1]"""
+        lows, scales = self._build_lowres(eng, x)
+        return [eng.bilinear(o, s) for o, s in zip(lows, scales)]
 
     def forward(self, x, mode='test'):
         return list(run_module(self._build, [x], self.hot_parameters(x.shape[1] == 1), self.training))

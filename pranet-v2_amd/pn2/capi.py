@@ -123,6 +123,10 @@ class BnReduceJob(C.Structure):
                [(n, C.c_int) for n in ("ld_dy", "ld_y", "ld_x", "M", "Cp", "nblk", "rows_per_blk", "cvp", "r6", "pad_")]
 
 
+class SegUpMap(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("ld", C.c_int), ("H", C.c_int), ("W", C.c_int)]
+
+
 P, I, LL, FL = C.c_void_p, C.c_int, C.c_longlong, C.c_float
 
 # name -> argtypes ; every function returns int (0 = ok)
@@ -266,6 +270,7 @@ SIGNATURES = {
     "pn2_eval_wfm_blocks": [I, I],
     "pn2_eval_wfm": [P, P, I, I, P, C.c_double, P, P, P, P],
     "pn2_seg_labels": [P, I, I, I, I, I, I, P, P],
+    "pn2_seg_labels_up": [C.POINTER(SegUpMap), I, I, I, I, I, I, P, P],
     "pn2_seg_counts": [P, P, LL, I, P, P],
     "pn2_seg_surface_workspace": [I, I, I, I, C.POINTER(LL)],
     "pn2_seg_surface_hist_len": [I, I, I],

@@ -9,6 +9,8 @@ import torch
 from .capi import call, F32
 from .engine import Act, BnFoldCache, Engine, PackCache, StepArena, TUNER, _p, _stream
 from .graph import get_compute_dtype
+from .volinput import zoom
+from .voleval import MODES, predict_labels_up, volume_dice, volume_metrics
 
 
 class Predictor:
@@ -23,13 +25,13 @@ class Predictor:
         self._states = {}               # input shape -> captured forward (insertion order = LRU order)
         self.max_shapes = 8
 
-    def _forward(self, st, x):
+    def _forward(self, st, x, build=None):
         self.pack_cache.refresh()
         self.bn_fold.refresh()
         if st["arena"] is not None:
             st["arena"].begin_step(x.device)
         eng = Engine(self.dtype, False, need_grad=False, pack_cache=self.pack_cache, tuner=TUNER, arena=st["arena"], bn_fold=self.bn_fold)
-        outs = self.model._build(eng, eng.from_nchw(x))
+        outs = (build or self.model._build)(eng, eng.from_nchw(x))
         eng.finish_forward()
         return eng, outs
 
@@ -45,29 +47,32 @@ class Predictor:
     def _state(self, x):
         """One captured forward per INPUT shape (test sets have one test size but a different ground-truth size for almost every image: the
         sum -> resize -> sigmoid -> min-max -> uint8 tail of MyTest_med.py:104-111 runs eagerly, 6 launches, on the replayed maps)."""
+        def run(st):
+            eng, outs = self._forward(st, st["x"])
+            return tuple(eng.to_nchw(o) for o in outs)
+        return self._captured(tuple(x.shape), x, run)
+
+    def _captured(self, key, x, run, static=None):
+        """The state of `key`, captured on first use: run(st) is the pass over the static input st["x"] (a clone of x); what it returns stays in st["out"].
+        static(): further buffers of a new state that the pass writes."""
         self._check_weights()
-        key = tuple(x.shape)
         st = self._states.get(key)
         if st is None:
             if self.model.training:
                 raise RuntimeError("Predictor runs eval-mode BatchNorm: call model.eval() first")
             if len(self._states) >= self.max_shapes:          # bounded: evict the least recently used input shape
                 self._states.pop(next(iter(self._states)))
-            st = self._states[key] = {"arena": StepArena(), "graph": None, "x": x.clone(), "out": None}
-
-            def run():
-                eng, outs = self._forward(st, st["x"])
-                return tuple(eng.to_nchw(o) for o in outs)
+            st = self._states[key] = {"arena": StepArena(), "graph": None, "x": x.clone(), "out": None, **(static() if static else {})}
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(2):              # pass 1 sizes the arena and tunes, pass 2 runs on the addresses the graph will replay
-                    run()
+                    run(st)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             st["graph"] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(st["graph"]):
-                st["out"] = run()
+                st["out"] = run(st)
         else:
             self._states[key] = self._states.pop(key)          # most recently used last
         return st
@@ -93,3 +98,84 @@ class Predictor:
         scratch = torch.empty(2 + 2 * 512, dtype=torch.float32, device=images.device)
         call.pn2_eval_tail(r.ptr, _p(u8), _p(scratch), r.M, _stream())
         return u8
+
+
+class VolumePredictor(Predictor):
+    """The multi-class volume inference of test_single_volume / val_single_volume (multiclass_seg/EMCAD/utils/utils.py:165-301) from captured graphs:
+           vp = VolumePredictor(model.eval(), patch_size=(224, 224), batch_size=16)
+           labels = vp.predict(image, "sum_fg")                         # image [D][H][W] or [H][W] on the GPU -> uint8 labels of the same shape
+           vp.test_single_volume(image, label, classes, use_dual=True)  # -> [(dice, hd95, jaccard, asd)] as pn2.voleval.test_single_volume
+           vp.val_single_volume(image, label, classes, use_dual=True)   # -> [dice]                       as pn2.voleval.val_single_volume
+    One graph per (batch, patch height, patch width, mode) holds the eval forward up to the low-resolution head maps (model._build_lowres) and ONE launch
+    that turns them into the uint8 labels of the batch (pn2_seg_labels_up): the full-resolution K-class maps never exist.  The spline zoom going in, the order-0
+    zoom coming out and the metric kernels stay outside (volume sizes vary; their tables are cached on the host, pn2/volinput.py)."""
+
+    def __init__(self, model, patch_size=(224, 224), batch_size=16, dtype=None):
+        super().__init__(model, dtype)
+        if not hasattr(model, "_build_lowres"):
+            raise TypeError("VolumePredictor needs a model with K-class head maps (lib.networks.EMCADNet)")
+        self.patch_size = (int(patch_size[0]), int(patch_size[1]))
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError("batch_size >= 1")
+
+    @staticmethod
+    def _pick(lows, scales, mode):
+        """The maps of a mode, as voleval.test_single_volume / val_single_volume pick them from the model's output list."""
+        sel = {"last": slice(-1, None), "sum_fg": slice(0, 4)}.get(mode)
+        if sel is not None:
+            return lows[sel], scales[sel]
+        return lows[:4] + lows[-4:], scales[:4] + scales[-4:]
+
+    def _labels(self, xb, mode):
+        """xb [B][1][h][w] fp32 -> the state whose st["labels"] (uint8 [B][h][w]) holds the labels of xb until the next call with this shape and mode."""
+        if mode not in MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(MODES)}")
+        if not xb.is_cuda:
+            raise RuntimeError("pn2.infer needs GPU tensors (no CPU fallback)")
+        if self.model.training:          # on every call: a replay would go on serving the eval-mode graph
+            raise RuntimeError("VolumePredictor runs eval-mode BatchNorm: call model.eval() first")
+        B, _, h, w = xb.shape
+
+        def run(st):
+            eng, (lows, scales) = self._forward(st, st["x"], self.model._build_lowres)
+            st["lows"] = lows
+            maps, sc = self._pick([a.t[..., :a.C] for a in lows], list(scales), mode)
+            return predict_labels_up(maps, sc, mode, out=st["labels"])
+        st = self._captured((B, h, w, mode), xb, run, lambda: {"labels": torch.empty((B, h, w), dtype=torch.uint8, device=xb.device), "lows": None})
+        st["x"].copy_(xb, non_blocking=True)
+        st["graph"].replay()
+        return st
+
+    def lowres(self, xb, mode="last"):
+        """Debugging / tests: clones of the low-resolution head maps of one batch xb [B][1][h][w], NCHW fp32, as the graph of `mode` leaves them."""
+        st = self._labels(xb.float(), mode)
+        return [a.t[..., :a.C].permute(0, 3, 1, 2).clone() for a in st["lows"]]
+
+    def predict(self, image, mode):
+        """uint8 label volume of image [D][H][W] (or of one image [H][W], which is not resampled: utils.py:224-231).  Slices whose size differs from patch_size are
+        resampled as the reference does; a last batch shorter than batch_size is filled with zero slices (eval-mode BatchNorm keeps the samples independent)."""
+        x = image.float()
+        if x.dim() == 2:
+            return self._labels(x[None, None].contiguous(), mode)["labels"][0].clone()
+        D, H, W = x.shape
+        ph, pw = self.patch_size
+        B = self.batch_size
+        preds = []
+        for i in range(0, D, B):
+            xb = zoom(x[i:i + B], (ph, pw), 3)
+            n = xb.shape[0]
+            if n < B:
+                xb = torch.cat([xb, xb.new_zeros((B - n, ph, pw))])
+            lab = self._labels(xb[:, None], mode)["labels"][:n]
+            preds.append(zoom(lab, (H, W), 0) if (H, W) != (ph, pw) else lab.clone())          # (the next replay rewrites the static buffer)
+        return torch.cat(preds)
+
+    def test_single_volume(self, image, label, classes, use_dual=None):
+        image, label = image.squeeze(0), label.squeeze(0)
+        pred = self.predict(image, "sum_fg" if use_dual and image.dim() == 3 else "last")
+        return volume_metrics(pred, label, classes)
+
+    def val_single_volume(self, image, label, classes, use_dual=False):
+        image, label = image.squeeze(0), label.squeeze(0)
+        return volume_dice(self.predict(image, "sum_fg_minus_bg" if use_dual else "last"), label, classes)

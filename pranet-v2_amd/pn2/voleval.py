@@ -6,7 +6,7 @@ import ctypes as C
 
 import torch
 
-from .capi import call
+from .capi import call, SegUpMap
 from .core import _p, _stream
 from .volinput import zoom
 
@@ -39,6 +39,34 @@ def predict_labels(outs, mode):
     out = torch.empty((N, H, W), dtype=torch.uint8, device=outs[0].device)
     ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
     call.pn2_seg_labels(ptrs, len(outs), MODES[mode], N, K, H, W, _p(out), _stream())
+    return out
+
+
+def predict_labels_up(maps, scales, mode, out=None):
+    """predict_labels of the maps up-sampled bilinearly (align_corners=False) by their integer `scales`, in one launch and without the full-resolution maps
+    (pn2_seg_labels_up): maps are 1..8 NHWC fp32 tensors [N][h][w][K], 2 <= K <= 16, each of its own size with h * scale, w * scale the same for all.  The last
+    axis may be a slice of a wider, channel-padded one (t[..., :K]): only its stride has to be 1.  Returns uint8 [N][h * scale][w * scale] (written into `out` if given)."""
+    if mode not in MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(MODES)}")
+    maps, scales = [m.detach() for m in maps], [int(s) for s in scales]
+    _need_gpu(*maps)
+    if not 1 <= len(maps) <= 8 or len(scales) != len(maps) or (mode == "sum_fg_minus_bg" and len(maps) % 2):
+        raise ValueError("1..8 maps (an even number for sum_fg_minus_bg), one scale for each")
+    N, _, _, K = maps[0].shape if maps[0].dim() == 4 else (0, 0, 0, 0)
+    OH, OW = maps[0].shape[1] * scales[0], maps[0].shape[2] * scales[0]
+    descs = (SegUpMap * len(maps))()
+    for d, m, s in zip(descs, maps, scales):
+        if m.dim() != 4 or m.dtype != torch.float32 or m.shape[0] != N or m.shape[3] != K or not 2 <= K <= 16 or s < 1 or (m.shape[1] * s, m.shape[2] * s) != (OH, OW):
+            raise ValueError("maps must be fp32 [N][h][w][K] with 2 <= K <= 16 and one output size h * scale, w * scale")
+        ld = m.stride(2)
+        if m.stride(3) != 1 or ld < K or m.stride(1) != m.shape[2] * ld or m.stride(0) != m.shape[1] * m.shape[2] * ld:
+            raise ValueError("maps must be dense NHWC up to a padded channel axis")
+        d.p, d.ld, d.H, d.W = m.data_ptr(), ld, m.shape[1], m.shape[2]
+    if out is None:
+        out = torch.empty((N, OH, OW), dtype=torch.uint8, device=maps[0].device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, OH, OW) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous uint8 GPU tensor {(N, OH, OW)}")
+    call.pn2_seg_labels_up(descs, len(maps), MODES[mode], N, K, OH, OW, _p(out), _stream())
     return out
 
 
