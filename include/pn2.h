@@ -215,6 +215,11 @@ int pn2_affine_act_sum(int dt, const void* x, int ld_x, void* y, int ld_y, int M
  * slice spx[3] straight into the concat buffer (Res2Net_v1b.py:78-79: `out = torch.cat((out, spx[self.nums]), 1)`), no copy launch.  16-byte aligned rows / c_lo only. */
 int pn2_affine_act_tee(int dt, const void* x, int ld_x, void* y, int ld_y, int M, int C, const float* scale, const float* shift, int relu,
                        void* y3, int ld_y3, int c_lo, void* stream);
+/* y[m][c] = act(fma(x[m][c], scale[c], shift[c]) + T(fma(x2[m][c], scale2[c], shift2[c]))), T = rounding to the storage dtype: pn2_affine_act (no activation) of x2
+ * followed by pn2_affine_act of x with that result as the residual, bit for bit, as ONE pass - the intermediate tensor is never written.  A Bottle2neck stage block's
+ * out = relu(bn3(conv3) + downsample(x)) (Res2Net_v1b.py:82-89), whose downsample BatchNorm output has no other reader.  16-byte aligned rows only (-2 otherwise). */
+int pn2_affine_act_dual(int dt, const void* x, int ld_x, const float* scale, const float* shift, const void* x2, int ld_x2, const float* scale2, const float* shift2,
+                        void* y, int ld_y, int M, int C, int relu, void* stream);
 /* BatchNorm + ReLU + MaxPool2d(3, 2, 1) forward as ONE pass (the stem of Res2Net_v1b.py:137-139: self.bn1 -> self.relu -> self.maxpool): the normalised full-resolution activation feeds
  * the pool alone, so it is never written.  pooled[n][oy][ox][c] = max over the window of T(relu(raw*scale + shift)), idx = argmax tap (0..8), exactly as pn2_affine_act followed by
  * pn2_maxpool3x3s2_fwd give them.  The backward is pn2_maxpool3x3s2_bwd + the BatchNorm passes with the ReLU mask recomputed from raw. */
@@ -274,6 +279,12 @@ int pn2_bn_bwd_reduce_multi(int dt, const pn2_bnreduce_job* jobs_dev, const int*
 int pn2_bn_bwd_apply(int dt, int dt_dy, const void* dy, int ld_dy, int Cdy, const void* y, int ld_y, int dt_y, const void* x, int ld_x,
                      int M, int Cp, const float* mean, const float* invstd, const float* coef, void* dx, int ld_dx,
                      void* dres, int ld_dres, int dres_accum, const float* mask_scale, const float* mask_shift, int relu6, void* stream);
+/* pass 2 for TWO BatchNorms that receive the same, already masked gradient dz (bn3 and the downsample BatchNorm of a Bottle2neck stage block): pn2_bn_bwd_apply without
+ * y, dres and mask for each of (x_a, coef_a, ...) -> dx_a and (x_b, coef_b, ...) -> dx_b, with dz read once.  Both outputs bit-identical to their single launches.
+ * 16-byte aligned rows only (-2 otherwise). */
+int pn2_bn_bwd_apply_dual(int dt, const void* dz, int ld_dz, int M, int Cp,
+                          const void* x_a, int ld_xa, const float* mean_a, const float* invstd_a, const float* coef_a, void* dx_a, int ld_dxa,
+                          const void* x_b, int ld_xb, const float* mean_b, const float* invstd_b, const float* coef_b, void* dx_b, int ld_dxb, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- pooling
  * nn.MaxPool2d(3,2,1) Res2Net_v1b.py:112 ; nn.AvgPool2d(3,stride,1) :40,80 ; AvgPool2d(s,s,ceil,count_include_pad=False) :131-132 */

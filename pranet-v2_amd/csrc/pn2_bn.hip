@@ -756,6 +756,110 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows_tab(const pn2_bnapply_j
                               (T*)j.dres, j.ld_dres, j.dres_accum, j.rows_per_blk, j.cvp, j.msc, j.msh, j.r6, blockIdx.x - bstart[jb]);
 }
 
+// y = act(fma(x, sc, sh) + T(fma(x2, sc2, sh2))): the output pass of a Bottle2neck stage block (Res2Net_v1b.py:82-89: out = relu(bn3(conv3) + downsample(x))) with the
+// downsample BatchNorm's output formed on the fly instead of written by a pass of its own and re-read here.  T rounds to the storage dtype, as that pass's store did, so the
+// result is the one of affine_rows_k (no ReLU) followed by affine_rows_k (residual), bit for bit.  Its own kernel: the second parameter set would cost affine_rows_k registers.
+template <typename T>
+__global__ __launch_bounds__(256) void affine_dual_rows_k(const T* __restrict__ x, int ld_x, const float* __restrict__ scale, const float* __restrict__ shift,
+                                                          const T* __restrict__ x2, int ld_x2, const float* __restrict__ scale2, const float* __restrict__ shift2,
+                                                          T* __restrict__ y, int ld_y, int M, int C, int relu, int rows_per_blk, int CVP) {
+    constexpr int V = TT<T>::VEC;
+    const int CV = C / V, R = 256 / CVP;
+    const int cvl = threadIdx.x % CVP, rl = threadIdx.x / CVP;
+    const int r0 = blockIdx.x * rows_per_blk;
+    int r1 = r0 + rows_per_blk; if (r1 > M) r1 = M;
+    for (int cv = cvl; cv < CV; cv += CVP) {
+        const int c = cv * V;
+        float sc[V], sh[V], sc2[V], sh2[V];
+        ldpar<V>(scale + c, sc); ldpar<V>(shift + c, sh); ldpar<V>(scale2 + c, sc2); ldpar<V>(shift2 + c, sh2);
+        for (int m = r0 + rl; m < r1; m += R * RU) {
+            uint4 vx[RU], vr[RU];
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const int mm = m + u * R;
+                if (mm < r1) {
+                    vx[u] = *reinterpret_cast<const uint4*>(x + (size_t)mm * ld_x + c);
+                    vr[u] = *reinterpret_cast<const uint4*>(x2 + (size_t)mm * ld_x2 + c);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const int mm = m + u * R;
+                if (mm < r1) {
+                    float v[V], r[V];
+                    TT<T>::unpack(vx[u], v);
+                    TT<T>::unpack(vr[u], r);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) r[e] = fmaf(r[e], sc2[e], sh2[e]);
+                    TT<T>::unpack(TT<T>::pack(r), r);          // the value the separate pass would have stored
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        float t = fmaf(v[e], sc[e], sh[e]);
+                        t += r[e];
+                        v[e] = relu ? (relu == 2 ? fminf(fmaxf(t, 0.f), 6.f) : fmaxf(t, 0.f)) : t;
+                    }
+                    *reinterpret_cast<uint4*>(y + (size_t)mm * ld_y + c) = TT<T>::pack(v);
+                }
+            }
+        }
+    }
+}
+
+// bn_bwd_apply_rows_k<T, LEAN = true> for TWO BatchNorms that share the incoming gradient dz (already masked by its producer): bn3 and the downsample BatchNorm of a
+// Bottle2neck stage block, whose sum the block's ReLU follows.  dz is read once; each output is formed by the single launch's operation sequence, bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_apply_dual_rows_k(const T* __restrict__ dz, int ld_dz, int M, int Cp, int rows_per_blk, int CVP,
+                                                                const T* __restrict__ xa, int ld_xa, const float* __restrict__ mean_a, const float* __restrict__ invstd_a,
+                                                                const float* __restrict__ coef_a, T* __restrict__ dxa, int ld_dxa,
+                                                                const T* __restrict__ xb, int ld_xb, const float* __restrict__ mean_b, const float* __restrict__ invstd_b,
+                                                                const float* __restrict__ coef_b, T* __restrict__ dxb, int ld_dxb) {
+    constexpr int V = TT<T>::VEC;
+    const int CV = Cp / V, R = 256 / CVP;
+    const int cvl = threadIdx.x % CVP, rl = threadIdx.x / CVP;
+    const int r0 = blockIdx.x * rows_per_blk;
+    int r1 = r0 + rows_per_blk; if (r1 > M) r1 = M;
+    for (int cv = cvl; cv < CV; cv += CVP) {
+        const int c = cv * V;
+        float ka[2][V], kb[2][V], kd[2][V], kmu[2][V];          // dx = a*dz + b*(x - mu) + d, as bn_bwd_apply_rows_body
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float* coef = s ? coef_b : coef_a;
+            float c1[V], c2[V], is[V];
+            ldpar<V>(coef + c, ka[s]); ldpar<V>(coef + Cp + c, c1); ldpar<V>(coef + 2 * Cp + c, c2); ldpar<V>((s ? invstd_b : invstd_a) + c, is); ldpar<V>((s ? mean_b : mean_a) + c, kmu[s]);
+#pragma unroll
+            for (int e = 0; e < V; ++e) { kb[s][e] = __fmul_rn(__fmul_rn(-ka[s][e], c2[e]), is[e]); kd[s][e] = __fmul_rn(-ka[s][e], c1[e]); }
+        }
+        for (int m = r0 + rl; m < r1; m += R * RU) {
+            uint4 vg[RU], va[RU], vb[RU];
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const int mm = m + u * R;
+                if (mm < r1) {
+                    vg[u] = *reinterpret_cast<const uint4*>(dz + (size_t)mm * ld_dz + c);
+                    va[u] = *reinterpret_cast<const uint4*>(xa + (size_t)mm * ld_xa + c);
+                    vb[u] = *reinterpret_cast<const uint4*>(xb + (size_t)mm * ld_xb + c);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const int mm = m + u * R;
+                if (mm < r1) {
+                    float g[V], xv[V], o[V];
+                    TT<T>::unpack(vg[u], g);
+                    TT<T>::unpack(va[u], xv);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) o[e] = __fmaf_rn(ka[0][e], g[e], __fmaf_rn(kb[0][e], xv[e] - kmu[0][e], kd[0][e]));
+                    *reinterpret_cast<uint4*>(dxa + (size_t)mm * ld_dxa + c) = TT<T>::pack(o);
+                    TT<T>::unpack(vb[u], xv);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) o[e] = __fmaf_rn(ka[1][e], g[e], __fmaf_rn(kb[1][e], xv[e] - kmu[1][e], kd[1][e]));
+                    *reinterpret_cast<uint4*>(dxb + (size_t)mm * ld_dxb + c) = TT<T>::pack(o);
+                }
+            }
+        }
+    }
+}
+
 
 // rows per block of the row-walk kernels (affine_rows_*, bn_bwd_apply_rows_*): at least one and at most 4 * RU rows per row lane
 inline void rows_geometry(int M, int CV, int& cvp, int& rows_per_blk, int& nblk) { rows_walk_geometry(M, CV, 1, RU * 4, cvp, rows_per_blk, nblk); }
@@ -1005,6 +1109,39 @@ int pn2_affine_act_tee(int dt, const void* x, int ld_x, void* y, int ld_y, int M
     const RowsPlan p = rows_plan(true, M, C, V);
     return with_storage_dtype(dt, [&](auto ty) {
         return launch_affine_rows<type_of<decltype(ty)>>(p, (hipStream_t)stream, x, ld_x, y, ld_y, M, C, scale, shift, nullptr, 0, relu, nullptr, 0, nullptr, 0, y3, ld_y3, c_lo);
+    });
+}
+
+/* y = act(fma(x, scale, shift) + T(fma(x2, scale2, shift2))): pn2_affine_act (no activation) of x2 followed by pn2_affine_act of x with that result as the
+ * residual, as ONE pass that never writes the intermediate tensor.  16-byte aligned rows only (-2 otherwise). */
+int pn2_affine_act_dual(int dt, const void* x, int ld_x, const float* scale, const float* shift, const void* x2, int ld_x2, const float* scale2, const float* shift2,
+                        void* y, int ld_y, int M, int C, int relu, void* stream) {
+    if (!x || !x2 || !y || !scale || !shift || !scale2 || !shift2) return -1;
+    const int V = vec_of(dt);
+    if (M < 1 || C < 1 || !affine_aligned(V, C, ld_x, ld_y, x2, ld_x2)) return -2;
+    const RowsPlan p = rows_plan(true, M, C, V);
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<affine_dual_rows_k<T>>(dim3(p.nblk), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, ld_x, scale, shift, (const T*)x2, ld_x2, scale2, shift2,
+                                                 (T*)y, ld_y, M, C, relu, p.rows_per_blk, p.cvp);
+    });
+}
+
+/* pn2_bn_bwd_apply in its lean form (dy already masked, no stored activation, no residual gradient) for TWO BatchNorms that receive the same gradient dz:
+ * dx_a from (x_a, mean_a, invstd_a, coef_a), dx_b from (x_b, ...), dz read once.  Each output is bit-identical to its own pn2_bn_bwd_apply launch.
+ * 16-byte aligned rows only (-2 otherwise). */
+int pn2_bn_bwd_apply_dual(int dt, const void* dz, int ld_dz, int M, int Cp,
+                          const void* x_a, int ld_xa, const float* mean_a, const float* invstd_a, const float* coef_a, void* dx_a, int ld_dxa,
+                          const void* x_b, int ld_xb, const float* mean_b, const float* invstd_b, const float* coef_b, void* dx_b, int ld_dxb, void* stream) {
+    if (!dz || !x_a || !mean_a || !invstd_a || !coef_a || !dx_a || !x_b || !mean_b || !invstd_b || !coef_b || !dx_b) return -1;
+    const int V = vec_of(dt);
+    if (M < 1 || Cp < 1 || Cp % V || ld_dz % V || ld_xa % V || ld_dxa % V || ld_xb % V || ld_dxb % V) return -2;
+    const RowsPlan p = rows_plan(true, M, Cp, V);
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<bn_bwd_apply_dual_rows_k<T>>(dim3(p.nblk), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dz, ld_dz, M, Cp, p.rows_per_blk, p.cvp,
+                                                       (const T*)x_a, ld_xa, mean_a, invstd_a, coef_a, (T*)dx_a, ld_dxa,
+                                                       (const T*)x_b, ld_xb, mean_b, invstd_b, coef_b, (T*)dx_b, ld_dxb);
     });
 }
 

@@ -101,7 +101,8 @@ class Bottle2neck(nn.Module):
             k = pool.kernel_size if isinstance(pool.kernel_size, int) else pool.kernel_size[0]
             # (fold_bwd: conv1 above is x's first consumer - its dgrad runs last in the backward pass and adds this pool's gradient in its epilogue)
             r = x if k == 1 else eng.avgpool(x, k, k, 0, ceil_mode=True, count_include_pad=False, fold_bwd=True)
-            res = eng.conv_bn_act(r, dconv, dbn, relu=False)
+            # (defer_out: conv3 below is the only reader of the downsample BatchNorm's output - in a training pass it is never written, conv3's output pass normalises both)
+            res = eng.conv_bn_act(r, dconv, dbn, relu=False, defer_out=True)
         else:
             res = x
         return eng.conv_bn_act(cat, self.conv3, self.bn3, relu=True, residual=res, x_last=True)

@@ -169,6 +169,7 @@ SIGNATURES = {
     "pn2_bn_eval_prepare_multi": [P, P, I, I, P],
     "pn2_affine_act_sum": [I, P, I, P, I, I, I, P, P, I, P, I, P, I, P],
     "pn2_affine_act_tee": [I, P, I, P, I, I, I, P, P, I, P, I, I, P],
+    "pn2_affine_act_dual": [I, P, I, P, P, P, I, P, P, P, I, I, I, I, P],
     "pn2_bn_relu_maxpool_fwd": [I, P, I, P, P, P, I, P, I, I, I, I, I, I, P],
     "pn2_pool_bn_bwd_reduce": [I, P, I, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, I, P],
     "pn2_pool_bn_bwd_apply": [I, P, I, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, I, P],
@@ -178,6 +179,7 @@ SIGNATURES = {
     "pn2_bn_bwd_finalize": [P, P, I, C.POINTER(BnDesc), P, P, P, P, I, P, P],
     "pn2_bn_bwd_finalize_seg": [C.POINTER(BnSegs), C.POINTER(BnDesc), P, P, P, P, I, P, P],
     "pn2_bn_bwd_apply": [I, I, P, I, I, P, I, I, P, I, I, I, P, P, P, P, I, P, I, I, P, P, I, P],
+    "pn2_bn_bwd_apply_dual": [I, P, I, I, I, P, I, P, P, P, P, I, P, I, P, P, P, P, I, P],
     "pn2_maxpool3x3s2_fwd": [I, P, I, P, I, P, I, I, I, I, I, I, P],
     "pn2_maxpool3x3s2_bwd": [I, P, I, P, P, I, I, I, I, I, I, I, P],
     "pn2_avgpool_fwd": [I, P, I, P, I, I, I, I, I, I, I, I, I, I, I, P],

@@ -89,7 +89,7 @@ class _LinearAsConv:
 class Act:
     """NHWC activation view.  t: torch tensor (N,H,W,Cp) whose last dim is contiguous; ld = pixel stride."""
     __slots__ = ("eng", "t", "N", "H", "W", "C", "gw", "gwp", "dt", "grad", "_written", "child_written", "requires_grad", "parent", "c0", "lat", "galias",
-                 "bnb", "bstats", "sum_of", "dual_done", "_sealed", "grad_masked", "colparts", "pool_prior")
+                 "bnb", "bstats", "sum_of", "dual_done", "_sealed", "grad_masked", "colparts", "pool_prior", "deferred", "prod")
 
     def __init__(self, eng, t, C_, gw=None, gwp=None, dt=None, requires_grad=True):
         self.eng, self.t = eng, t
@@ -109,6 +109,10 @@ class Act:
         self._sealed = False            # a dgrad that declared itself the last contribution has written this gradient
         self.grad_masked = False        # that dgrad stored dz = dy * [y > 0] (PN2_BNB_STORE_MASKED): the gradient buffer already carries the ReLU mask
         self.colparts = None            # (partial rows, nblk, gradient tensor): column sums of this Act's gradient left by the kernel that wrote it (EncoderOps.dwconv_gelu)
+        self.deferred = None            # the conv_bn_act record of a train-mode BatchNorm output that was NOT written (conv_bn_act(defer_out=True)): `t` is the raw conv output; the op that
+                                        # takes this Act as its residual normalises it on the fly (pn2_affine_act_dual) or has it written first (ConvOps._materialize)
+        self.prod = None                # the conv_bn_act record that produced this train-mode BatchNorm output without activation (a residual candidate): the residual consumer's backward can run this
+                                        # BatchNorm's backward together with its own (ConvOps._bn_backward_dual) and leaves the raw gradient in prod.draw_done - the producer then skips its own
         self.pool_prior = None          # gradient of AvgPool2d(2, 2)(this Act), not yet applied: the dgrad that completes this Act's gradient adds 1/4 of it in its epilogue (SpatialOps.avgpool(fold_bwd=True))
 
     @property
@@ -394,6 +398,8 @@ DW_COLSUM = os.environ.get("PN2_DW_COLSUM", "1") == "1"             # PVTv2 Mlp:
 MASKED_STORE = os.environ.get("PN2_MASKED_STORE", "1") == "1"       # ... which then stores dy * [y > 0] for BN + residual + ReLU outputs (residual gradient aliases it)
 POOL_BWD_QUAD = os.environ.get("PN2_POOL_BWD_QUAD", "1") == "1"  # ... and its backward without the full-resolution gradient tensor (pn2_pool_bn_bwd_reduce / _apply); 0: pool-backward launch + the generic BatchNorm passes
 RES_STATS = os.environ.get("PN2_RES_STATS", "1") == "1"          # the downsample BatchNorm's backward sums from the dgrad epilogue that forms bn3's masked gradient (pn2_conv_ep.c): no reduce pass
+DUAL_AFFINE = os.environ.get("PN2_DUAL_AFFINE", "1") == "1"      # Bottle2neck stage blocks: the downsample BatchNorm's output is never written - out = relu(bn3(raw3) + T(bn_d(raw_d))) in one pass (pn2_affine_act_dual); 0: two normalise passes
+DUAL_BNB_APPLY = os.environ.get("PN2_DUAL_BNB_APPLY", "1") == "1"  # ... and in the backward bn3 and the downsample BatchNorm, whose sums one dgrad epilogue left (PN2_RES_STATS), share one apply pass over the masked gradient (pn2_bn_bwd_apply_dual)
 MUL_BWD = os.environ.get("PN2_MUL_BWD", "1") == "1"              # backward of a product (the aggregation's): both operand gradients from one pass (pn2_mul_bwd); 0: two pn2_binary launches
 POOL_FOLD = os.environ.get("PN2_POOL_FOLD", "1") == "1"          # Bottle2neck stage blocks: the backward of the downsample branch's AvgPool2d(2, 2) rides in conv1's dgrad epilogue (pn2_conv_ep.pool) - no pool-backward launch
 POOL_FUSE = os.environ.get("PN2_POOL_FUSE", "1") == "1"          # the stem's bn1 -> ReLU -> MaxPool as one op: the 176 x 176 BatchNorm output is never written (conv_bn_act(pool=True))

@@ -84,6 +84,13 @@ def _time_candidates(cands, run, admit=None):
     return kept[min(range(len(kept)), key=lambda i: times[i])] if kept else None
 
 
+def out_ok_for_dual(eng, s, residual, out, y_dt, y_C, bias, sum_with, gate, tee, pool):
+    """Whether the output pass of the conv_bn_act call `s` is the plain same-dtype 16-byte-row pass that pn2_affine_act_dual replaces (residual: the deferred BatchNorm output)."""
+    return (core.DUAL_AFFINE and y_C is None and y_dt in (None, eng.dt) and bias is None and sum_with is None and gate is None and tee is None and not pool
+            and (residual.N, residual.H, residual.W, residual.Cp, residual.dt) == (s.N, s.OH, s.OW, s.Cp, eng.dt) and s.Cp % s.V == 0
+            and (out is None or out.ld % s.V == 0))
+
+
 class ConvOps:
     # ------------------------------------------------------------------ weights
     def _pack_desc(self, w, x_map, out_map, transposed):
@@ -268,7 +275,7 @@ class ConvOps:
 
     # ------------------------------------------------------------------ conv (+BN +ReLU +residual): the orchestrator, then its steps in the order they run
     def conv_bn_act(self, x, conv, bn=None, relu=False, residual=None, out=None, out_map=None, y_dt=None, y_C=None, bias=None, sum_with=None,
-                    raw_out=None, par_out=None, x_last=False, gate=None, tee=None, pool=False):
+                    raw_out=None, par_out=None, x_last=False, gate=None, tee=None, pool=False, defer_out=False):
         """y = act(BN(conv(x)) + residual)   — BasicConv2d / Bottle2neck pieces.
 
         conv: nn.Conv2d (bias-free unless `bias` given), bn: nn.BatchNorm2d or None.
@@ -285,6 +292,9 @@ class ConvOps:
         x_last:   the caller guarantees that this conv's data gradient is the LAST contribution to x's gradient (x's first consumer in forward
                   order).  If x is the output of a train-mode BatchNorm, the dgrad GEMM then takes that BatchNorm's backward statistics in its
                   epilogue (pn2_conv_gemm_ep) and x's producer skips its pn2_bn_bwd_reduce pass.
+        defer_out: the caller guarantees that the output is consumed ONLY as the `residual` of one later conv_bn_act (Bottle2neck's downsample branch).  A train-mode
+                  BatchNorm output without activation is then not written: the returned Act carries the raw conv output and the BatchNorm's rows (Act.deferred), and the
+                  consumer's output pass normalises both operands (pn2_affine_act_dual), behind ONE finalize launch for the two BatchNorms.  Bit-identical to the two passes.
         """
         assert tee is None or (self.training and bn is not None and bias is None and gate is None and sum_with is None), "tee: train-mode conv + BatchNorm outputs only"
         # pool: the op is conv -> BatchNorm -> ReLU -> MaxPool2d(3, 2, 1) and returns the POOLED activation; the full-resolution BatchNorm output is never written
@@ -294,6 +304,13 @@ class ConvOps:
         s = self._conv_geometry(x, conv, out_map)
         s.bn, s.relu, s.residual, s.bias, s.sum_with, s.x_last, s.gate, s.tee, s.pool, s.y_C, s.train_bn = bn, relu, residual, bias, sum_with, x_last, gate, tee, pool, y_C, bn is not None and self.training
         s.wp, s.pd = self.pack(s.w, s.x_map, s.o_map, False)
+        # a residual whose BatchNorm output was deferred: normalised inside this op's output pass where that pass is the plain same-dtype one, else written first
+        s.dual = s.draw_done = None          # draw_done: the gradient of s.raw once the residual consumer's backward has formed it (_bn_backward_dual)
+        if residual is not None and residual.deferred is not None:
+            if (s.train_bn and out_ok_for_dual(self, s, residual, out, y_dt, y_C, bias, sum_with, gate, tee, pool)):
+                s.dual = residual.deferred
+            else:
+                self._materialize(residual)
         # biased conv / nn.Linear with nothing behind it (no BN, activation, residual or re-layout): the bias goes into the GEMM epilogue and
         # the GEMM writes the output itself - no separate affine pass
         s.fuse_bias = (core.FUSE_BIAS and bn is None and bias is not None and not relu and residual is None and out is None and y_C is None and (y_dt is None or y_dt == self.dt))
@@ -320,11 +337,26 @@ class ConvOps:
             s.bd = _bn_desc(bn, s.M, s.Cp, s.Cout, s.gw_o, s.gwp_o, tile_rows=s.tile_rows)
             s.par = par_out if par_out is not None else self.fbuf(4, s.Cp)          # rows: scale, shift, mean, invstd
             assert tuple(s.par.shape) == (4, s.Cp) and s.par.stride(1) == 1
-            s.scale, s.shift, s.mean, s.invstd = self._bn_forward(bn, s.bd, s.par, s.psum, s.psq, s.nblk, bias)
+            s.defer = bool(defer_out and core.DUAL_AFFINE and s.train_bn and not relu and residual is None and out is None and sum_with is None and tee is None and not pool
+                           and gate is None and y_C is None and bias is None and y_dt in (None, self.dt) and not s.fuse_bias and s.Cp % s.V == 0 and s.raw_ld % s.V == 0)
+            if s.defer:             # neither finalized nor written here: the consumer does both (or _materialize)
+                s.scale, s.shift, s.mean, s.invstd = s.par[0], s.par[1], s.par[2], s.par[3]
+            elif s.dual is not None:
+                # the two BatchNorms' finalize launches depend on their own GEMMs only: one table-driven launch for both (inside a lock-step cache; else one after the other)
+                d = s.dual
+                s.scale, s.shift, s.mean, s.invstd = self.lockstep("bn.dual", [lambda: self._bn_forward(d.bn, d.bd, d.par, d.psum, d.psq, d.nblk),
+                                                                               lambda: self._bn_forward(bn, s.bd, s.par, s.psum, s.psq, s.nblk)])[1]
+                residual.deferred = None
+            else:
+                s.scale, s.shift, s.mean, s.invstd = self._bn_forward(bn, s.bd, s.par, s.psum, s.psq, s.nblk, bias)
         elif bias is not None:
             s.shift = self._padded_bias(bias, s.Cout, s.Cp)
         s.y_dt = self.dt if y_dt is None else y_dt
-        self._conv_output(s, out)
+        if bn is not None and s.defer:
+            s.out, s.y2, s.pidx, s.ncopy = Act(self, s.raw, s.Cout, s.gw_o, s.gwp_o, self.dt), None, None, s.Cp
+            s.out.deferred = s
+        else:
+            self._conv_output(s, out)
         if not self.need_grad:
             return s.out if s.y2 is None else (s.out, s.y2)
         # the BatchNorm-backward statistics of this output's gradient can be taken by the dgrad GEMM that completes it (x_last of the consumer)
@@ -332,6 +364,8 @@ class ConvOps:
         s.bnb_ok = (core.BNB_EPILOGUE and s.train_bn and not s.fuse_bias and y_C is None and s.y_dt == self.dt and relu in (False, True) and out.ld % V == 0 and s.Cp % V == 0 and not pool)
         if s.bnb_ok:
             out.bnb = Bnb(s.raw, s.par, bool(relu), out.t if residual is not None else None)
+            if not relu and residual is None:
+                out.prod = s          # a residual candidate: see _bn_backward_dual
             if (residual is not None and relu and residual.bnb is not None and not residual.bnb.relu and residual.bnb.ymask is None and residual.bnb.split == 0 and residual.parent is None and residual.Cp == s.Cp):
                 out.bnb.res = residual          # (only as this op's residual operand: Bottle2neck's downsample branch)
         self.record(partial(self._conv_bwd, s))
@@ -340,8 +374,11 @@ class ConvOps:
     def _conv_bwd(self, s):
         """Backward of conv_bn_act: incoming gradient -> BatchNorm backward (or bias only) -> gate -> bias gradient -> weight gradient -> data gradient."""
         x, s.st = s.x, _stream()
+        s.out.prod = None          # (the link back to this record has served: no reference cycle survives the backward pass)
         self._bwd_incoming(s)
-        if s.train_bn:          # in the form the incoming gradient allows: per pooling quad, on statistics dgrad epilogues left, or plain
+        if s.train_bn and s.draw_done is not None:
+            bias_done = s.bias is None          # (the backward of the op this output was the residual of has formed s.draw, with this BatchNorm's parameter gradients: _bn_backward_dual)
+        elif s.train_bn:          # in the form the incoming gradient allows: per pooling quad, on statistics dgrad epilogues left, or plain
             coef, sinks = self.fbuf(3 * s.Cp), self._bn_sinks(s.bn)
             segs = s.out.find_bstats() if (s.bnb_ok and s.dy.stride(2) % s.V == 0) else None
             if s.quad:
@@ -372,6 +409,13 @@ class ConvOps:
             self._dgrad_small_cin(s)
         else:
             self._dgrad_gemm(s)
+
+    def _materialize(self, a):
+        """Write the deferred BatchNorm output `a` after all (a consumer whose output pass cannot normalise it on the fly): its finalize and its normalise pass, as conv_bn_act would have run them."""
+        d, a.deferred = a.deferred, None
+        self._bn_forward(d.bn, d.bd, d.par, d.psum, d.psq, d.nblk)
+        a.t = self.empty(d.N, d.OH, d.OW, d.Cp)
+        call.pn2_affine_act(self.dt, _p(d.raw), d.raw_ld, self.dt, a.ptr, a.ld, d.M, d.Cp, _p(d.scale), _p(d.shift), C.c_void_p(0), 0, 0, d.st)
 
     def _conv_geometry(self, x, conv, out_map):
         """-> the per-call record of conv_bn_act: geometry and layouts (Cp: the padded OUTPUT width; k: as _conv_desc takes it; V: elements per 16-byte vector); the steps add what they share (operands, wp / pd, raw, par, out ...)."""
@@ -485,6 +529,9 @@ class ConvOps:
             if tee is not None and residual is None and y_dt == self.dt and s.ncopy == Cp and core.TEE_CONCAT and tee[0].dt == self.dt and not (tee[1] % V or tee[0].ld % V or out.ld % V or raw_ld % V or Cp % V):
                 call.pn2_affine_act_tee(self.dt, _p(raw), raw_ld, out.ptr, out.ld, M, Cp, _p(s.scale), _p(s.shift), _relu_code(s.relu), tee[0].ptr, tee[0].ld, tee[1], st)
                 tee = None
+            elif s.dual is not None:          # the residual is a BatchNorm output that was never written: both operands normalised here
+                d = s.dual
+                call.pn2_affine_act_dual(self.dt, _p(raw), raw_ld, _p(s.scale), _p(s.shift), _p(d.raw), d.raw_ld, _p(d.scale), _p(d.shift), out.ptr, out.ld, M, Cp, _relu_code(s.relu), st)
             else:
                 call.pn2_affine_act(self.dt, _p(raw), raw_ld, y_dt, out.ptr, out.ld, M, s.ncopy, _p(s.scale), _p(s.shift),
                                     residual.ptr if residual is not None else C.c_void_p(0), residual.ld if residual is not None else 0, _relu_code(s.relu), st)
@@ -515,7 +562,7 @@ class ConvOps:
             call.pn2_maxpool3x3s2_bwd(self.dt, _p(dy), dy.stride(2), _p(s.pidx), _p(dyf), Cp, N, OH, OW, Cp, out.H, out.W, st)
             dy = dyf
         s.dy, s.dt_dy, s.Cdy = dy, out.dt, s.ncopy
-        s.draw = self.empty(N, OH, OW, Cp)
+        s.draw = s.draw_done if s.draw_done is not None else self.empty(N, OH, OW, Cp)
         s.ymask, s.msc, s.msh = (out if relu else None), None, None
         s.r6 = 1 if relu == 2 else 0          # relu: False / True (ReLU) / 2 (ReLU6: the mask also drops the saturated y == 6)
         if (s.bnb_ok or s.pool) and relu and s.residual is None and dy.stride(2) % V == 0:
@@ -552,8 +599,38 @@ class ConvOps:
                                        _p(msc[c0:]) if msc is not None else nul, _p(s.msh[c0:]) if msc is not None else nul, s.r6, st)
             sg.c0[k_], sg.nblk[k_], sg.ldp[k_], sg.p1[k_], sg.p2[k_] = c0, nb_, ldp, p1.data_ptr(), p2.data_ptr()
             self._keep.append((p1, p2))
+        rg, racc = self._bwd_residual_sink(s)
+        if self._bn_backward_dual(s, sg, coef, sinks, rg):
+            return
         call.pn2_bn_bwd_finalize_seg(C.byref(sg), C.byref(s.bd), _p(s.bn.weight), _p(s.invstd), _p(sinks[0]), _p(sinks[1]), sinks[2], _p(coef), st)
-        self._bn_bwd_apply(s, coef, s.draw, *self._bwd_residual_sink(s))
+        self._bn_bwd_apply(s, coef, s.draw, rg, racc)
+
+    def _bn_backward_dual(self, s, sg, coef, sinks, rg):
+        """BatchNorm + residual + ReLU whose residual is a BatchNorm output without activation (Bottle2neck's bn3 and downsample BatchNorm): when the dgrad epilogue that stored the
+        masked gradient dz left the backward sums of BOTH (PN2_RES_STATS) and dz is the residual's gradient buffer, the two finalize launches go out as one table and one pass
+        (pn2_bn_bwd_apply_dual) reads dz once for both raw gradients; the residual's producer record (Act.prod) then finds its own in draw_done.  -> whether it ran."""
+        r, dy, V = s.residual, s.dy, s.V
+        if not (core.DUAL_BNB_APPLY and r is not None and s.out.bnb is not None and s.out.bnb.res is r and s.out.grad_masked and rg is None and r.grad is dy
+                and s.ymask is None and s.msc is None and s.dt_dy == self.dt and s.Cdy == s.Cp and dy.stride(2) % V == 0 and s.Cp % V == 0 and s.raw_ld % V == 0
+                and r.prod is not None and r.prod.draw_done is None and (r.M, r.Cp, r.dt) == (s.M, s.Cp, self.dt) and r.prod.raw_ld % V == 0):
+            return False
+        rsegs = r.find_bstats()
+        if len(rsegs) != 1 or rsegs[0][2] is None:
+            return False
+        st, d = s.st, r.prod
+        _c0, _nc, q1, q2, nb_, ldp = rsegs[0]
+        sg_r = capi.BnSegs()
+        sg_r.nseg, sg_r.c0[0], sg_r.nblk[0], sg_r.ldp[0], sg_r.p1[0], sg_r.p2[0] = 1, 0, nb_, ldp, q1.data_ptr(), q2.data_ptr()
+        self._keep.append((q1, q2))
+        coef_r, sinks_r = self.fbuf(3 * r.Cp), self._bn_sinks(d.bn)
+        self.lockstep("bnb.dual", [
+            lambda: call.pn2_bn_bwd_finalize_seg(C.byref(sg), C.byref(s.bd), _p(s.bn.weight), _p(s.invstd), _p(sinks[0]), _p(sinks[1]), sinks[2], _p(coef), st),
+            lambda: call.pn2_bn_bwd_finalize_seg(C.byref(sg_r), C.byref(d.bd), _p(d.bn.weight), _p(d.invstd), _p(sinks_r[0]), _p(sinks_r[1]), sinks_r[2], _p(coef_r), st)])
+        draw_r = self.empty(r.N, r.H, r.W, r.Cp)
+        call.pn2_bn_bwd_apply_dual(self.dt, _p(dy), dy.stride(2), s.M, s.Cp, _p(s.raw), s.raw_ld, _p(s.mean), _p(s.invstd), _p(coef), _p(s.draw), s.Cp,
+                                   _p(d.raw), d.raw_ld, _p(d.mean), _p(d.invstd), _p(coef_r), _p(draw_r), r.Cp, st)
+        d.draw_done = draw_r
+        return True
 
     def _bn_backward_plain(self, b, mods, draw=None, coef=None, sinks=None, res_sink=None):
         """The plain BatchNorm backward of conv_bn_act, conv_bn_multi and EncoderOps.bn_after: one reduce pass over the operands b (st, dy, dt_dy, Cdy, ymask, raw, raw_ld, M, Cp, mean, invstd, msc, msh, r6), one finalize per

@@ -27,6 +27,10 @@ def _bytes(name, a):
         if name == "pn2_bn_bwd_apply":
             dt, dt_dy, Cdy, y, M, Cp, dres = a[0], a[1], a[4], a[5], a[10], a[11], a[17]
             return M * (Cdy * _EL[dt_dy] + Cp * _EL[dt] * (2 + (1 if y.value else 0) + (1 if dres.value else 0)))
+        if name == "pn2_affine_act_dual":
+            return a[11] * a[12] * _EL[a[0]] * 3            # both raw tensors in, y out
+        if name == "pn2_bn_bwd_apply_dual":
+            return a[3] * a[4] * _EL[a[0]] * 5              # dz and both raw tensors in, both gradients out
         if name == "pn2_affine_act_sum":
             dt, M, C = a[0], a[5], a[6]
             return M * C * _EL[dt] * 4                      # raw + the other operand in, y and y + operand out
@@ -285,7 +289,7 @@ def measure_step(trainer, x, m, dtype, config=None):
     roofline["conv_classes"] = {k: {"ms": round(v[0], 3), "launches": v[1], "TFLOPs": round(v[2] / (v[0] * 1e-3) / 1e12, 1), "frac": round(v[2] / (v[0] * 1e-3) / 1e12 / peak_tf, 4)}
                                 for k, v in sorted(cls.items(), key=lambda kv: -kv[1][0])}
     # the BatchNorm family: HBM-bound streaming passes + the per-layer finalisation launches
-    bn_names = ("pn2_affine_act", "pn2_affine_act_sum", "pn2_affine_multi", "pn2_bn_finalize", "pn2_bn_finalize_multi", "pn2_bn_bwd_reduce", "pn2_bn_bwd_reduce_multi",
+    bn_names = ("pn2_affine_act", "pn2_affine_act_sum", "pn2_affine_act_dual", "pn2_bn_bwd_apply_dual", "pn2_affine_multi", "pn2_bn_finalize", "pn2_bn_finalize_multi", "pn2_bn_bwd_reduce", "pn2_bn_bwd_reduce_multi",
                 "pn2_bn_bwd_finalize", "pn2_bn_bwd_finalize_seg", "pn2_bn_bwd_finalize_multi", "pn2_bn_bwd_apply", "pn2_bn_bwd_apply_multi")
     bn = [agg[k] for k in bn_names if k in agg]
     if bn:
