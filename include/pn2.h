@@ -487,6 +487,24 @@ int pn2_mutation_loss_fwd(const float* const* fg, const float* const* bg, const 
 int pn2_mutation_loss_bwd(const float* const* fg, const float* const* bg, float* const* dfg, float* const* dbg, const long long* label, const float* bg_mask,
                           int N, long long HW, int K, float lc1, float lc2, float lc3, const float* sums, float gscale, void* stream);
 
+/* The same dual loss (EMCAD/trainer.py:109-140) for 2 <= K <= 9 classes and every supervision mode: the sum runs over the subsets SELECTED by `subsets`, the
+ * 15-bit mask of pn2_seg_loss_* below (bit s-1 selects subset s, bit i of s: fg_i and bg_i are in the sums; 'mutation' 0x7FFF, 'deep_supervision' 0x008B,
+ * last map only 0x0080).  Dice is the mean over the K classes (eps 1e-5), BCE the mean over N*K*H*W.
+ * fg[4] / bg[4] (host arrays of device pointers): [N][H][W][K] fp32; label [N][H][W] int64 in 0..K-1; bg_mask [N][K][H][W] fp32.
+ * partial [pn2_mutation_loss_blocks(N*HW)][pn2_dual_loss_width(K)] scratch (rows of 16-byte-aligned floats: block rows, then the group rows in double);
+ * sums [pn2_dual_loss_width(K)] = 15 x (CE, BCE, I[K], Z[K]) then the label histogram T[K], summed over the pixels, kept for the backward - the columns of an
+ * unselected subset are zeros; loss[1].
+ * Backward: dfg[i] / dbg[i] = gscale * d loss / d map, same layout (written, not accumulated; exact zeros for a map in no selected subset - such a map is
+ * never read into a sum, whatever it holds).
+ * pn2_dual_loss_width: 15 * (2 + 2K) + K, -1 outside 2 <= K <= 9.  -1: a null pointer; -2: subsets == 0, bits above 15, K outside 2..9, N or HW < 1 (nothing
+ * is launched).  With K = 9 and subsets = 0x7FFF: the bits of pn2_mutation_loss_fwd / _bwd (the backward then runs
+ * that entry's kernel). */
+int pn2_dual_loss_width(int K);
+int pn2_dual_loss_fwd(const float* const* fg, const float* const* bg, unsigned subsets, const long long* label, const float* bg_mask, int N, long long HW, int K,
+                      float lc1, float lc2, float lc3, float* partial, float* sums, float* loss, void* stream);
+int pn2_dual_loss_bwd(const float* const* fg, const float* const* bg, float* const* dfg, float* const* dbg, unsigned subsets, const long long* label,
+                      const float* bg_mask, int N, long long HW, int K, float lc1, float lc2, float lc3, const float* sums, float gscale, void* stream);
+
 /* EMCAD/trainer.py:141-153 (single supervision, EMCADNet with dual=False) with utils/utils.py:102-138 (DiceLoss, softmax=True): sum over the SELECTED
  * non-empty subsets s of the 4 maps of   w_ce * CrossEntropy(sum_{i in s} P_i, label) + w_dice * DiceLoss(softmax(sum_{i in s} P_i), label).
  * subsets: 15-bit mask, bit s-1 selects subset s, bit i of s means map i is in the sum - trainer.py:114-119: 'mutation' 0x7FFF (powerset),

@@ -996,7 +996,187 @@ __global__ __launch_bounds__(256) void sloss_bwd_k(sl_maps m, unsigned subsets, 
         for (int k = 0; k < K; ++k) m.d[i][p * K + k] = gf[i][k];
 }
 
-// the built class counts of the single-supervision loss: f(Int<K>) for 2 <= K <= 9, -2 for any other
+// ------------------------------------------------------------------------------------------ dual-supervision loss, K = 2..9 classes, selected subsets
+// EMCAD/trainer.py:109-140 (dual) in every supervision mode: mloss_*_k with the subsets that are scored as sloss_*_k's run-time 15-bit mask, on the same ce_dice_*
+// core, MLW<K> rows, reduce kernel and Dice term.  The forward keeps mloss_fwd_k's unrolled subset loop, every subset under one scalar branch on its mask bit (which
+// maps a subset sums is then fixed at compile time: a map outside every selected subset is loaded and never read, whatever it holds); the backward's foreground
+// loop is rolled as in mloss_bwd_k, with sloss_bwd_k's selects instead of 0 / 1 multiplies.  Sums, their order and their values are those of mloss_*_k: with
+// K = 9 and all 15 subsets the forward gives the bits of mloss_fwd_k<9>.  The backward does not (the compiler fuses other multiply-adds, one ulp here and there);
+// pn2_dual_loss_bwd sends that one case to mloss_bwd_k<9> itself.
+template <int K>
+__global__ __launch_bounds__(256) void dloss_fwd_k(ml_maps m, unsigned subsets, const long long* __restrict__ label, const float* __restrict__ bgm, size_t NP, size_t HW,
+                                                   float* __restrict__ partial) {
+    constexpr int W = MLW<K>::W, NV = MLW<K>::NV;
+    __shared__ float red[16][NV];          // the 16 DPP-row partials of the block (see mloss_fwd_k)
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, rrow = wid * 4 + (lane >> 4);
+    const bool rlead = (lane & 15) == 0;
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = p < NP;
+    const size_t n = ok ? p / HW : 0, hw = ok ? p % HW : 0;
+    int lab = -1;
+    {       // ---- foreground maps: CE, intersect and sum p^2 per class
+        float f[4][K];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int k = 0; k < K; ++k) f[i][k] = 0.f;
+        if (ok) {
+            lab = (int)label[p];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int k = 0; k < K; ++k) f[i][k] = m.fg[i][p * K + k];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {          // label histogram (sum of target^2 per class), once
+            const float t = row16_sum((ok && lab == k) ? 1.f : 0.f);
+            if (rlead) red[rrow][ML_NS * W + k] = t;
+        }
+#pragma unroll
+        for (int s = 1; s <= ML_NS; ++s) {
+            if (!(subsets >> (s - 1) & 1)) continue;
+            float z[K], v[W];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                z[k] = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) if (s >> i & 1) z[k] += f[i][k];
+            }
+            v[0] = ce_dice_fwd<K>(z, lab, v + 2, v + 2 + K); v[1] = 0.f;
+#pragma unroll
+            for (int j = 0; j < W; ++j) if (j != 1) v[j] = row16_sum(ok ? v[j] : 0.f);
+            if (rlead) {
+#pragma unroll
+                for (int j = 0; j < W; ++j) if (j != 1) red[rrow][(s - 1) * W + j] = v[j];
+            }
+        }
+    }
+    {       // ---- background maps: BCE, class by class with four logits live
+        float bce[ML_NS];
+#pragma unroll
+        for (int s = 0; s < ML_NS; ++s) bce[s] = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float b[4] = {0.f, 0.f, 0.f, 0.f}, mk = 0.f;
+            if (ok) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) b[i] = m.bg[i][p * K + k];
+                mk = bgm[(n * K + k) * HW + hw];
+            }
+#pragma unroll
+            for (int s = 1; s <= ML_NS; ++s) {
+                if (!(subsets >> (s - 1) & 1)) continue;
+                float zb = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) if (s >> i & 1) zb += b[i];
+                bce[s - 1] += fmaxf(zb, 0.f) - zb * mk + __logf(1.f + __expf(-fabsf(zb)));
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < ML_NS; ++s) {
+            if (!(subsets >> s & 1)) continue;
+            const float t = row16_sum(ok ? bce[s] : 0.f);
+            if (rlead) red[rrow][s * W + 1] = t;
+        }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < NV; j += 256) {
+        const int s0 = j / W;          // == ML_NS for the histogram columns
+        float t = 0.f;
+        if (s0 >= ML_NS || (subsets >> s0 & 1)) {          // an unselected subset's columns were never written: exact zeros
+#pragma unroll
+            for (int i = 0; i < 16; ++i) t += red[i][j];
+        }
+        partial[(size_t)blockIdx.x * NV + j] = t;
+    }
+}
+
+// sums[15 * (2 + 2K) + K] (double-accumulated over the group rows) and the scalar loss over the selected subsets
+__global__ void dloss_finalize_k(const double* __restrict__ grp, int ngrp, int K, unsigned subsets, float* __restrict__ sums, float* __restrict__ loss, double npix,
+                                 float lc1, float lc2, float lc3) {
+    const int W = 2 + 2 * K, NV = ML_NS * W + K;
+    __shared__ double sh[MLW<9>::NV];
+    group_sums(grp, ngrp, NV, sh, sums);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int s = 0; s < ML_NS; ++s) {
+            if (!(subsets >> s & 1)) continue;
+            const double ce = sh[s * W] / npix, bce = sh[s * W + 1] / (npix * K);
+            const double dice = dice_sum(sh, K, s * W + 2, s * W + 2 + K, ML_NS * W);
+            tot += lc1 * ce + lc2 * dice / K + lc3 * bce;
+        }
+        loss[0] = (float)tot;
+    }
+}
+
+// gradients of the eight maps; a map in no selected subset gets exact zeros, written
+template <int K>
+__global__ __launch_bounds__(256) void dloss_bwd_k(ml_maps m, unsigned subsets, const long long* __restrict__ label, const float* __restrict__ bgm, size_t NP, size_t HW,
+                                                   const float* __restrict__ sums, float gscale, float lc1, float lc2, float lc3) {
+    __shared__ float tA[ML_NS * K], tB[ML_NS * K];
+    dice_coef<K>(sums, MLW<K>::W, 2, gscale * lc2 / K, tA, tB);
+    __syncthreads();
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= NP) return;
+    const int lab = (int)label[p];
+    const size_t n = p / HW, hw = p % HW;
+    const float wce = gscale * lc1 / (float)NP, wbce = gscale * lc3 / ((float)NP * K);
+    {       // ---- foreground maps: d(CE + Dice) / d logits
+        float f[4][K], gf[4][K];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int k = 0; k < K; ++k) { f[i][k] = m.fg[i][p * K + k]; gf[i][k] = 0.f; }
+#pragma unroll 1
+        for (int s = 1; s <= ML_NS; ++s) {
+            if (!(subsets >> (s - 1) & 1)) continue;
+            const bool b0 = s & 1, b1 = s & 2, b2 = s & 4, b3 = s & 8;
+            float z[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) z[k] = (((b0 ? f[0][k] : 0.f) + (b1 ? f[1][k] : 0.f)) + (b2 ? f[2][k] : 0.f)) + (b3 ? f[3][k] : 0.f);
+            float mx, pr[K], g[K], dot = 0.f;
+            const float inv = __builtin_amdgcn_rcpf(exp_shifted<K>(z, pr, mx));
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                pr[k] *= inv;
+                g[k] = dice_dp(lab == k ? tA[(s - 1) * K + k] : 0.f, tB[(s - 1) * K + k], pr[k]);
+                dot += g[k] * pr[k];
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float dz = ce_dice_dz(pr[k], lab == k, g[k], dot, wce);
+                gf[0][k] += b0 ? dz : 0.f; gf[1][k] += b1 ? dz : 0.f; gf[2][k] += b2 ? dz : 0.f; gf[3][k] += b3 ? dz : 0.f;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int k = 0; k < K; ++k) m.dfg[i][p * K + k] = gf[i][k];
+    }
+    // ---- background maps: d BCE / d logits, class by class (which maps a subset sums is fixed at compile time here)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float b[4], gb[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b[i] = m.bg[i][p * K + k];
+        const float mk = bgm[(n * K + k) * HW + hw];
+#pragma unroll
+        for (int s = 1; s <= ML_NS; ++s) {
+            if (!(subsets >> (s - 1) & 1)) continue;
+            float zb = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) if (s >> i & 1) zb += b[i];
+            const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-zb)), dzb = wbce * (sg - mk);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) if (s >> i & 1) gb[i] += dzb;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) m.dbg[i][p * K + k] = gb[i];
+    }
+}
+
+// the built class counts of the single-supervision and the dual-supervision loss: f(Int<K>) for 2 <= K <= 9, -2 for any other
 template <typename F>
 int with_seg_classes(int K, F f) {
     switch (K) {
@@ -1328,6 +1508,43 @@ int pn2_seg_loss_bwd(const float* const* maps, float* const* dmaps, unsigned sub
     return with_seg_classes(K, [&](auto k) {
         return pn2_launch<sloss_bwd_k<decltype(k)::value>>(dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, m, subsets, label, NP, sums,
                                                            gscale, w_ce, w_dice);
+    });
+}
+
+/* EMCAD/trainer.py:109-140 (dual) in every supervision mode: pn2_mutation_loss_* for 2 <= K <= 9 over the subsets selected by `subsets` (the mask of pn2_seg_loss_*).
+ * Buffers as there, rows of pn2_dual_loss_width(K) values; the columns of an unselected subset are zeros. */
+int pn2_dual_loss_width(int K) { const int wd = with_seg_classes(K, [](auto k) { return MLW<decltype(k)::value>::NV; }); return wd > 0 ? wd : -1; }
+
+int pn2_dual_loss_fwd(const float* const* fg, const float* const* bg, unsigned subsets, const long long* label, const float* bg_mask, int N, long long HW, int K,
+                      float lc1, float lc2, float lc3, float* partial, float* sums, float* loss, void* stream) {
+    if (!fg || !bg || !label || !bg_mask || !partial || !sums || !loss) return -1;
+    if (!seg_loss_args_ok(subsets, N, HW, K)) return -2;
+    ml_maps m;
+    for (int i = 0; i < 4; ++i) { m.fg[i] = fg[i]; m.bg[i] = bg[i]; m.dfg[i] = nullptr; m.dbg[i] = nullptr; if (!fg[i] || !bg[i]) return -1; }
+    const size_t NP = (size_t)N * HW;
+    hipStream_t st = (hipStream_t)stream;
+    double* grp; int ngrp;
+    if (int rc = with_seg_classes(K, [&](auto k) {
+            return pn2_launch<dloss_fwd_k<decltype(k)::value>>(dim3(ml_blocks((long long)NP)), dim3(256), 0, 0, st, m, subsets, label, bg_mask, NP, (size_t)HW, partial); }))
+        return rc;
+    if (int rc = loss_reduce(partial, NP, pn2_dual_loss_width(K), st, grp, ngrp)) return rc;
+    return pn2_launch<dloss_finalize_k>(dim3(1), dim3(256), 0, 0, st, grp, ngrp, K, subsets, sums, loss, (double)NP, lc1, lc2, lc3);
+}
+
+int pn2_dual_loss_bwd(const float* const* fg, const float* const* bg, float* const* dfg, float* const* dbg, unsigned subsets, const long long* label,
+                      const float* bg_mask, int N, long long HW, int K, float lc1, float lc2, float lc3, const float* sums, float gscale, void* stream) {
+    if (!fg || !bg || !dfg || !dbg || !label || !bg_mask || !sums) return -1;
+    if (!seg_loss_args_ok(subsets, N, HW, K)) return -2;
+    ml_maps m;
+    for (int i = 0; i < 4; ++i) { m.fg[i] = fg[i]; m.bg[i] = bg[i]; m.dfg[i] = dfg[i]; m.dbg[i] = dbg[i]; if (!fg[i] || !bg[i] || !dfg[i] || !dbg[i]) return -1; }
+    const size_t NP = (size_t)N * HW;
+    // K = 9 with all 15 subsets keeps the backward kernel it had: the faster one at 16 x 512^2, and the bits of pn2_mutation_loss_bwd, which
+    // dloss_bwd_k<9> misses by one ulp in some elements (the compiler fuses other multiply-adds there)
+    if (K == 9 && subsets == 0x7FFFu)
+        return pn2_launch<mloss_bwd_k<9>>(dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, m, label, bg_mask, NP, (size_t)HW, sums, gscale, lc1, lc2, lc3);
+    return with_seg_classes(K, [&](auto k) {
+        return pn2_launch<dloss_bwd_k<decltype(k)::value>>(dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, m, subsets, label, bg_mask, NP,
+                                                           (size_t)HW, sums, gscale, lc1, lc2, lc3);
     });
 }
 

@@ -234,65 +234,8 @@ def _grad_ptrs(outs):
     return ptrs
 
 
-def _mutation_width(K):
-    wd = call.pn2_mutation_loss_width(K)
-    if wd < 0:
-        raise RuntimeError(f"pn2.mutation_loss is built for K = 9 classes (got {K})")
-    return wd
-
-
-class _MutationLoss(torch.autograd.Function):
-    """The multi-class dual-supervision loss of EMCAD/trainer.py:106-140 as two kernels (pn2_mutation_loss_fwd / _bwd)."""
-
-    @staticmethod
-    def forward(ctx, label, bg_mask, lc, *maps):
-        if not maps[0].is_cuda:
-            raise RuntimeError("pn2.mutation_loss needs GPU tensors (no CPU fallback)")
-        N, K, H, W = maps[0].shape
-        nhwc = _nhwc(maps)
-        lab = label.long().contiguous()
-        bgm = bg_mask.float().contiguous()
-        partial, sums, loss = _loss_scratch(N * H * W, _mutation_width(K), _empty_on(maps[0].device))
-        call.pn2_mutation_loss_fwd(_ptrs(nhwc[:4]), _ptrs(nhwc[4:]), _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(partial), _p(sums), _p(loss), _stream())
-        ctx.save_for_backward(lab, bgm, sums, *nhwc)
-        ctx.meta = (N, K, H, W, lc)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        lab, bgm, sums, *nhwc = ctx.saved_tensors
-        N, K, H, W, lc = ctx.meta
-        grads = [torch.empty_like(t) for t in nhwc]
-        call.pn2_mutation_loss_bwd(_ptrs(nhwc[:4]), _ptrs(nhwc[4:]), _ptrs(grads[:4]), _ptrs(grads[4:]), _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2],
-                                   _p(sums), 1.0, _stream())
-        return (None, None, None, *[(gr * g).permute(0, 3, 1, 2) for gr in grads])
-
-
-def mutation_forward_backward(eng, outs, label, bg_mask, lc=(0.5, 0.7, 0.3), gscale=1.0):
-    """Trainer path of the same loss: `outs` are the engine's 8 fp32 [N][H][W][K] maps; the loss kernel reads them in place and the backward
-    kernel writes their gradients straight into the activations' gradient buffers (no autograd bridge, no copies).  Returns loss[1]."""
-    N, H, W, K = _engine_maps(outs)
-    wd = _mutation_width(K)
-    lab = label.long().contiguous()
-    bgm = bg_mask.float().contiguous()
-    partial, sums, loss = _loss_scratch(N * H * W, wd, eng.fbuf)
-    fg, bg = _ptrs([o.t for o in outs[:4]]), _ptrs([o.t for o in outs[4:]])
-    st = _stream()
-    call.pn2_mutation_loss_fwd(fg, bg, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(partial), _p(sums), _p(loss), st)
-    dfg, dbg = _grad_ptrs(outs[:4]), _grad_ptrs(outs[4:])
-    call.pn2_mutation_loss_bwd(fg, bg, dfg, dbg, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(sums), float(gscale), st)
-    eng.keep_alive = (lab, bgm)
-    return loss
-
-
-def mutation_loss(outs, label, bg_mask, lc=(0.5, 0.7, 0.3)):
-    """sum over the 15 non-empty subsets s of the 4 scales of lc1*CE(sum fg) + lc2*Dice(softmax(sum fg)) + lc3*BCEWithLogits(sum bg, bg_mask)
-    (EMCAD/trainer.py:106-140, supervision='mutation', dual): outs = the 8 maps EMCADNet returns, label (N,H,W) int, bg_mask (N,K,H,W)."""
-    return _MutationLoss.apply(label, bg_mask, tuple(float(v) for v in lc), *outs)
-
-
-# subsets of the 4 maps the single-supervision trainer scores (EMCAD/trainer.py:114-119) as the kernels' 15-bit mask: bit s-1 selects subset s,
-# bit i of s means map i is in the sum.  'last' is the reference's fallback ss = [[-1]] (any other string there).
+# subsets of the 4 scales the reference's trainers score (EMCAD/trainer.py:114-119) as the loss kernels' 15-bit mask: bit s-1 selects subset s,
+# bit i of s means map i (dual: fg_i and bg_i) is in the sum.  'last' is the reference's fallback ss = [[-1]] (any other string there).
 SEG_SUBSETS = {"mutation": 0x7FFF, "deep_supervision": 0x008B, "last": 0x0080}
 
 
@@ -300,6 +243,76 @@ def _seg_subsets(supervision):
     if supervision not in SEG_SUBSETS:
         raise ValueError(f"unknown supervision {supervision!r} (one of {sorted(SEG_SUBSETS)})")
     return SEG_SUBSETS[supervision]
+
+
+def _mutation_width(K):
+    wd = call.pn2_dual_loss_width(K)
+    if wd < 0:
+        raise RuntimeError(f"pn2.mutation_loss is built for 2 <= K <= 9 classes (got {K})")
+    return wd
+
+
+def _eight(outs):
+    if len(outs) != 8:
+        raise ValueError(f"pn2.mutation_loss takes the 8 maps of a dual EMCADNet, 4 foreground then 4 background (got {len(outs)})")
+
+
+class _MutationLoss(torch.autograd.Function):
+    """The multi-class dual-supervision loss of EMCAD/trainer.py:106-140 as two kernels (pn2_dual_loss_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, label, bg_mask, lc, subsets, *maps):
+        if not maps[0].is_cuda:
+            raise RuntimeError("pn2.mutation_loss needs GPU tensors (no CPU fallback)")
+        N, K, H, W = maps[0].shape
+        wd = _mutation_width(K)
+        nhwc = _nhwc(maps)
+        lab = label.long().contiguous()
+        bgm = bg_mask.float().contiguous()
+        partial, sums, loss = _loss_scratch(N * H * W, wd, _empty_on(maps[0].device))
+        call.pn2_dual_loss_fwd(_ptrs(nhwc[:4]), _ptrs(nhwc[4:]), subsets, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(partial), _p(sums), _p(loss), _stream())
+        ctx.save_for_backward(lab, bgm, sums, *nhwc)
+        ctx.meta = (N, K, H, W, lc, subsets)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lab, bgm, sums, *nhwc = ctx.saved_tensors
+        N, K, H, W, lc, subsets = ctx.meta
+        grads = [torch.empty_like(t) for t in nhwc]
+        call.pn2_dual_loss_bwd(_ptrs(nhwc[:4]), _ptrs(nhwc[4:]), _ptrs(grads[:4]), _ptrs(grads[4:]), subsets, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2],
+                               _p(sums), 1.0, _stream())
+        return (None, None, None, None, *[(gr * g).permute(0, 3, 1, 2) for gr in grads])
+
+
+def mutation_forward_backward(eng, outs, label, bg_mask, lc=(0.5, 0.7, 0.3), gscale=1.0, supervision="mutation"):
+    """Trainer path of the same loss: `outs` are the engine's 8 fp32 [N][H][W][K] maps; the loss kernel reads them in place and the backward
+    kernel writes their gradients straight into the activations' gradient buffers (no autograd bridge, no copies; exact zeros for a map outside
+    every subset).  Returns loss[1]."""
+    subsets = _seg_subsets(supervision)
+    _eight(outs)
+    N, H, W, K = _engine_maps(outs)
+    wd = _mutation_width(K)
+    lab = label.long().contiguous()
+    bgm = bg_mask.float().contiguous()
+    partial, sums, loss = _loss_scratch(N * H * W, wd, eng.fbuf)
+    fg, bg = _ptrs([o.t for o in outs[:4]]), _ptrs([o.t for o in outs[4:]])
+    st = _stream()
+    call.pn2_dual_loss_fwd(fg, bg, subsets, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(partial), _p(sums), _p(loss), st)
+    dfg, dbg = _grad_ptrs(outs[:4]), _grad_ptrs(outs[4:])
+    call.pn2_dual_loss_bwd(fg, bg, dfg, dbg, subsets, _p(lab), _p(bgm), N, H * W, K, lc[0], lc[1], lc[2], _p(sums), float(gscale), st)
+    eng.keep_alive = (lab, bgm)
+    return loss
+
+
+def mutation_loss(outs, label, bg_mask, lc=(0.5, 0.7, 0.3), supervision="mutation"):
+    """sum over the subsets s that `supervision` selects of lc1*CE(sum_{i in s} fg_i) + lc2*Dice(softmax(sum fg_i)) + lc3*BCEWithLogits(sum_{i in s} bg_i, bg_mask)
+    (EMCAD/trainer.py:106-140, dual): outs = the 8 maps a dual EMCADNet returns, 4 foreground then 4 background (N,K,H,W), 2 <= K <= 9; label (N,H,W)
+    int, bg_mask (N,K,H,W).  supervision: 'mutation' (all 15 non-empty subsets of the 4 scales), 'deep_supervision' (each scale on its own), 'last'
+    (the last scale only)."""
+    subsets = _seg_subsets(supervision)
+    _eight(outs)
+    return _MutationLoss.apply(label, bg_mask, tuple(float(v) for v in lc), subsets, *outs)
 
 
 def _seg_width(K):

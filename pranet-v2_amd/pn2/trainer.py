@@ -53,7 +53,7 @@ class Trainer:
                                (label, bg_mask) pair is accepted, bg_mask is not used).
         loss_weights: (lc1, lc2, lc3) of the dual loss, default (0.5, 0.7, 0.3); (w_ce, w_dice) of the single-supervision loss, default (0.3, 0.7).
         supervision: which subsets of the 4 maps the single-supervision loss scores - "mutation" (all 15), "deep_supervision" (each map alone),
-                 "last" (the last map); the dual loss is built for "mutation" only.
+                 "last" (the last map); a dual model is stepped with "mutation" only (pn2.loss.mutation_loss takes the other two).
         hot: the parameters the step trains (default model.hot_parameters()).
         force_dp: run the data-parallel machinery (bucket hooks, graph segments, asynchronous all-reduce) even on a 1-rank process group - how the
                  RCCL path is exercised on a single GPU (tests/test_gpu_dp.py, bench.py --dp1; also PN2_DP_FORCE=1)."""
@@ -64,7 +64,7 @@ class Trainer:
         if supervision not in L.SEG_SUBSETS:
             raise ValueError(f"unknown supervision {supervision!r} (one of {sorted(L.SEG_SUBSETS)})")
         if supervision != "mutation" and not self.single:
-            raise ValueError(f"supervision={supervision!r} needs loss='mutation' and a single-supervision EMCADNet (dual=False): the dual loss is built for 'mutation' only")
+            raise ValueError(f"supervision={supervision!r} needs loss='mutation' and a single-supervision EMCADNet (dual=False): Trainer steps a dual model with 'mutation' only")
         if loss_weights is None:
             loss_weights = (0.3, 0.7) if self.single else (0.5, 0.7, 0.3)
         self.loss_kind, self.supervision, self.loss_weights, self.weight_decay = loss, supervision, tuple(float(v) for v in loss_weights), float(weight_decay)

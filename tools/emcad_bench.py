@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """BASELINE config 5 on one GPU: EMCADNet(dual, K=9, pvt_v2_b2) forward + the reference trainer's 15-subset loss (torch ops, as trainer.py:106-140
 runs them) + backward + optimizer step through the nn.Module surface.  Usage: [EMCAD_ENCODER=pvt_v2_b0] emcad_bench.py [batch] [size] [steps]
-EMCAD_DUAL=0: the single-supervision model (EMCADNet(dual=False), 4 maps, CE + Dice of trainer.py:141-153); EMCAD_SUPERVISION = mutation | deep_supervision | last
-and EMCAD_CLASSES = 2..9 then apply."""
+EMCAD_DUAL=0: the single-supervision model (EMCADNet(dual=False), 4 maps, CE + Dice of trainer.py:141-153).  EMCAD_CLASSES = 2..9 and EMCAD_SUPERVISION =
+mutation | deep_supervision | last apply to both models; with EMCAD_TRAINER=1 the dual model takes 'mutation' only (pn2.trainer.Trainer refuses the others)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "pranet-v2_amd"))
@@ -23,9 +23,11 @@ ENC = "" if ENCODER == "pvt_v2_b2" else f" {ENCODER}"
 DUAL = os.environ.get("EMCAD_DUAL", "1") != "0"
 SUP = os.environ.get("EMCAD_SUPERVISION", "mutation")
 K = int(os.environ.get("EMCAD_CLASSES", "9"))
-if DUAL and (SUP != "mutation" or K != 9):
-    sys.exit("EMCAD_SUPERVISION / EMCAD_CLASSES apply to the single-supervision model (EMCAD_DUAL=0)")
-TAG = "dual K=9" if DUAL else f"single ({SUP}) K={K}"
+if not 2 <= K <= 9 or SUP not in ("mutation", "deep_supervision", "last"):
+    sys.exit("EMCAD_CLASSES is 2..9, EMCAD_SUPERVISION one of mutation | deep_supervision | last")
+if DUAL and SUP != "mutation" and os.environ.get("EMCAD_TRAINER", "0") == "1":
+    sys.exit("EMCAD_TRAINER=1 with the dual model runs EMCAD_SUPERVISION=mutation only")
+TAG = (f"dual K={K}" if SUP == "mutation" else f"dual ({SUP}) K={K}") if DUAL else f"single ({SUP}) K={K}"
 model = EMCADNet(num_classes=K, kernel_sizes=[1, 3, 5], expansion_factor=2, activation="relu6", encoder=ENCODER, pretrain=False, dual=DUAL).cuda().train()
 GRAPH = os.environ.get("EMCAD_GRAPH", "0") == "1"          # replay the whole step (forward, loss, backward, AdamW) from one hipGraph
 opt = torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=1e-4, capturable=GRAPH)
@@ -34,7 +36,7 @@ label = torch.randint(0, K, (bs, size // 16, size // 16), device="cuda")
 label = F.interpolate(label[:, None].float(), size=(size, size), mode="nearest")[:, 0].long()
 bg = torch.stack([(label != k).float() for k in range(K)], 1)
 subsets = [s for s in __import__("itertools").chain.from_iterable(__import__("itertools").combinations(range(4), r) for r in range(1, 5))]
-if not DUAL:
+if SUP != "mutation" or not DUAL:
     subsets = {"mutation": subsets, "deep_supervision": [(i,) for i in range(4)], "last": [(3,)]}[SUP]
 
 
@@ -83,7 +85,7 @@ if TRAINER:
 def step():
     P = model(x, mode="train")
     if FUSED:
-        loss = mutation_loss(P, label, bg) if DUAL else seg_loss(P, label, SUP)
+        loss = mutation_loss(P, label, bg, supervision=SUP) if DUAL else seg_loss(P, label, SUP)
     elif not DUAL:
         loss = 0.0
         for s in subsets:
