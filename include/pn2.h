@@ -436,6 +436,21 @@ int pn2_attn_bwd_blocks(int dt, int B, int heads, int Nq);   /* partial slots pe
 /* out = the forward result (delta = rowsum(dO * out) lets the bf16 MFMA path treat key ranges independently); delta: [B][heads][Nq] fp32 scratch */
 int pn2_attn_bwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, const void* out, int ld_o, const void* dout, int ld_do, const float* lse, void* dq, int ld_dq,
                  void* dkv, int ld_dkv, float* partial, float* delta, int B, int Nq, int Nkv, int heads, int head_dim, float scale, void* stream);
+/* The same attention for 1 <= Nkv <= 4096 (-2 above, and for every geometry the entry points above refuse): the keys are streamed through LDS in
+ * chunks of 128 with an online softmax, so nothing on chip grows with Nkv.  Argument lists, layouts, leading dimensions, dtypes, head dims and the
+ * meaning of lse (row maximum of the scaled scores + log of the sum) are those of pn2_attn_fwd / pn2_attn_bwd; bf16 views with every ld a multiple
+ * of 8 take the MFMA kernels, every other view the scalar ones (no refusal).  The forward needs no workspace.  Backward workspaces, all fp32, sizes
+ * in floats from pn2_attn_long_bwd_workspace(floats[3]):
+ *   floats[0] partial [B][heads][slots][2][128][hd]  dK / dV of one 128-key range per block, slots = pn2_attn_long_bwd_blocks (independent of Nkv)
+ *   floats[1] delta   [B][heads][Nq]                 rowsum(dO * out)
+ *   floats[2] dq_acc  [B][Nq][heads*hd]              dQ summed over the key ranges in fp32, rounded to the storage type once at the end
+ * The key ranges are plain launches in stream order and every sum has a fixed order: two calls give the same bits. */
+int pn2_attn_long_fwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads, int head_dim,
+                      float scale, void* stream);
+int pn2_attn_long_bwd_blocks(int dt, int B, int heads, int Nq);
+int pn2_attn_long_bwd_workspace(int dt, int B, int Nq, int heads, int head_dim, long long* floats);
+int pn2_attn_long_bwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, const void* out, int ld_o, const void* dout, int ld_do, const float* lse, void* dq, int ld_dq,
+                      void* dkv, int ld_dkv, float* partial, float* delta, float* dq_acc, int B, int Nq, int Nkv, int heads, int head_dim, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- EMCAD decoder (multiclass_seg/EMCAD/lib/decoders.py)
  * Memory-bound pieces of config 5; the 1x1 / 3x3 / 7x7 convs are pn2_conv_*, BatchNorm is pn2_bn_* fed by the partial rows below.          */

@@ -11,6 +11,7 @@ from .core import (Act, _PERMS, _p, _stream, rup)
 from .ops_conv import _bn_desc, _relu_code
 
 
+ATTN_SHORT_MAXKV = 256     # pn2_attn_fwd / pn2_attn_bwd keep the whole key set on chip up to here; above it Engine.attention streams (pn2_attn_long_*)
 _DP_KEEP = {}          # (drop probabilities, batch, device) -> [K][N] table of keep probabilities (drop_path_plan)
 
 
@@ -156,6 +157,23 @@ class EncoderOps:
         scale = hd ** -0.5
         o = Act(self, self.empty(q.N, q.H, q.W, Cc), Cc, Cc, Cc, self.dt)
         lse = self.fbuf(B, heads, Nq)
+        if Nkv > ATTN_SHORT_MAXKV:
+            # more keys than the on-chip kernels hold: the streamed family (pn2.h: pn2_attn_long_*), its workspaces from the step's fp32 buffers
+            call.pn2_attn_long_fwd(self.dt, q.ptr, Cc, kv.ptr, 2 * Cc, o.ptr, Cc, _p(lse), B, Nq, Nkv, heads, hd, scale, st)
+
+            def bwd_long():
+                st = _stream()
+                do = o.grad_buf()
+                assert o.grad_written and do.stride(2) == Cc and not q.grad_written and not kv.grad_written
+                n = (C.c_longlong * 3)()
+                call.pn2_attn_long_bwd_workspace(self.dt, B, Nq, heads, hd, n)
+                part, delta, dqacc = self.fbuf(n[0]), self.fbuf(n[1]), self.fbuf(n[2])
+                gq, _ = q.grad_sink()
+                gkv, _ = kv.grad_sink()
+                call.pn2_attn_long_bwd(self.dt, q.ptr, Cc, kv.ptr, 2 * Cc, o.ptr, Cc, _p(do), Cc, _p(lse), _p(gq), Cc, _p(gkv), 2 * Cc, _p(part), _p(delta),
+                                       _p(dqacc), B, Nq, Nkv, heads, hd, scale, st)
+            self.record(bwd_long)
+            return o
         call.pn2_attn_fwd(self.dt, q.ptr, Cc, kv.ptr, 2 * Cc, o.ptr, Cc, _p(lse), B, Nq, Nkv, heads, hd, scale, st)
 
         def bwd():

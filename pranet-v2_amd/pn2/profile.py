@@ -97,10 +97,12 @@ def _shape(name, a):
             return f"{a[6]}x{a[7]}x{a[8]}x{a[9]} flip{a[10]} acc{a[11]} gelu{1 if a[5].value else 0}"
         if name == "pn2_dwconv3x3_wgrad":
             return f"{a[5]}x{a[6]}x{a[7]}x{a[8]} gelu{1 if a[9].value else 0}"
-        if name == "pn2_attn_fwd":
+        if name in ("pn2_attn_fwd", "pn2_attn_long_fwd"):
             return f"B{a[8]} Nq{a[9]} Nkv{a[10]} h{a[11]}"
         if name == "pn2_attn_bwd":
             return f"B{a[16]} Nq{a[17]} Nkv{a[18]} h{a[19]}"
+        if name == "pn2_attn_long_bwd":
+            return f"B{a[17]} Nq{a[18]} Nkv{a[19]} h{a[20]}"
         if name in ("pn2_layernorm_fwd", "pn2_layernorm_bwd"):
             return f"M{a[5]} C{a[6]}"
         if name == "pn2_colsum":

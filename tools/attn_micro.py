@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the spatial-reduction attention kernels, bf16.  Usage: attn_micro.py [head_dim]
+"""Micro-benchmark of the spatial-reduction attention kernels, bf16.  Usage: attn_micro.py [head_dim] | attn_micro.py long [head_dim ...]
+long: the streamed kernels (pn2_attn_long_*) at the shapes of 4 x 1024^2 and 4 x 640^2, each next to the on-chip kernels at 256 keys.
 head_dim 64 (default): the PVTv2-B2 shapes of configs 4 (352^2) and 5 (512^2), bs=16.
 head_dim 32: the PVTv2-B0 shapes (16 x 512^2, 16 x 352^2, 6 x 224^2), each also run at head_dim 64 on the same (B, Nq, Nkv, heads), with two floors:
 the HBM bytes of q / kv / out / lse (forward) and q / kv / out / dO / lse / dq / dkv (backward) at 8 TB/s, and the exp count (B heads Nq Nkv, twice
@@ -63,12 +64,49 @@ def bench(B, Nq, Nkv, heads, hd=64, floors=False):
     return t_f, t_b
 
 
+def bench_long(B, Nq, Nkv, heads, hd):
+    """The streamed family (pn2_attn_long_*) at Nkv keys next to the on-chip family at 256 keys on the same (B, Nq, heads), same process: the figure of
+    merit is time per query x key.  Floors as in bench(): the HBM bytes that have to move once, and the exp count."""
+    dev = "cuda"; st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    Cc = heads * hd
+    q = torch.randn(B, Nq, Cc, device=dev).bfloat16(); kv = torch.randn(B, Nkv, 2 * Cc, device=dev).bfloat16()
+    o = torch.empty_like(q); do = torch.randn_like(q); dq = torch.empty_like(q); dkv = torch.empty_like(kv)
+    lse = torch.empty(B, heads, Nq, device=dev)
+    n = (C.c_longlong * 3)()
+    call.pn2_attn_long_bwd_workspace(BF16, B, Nq, heads, hd, n)
+    part, delta, dqacc = (torch.empty(int(v), device=dev) for v in n)
+    sc = hd ** -0.5
+    t_f = timeit(lambda: call.pn2_attn_long_fwd(BF16, P(q), Cc, P(kv), 2 * Cc, P(o), Cc, P(lse), B, Nq, Nkv, heads, hd, sc, st))
+    t_b = timeit(lambda: call.pn2_attn_long_bwd(BF16, P(q), Cc, P(kv), 2 * Cc, P(o), Cc, P(do), Cc, P(lse), P(dq), Cc, P(dkv), 2 * Cc, P(part), P(delta), P(dqacc),
+                                                B, Nq, Nkv, heads, hd, sc, st))
+    lse_b = 4 * B * heads * Nq
+    hf = (3 * q.numel() * 2 + kv.numel() * 2 + lse_b) / HBM * 1e6
+    hb = (5 * q.numel() * 2 + 2 * kv.numel() * 2 + 2 * lse_b) / HBM * 1e6
+    ex = B * heads * Nq * Nkv / EXP * 1e6
+    print(f"long  B{B} Nq{Nq:6d} Nkv{Nkv:4d} h{heads} hd{hd}: fwd {t_f:8.1f} us | bwd {t_b:8.1f} us | floors fwd HBM {hf:6.1f} exp {ex:6.1f} us, bwd HBM {hb:6.1f} exp {2 * ex:6.1f} us"
+          f" | workspaces partial {n[0] * 4 / 2**20:.1f} delta {n[1] * 4 / 2**20:.1f} dq {n[2] * 4 / 2**20:.1f} MiB")
+    if Nkv > 256:
+        s_f, s_b = bench(B, Nq, 256, heads, hd=hd, floors=True)
+        qk_l, qk_s = B * heads * Nq * Nkv, B * heads * Nq * 256
+        print(f"    per query x key, long / short(256 keys): fwd {(t_f / qk_l) / (s_f / qk_s):.2f}  bwd {(t_b / qk_l) / (s_b / qk_s):.2f}")
+    return t_f, t_b
+
+
+# (B, Nq, Nkv, heads): 4 x 1024^2 (1024 keys in every stage) and 4 x 640^2 (400 keys)
+LONG_SHAPES = [(4, 65536, 1024, 1), (4, 16384, 1024, 2), (4, 4096, 1024, 5), (4, 1024, 1024, 8),
+               (4, 25600, 400, 1), (4, 6400, 400, 2), (4, 1600, 400, 5), (4, 400, 400, 8)]
+
 B0_SHAPES = [(16, 16384, 256, 1), (16, 4096, 256, 2), (16, 1024, 256, 5), (16, 256, 256, 8),       # 16 x 512^2
              (16, 7744, 121, 1), (16, 1936, 121, 2), (16, 484, 121, 5), (16, 121, 121, 8),         # 16 x 352^2
              (6, 3136, 49, 1), (6, 784, 49, 2), (6, 196, 49, 5), (6, 49, 49, 8)]                   # 6 x 224^2
 
 
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "long":          # attn_micro.py long [head_dim ...]: the streamed family, hd 32 and 64 by default
+        for hd in ([int(a) for a in sys.argv[2:]] or [32, 64]):
+            for shp in LONG_SHAPES:
+                bench_long(*shp, hd)
+        sys.exit(0)
     hd = int(sys.argv[1]) if len(sys.argv) > 1 else 64
     if hd == 32:
         tot = [0.0] * 4
