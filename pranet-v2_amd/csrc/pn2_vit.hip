@@ -2,8 +2,8 @@
 //   LayerNorm forward / backward            nn.LayerNorm at pvtv2.py:71,119,126,169,224-247 (eps 1e-5 / 1e-6)
 //   column sums                             bias gradients of nn.Linear / biased nn.Conv2d (:19,22,62-65,70,167)
 //   depth-wise 3x3 conv (+bias, +GELU)      DWConv :363-374 followed by nn.GELU in Mlp.forward :42-49
-//   spatial-reduction attention             Attention.forward :90-111 (head_dim 32 or 64; <= 256 reduced key/value tokens on chip: pn2_attn_*,
-//                                            1..4096 streamed in 128-key chunks: pn2_attn_long_*)
+//   DropPath                                per-sample scale (+ residual) of Block.forward
+// (the spatial-reduction attention of Attention.forward is pn2_attn.hip)
 // Tokens [B, N, C] of the reference are NHWC pixels here (N = H*W), so no transposes are needed anywhere.
 // The Linear layers themselves run on the implicit-GEMM conv kernels (1x1) of pn2_conv.hip.
 // All kernels are deterministic (fixed-order reductions, no floating-point atomics).
@@ -751,906 +751,6 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_row_k(const T* __restrict
     }
 }
 
-// ------------------------------------------------------------------------------------------ spatial-reduction attention
-// HD = head_dim, 32 (pvt_v2_b0) or 64 (b1..b5):
-// q   [B][Nq][heads*HD]                      (Attention.q)
-// kv  [B][Nkv][2*heads*HD]: k of head h at columns h*HD.., v at heads*HD + h*HD..   (Attention.kv reshaped (B,-1,2,heads,HD), :98-101)
-// out [B][Nq][heads*HD]  = softmax(q k^T * scale) v   with heads concatenated (:107)
-// One block = 4 waves = 4 queries in flight for one (b, head); K^T, K, V^T, V of that head live in LDS (<= 256 keys).  Lane d < HD of a wave
-// owns dimension d of q / out (at HD = 32 the upper half-wave idles in the dimension walks); lane l owns keys l, l+64, ... for the score /
-// softmax part.
-constexpr int AT_MAXK = 4;       // keys per lane -> Nkv <= 256
-
-template <typename T, int HD>
-__device__ __forceinline__ void attn_stage_kv(const T* __restrict__ kv, int ld_kv, int Nkv, int NP, int heads, int h, float* Kt, float* Vt) {
-    // Kt/Vt: [HD dims][NP + 1]: the odd row stride makes both walks conflict-free — lanes over keys (row d, consecutive l) and lanes
-    // over dims (column l, stride NP + 1); pad keys hold zeros
-    const int RS = NP + 1;
-    for (int i = threadIdx.x; i < NP * HD; i += 256) {
-        const int l = i / HD, d = i % HD;
-        float k = 0.f, v = 0.f;
-        if (l < Nkv) { k = TT<T>::ld(kv + (size_t)l * ld_kv + h * HD + d); v = TT<T>::ld(kv + (size_t)l * ld_kv + heads * HD + h * HD + d); }
-        Kt[d * RS + l] = k;
-        Vt[d * RS + l] = v;
-    }
-}
-
-__device__ __forceinline__ float rdlane(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-
-constexpr int AT_QB = 4;         // queries a wave works on at once: every K / V value read from LDS is used AT_QB times
-
-template <typename T, int NK, int HD>
-__global__ __launch_bounds__(256) void attn_fwd_k(const T* __restrict__ q, int ld_q, const T* __restrict__ kv, int ld_kv, T* __restrict__ out, int ld_o,
-                                                  float* __restrict__ lse, int Nq, int Nkv, int heads, float scale, int q_per_blk) {
-    extern __shared__ float lds[];
-    constexpr int NP = NK * 64, RS = NP + 1;
-    float* Kt = lds; float* Vt = lds + HD * RS;
-    const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int dl = lane & (HD - 1);                                      // dimension of this lane in the dimension walks (lane < HD stores)
-    attn_stage_kv<T, HD>(kv + (size_t)b * Nkv * ld_kv, ld_kv, Nkv, NP, heads, h, Kt, Vt);
-    __syncthreads();
-    const int q0 = blockIdx.x * q_per_blk;
-    int q1 = q0 + q_per_blk; if (q1 > Nq) q1 = Nq;
-    for (int qb = q0 + wid * AT_QB; qb < q1; qb += 4 * AT_QB) {
-        float qd[AT_QB], s[AT_QB][NK];
-#pragma unroll
-        for (int i = 0; i < AT_QB; ++i) {
-            const int qi = qb + i < q1 ? qb + i : q1 - 1;
-            qd[i] = TT<T>::ld(q + ((size_t)b * Nq + qi) * ld_q + h * HD + dl) * scale;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) s[i][k] = 0.f;
-        }
-#pragma unroll
-        for (int d = 0; d < HD; ++d) {
-            float kk[NK];
-#pragma unroll
-            for (int k = 0; k < NK; ++k) kk[k] = Kt[d * RS + k * 64 + lane];
-#pragma unroll
-            for (int i = 0; i < AT_QB; ++i) {
-                const float qq = rdlane(qd[i], d);
-#pragma unroll
-                for (int k = 0; k < NK; ++k) s[i][k] += qq * kk[k];
-            }
-        }
-        float inv[AT_QB], o_[AT_QB];
-#pragma unroll
-        for (int i = 0; i < AT_QB; ++i) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) if (k * 64 + lane < Nkv) mx = fmaxf(mx, s[i][k]);
-            for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) { s[i][k] = (k * 64 + lane < Nkv) ? expf(s[i][k] - mx) : 0.f; sum += s[i][k]; }
-            sum = wave_sum(sum);
-            inv[i] = 1.f / sum; o_[i] = 0.f;
-            if (lane == 0 && qb + i < q1) lse[((size_t)b * heads + h) * Nq + qb + i] = mx + logf(sum);
-        }
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-#pragma unroll
-            for (int l = 0; l < 64; ++l) {
-                const float vv = Vt[dl * RS + k * 64 + l];
-#pragma unroll
-                for (int i = 0; i < AT_QB; ++i) o_[i] += rdlane(s[i][k], l) * vv;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < AT_QB; ++i)
-            if (qb + i < q1 && lane < HD) TT<T>::st(out + ((size_t)b * Nq + qb + i) * ld_o + h * HD + lane, o_[i] * inv[i]);
-    }
-}
-
-// backward.  A block owns a chunk of queries of one (b, head).  Per group of 4 x QB queries (QB per wave): phase A recomputes
-// p = exp(s - lse), dP = dO V^T, dS = p (dP - sum p dP) and dq = scale dS K exactly like the forward walks K / V; P, dS, q, dO of the
-// group go to LDS tiles.  Phase B: every wave owns NP/4 keys and accumulates dK[l][d] += dS[q][l] q[q][d], dV[l][d] += P[q][l] dO[q][d]
-// in registers (lane = d, broadcast LDS reads).  Block partials [2][NP][HD] are summed over the query chunks by attn_bwd_kv_reduce_k.
-constexpr int AT_QCHUNK = 256;
-
-template <typename T, int NK, int QB, int HD>
-__global__ __launch_bounds__(256) void attn_bwd_k(const T* __restrict__ q, int ld_q, const T* __restrict__ kv, int ld_kv, const T* __restrict__ dout, int ld_do,
-                                                  const float* __restrict__ lse, T* __restrict__ dq, int ld_dq, float* __restrict__ part,
-                                                  int Nq, int Nkv, int heads, float scale) {
-    extern __shared__ float lds[];
-    constexpr int NP = NK * 64, RS = NP + 1, KPW = NP / 4;
-    float* Kt = lds; float* Vt = Kt + HD * RS;
-    constexpr int GQ = 4 * QB;          // queries per group
-    float* Pt = Vt + HD * RS; float* dSt = Pt + GQ * NP; float* qt = dSt + GQ * NP; float* dot = qt + GQ * HD;
-    const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int dl = lane & (HD - 1);                                      // as in attn_fwd_k: lanes >= HD compute a copy of lane - HD and store nothing
-    attn_stage_kv<T, HD>(kv + (size_t)b * Nkv * ld_kv, ld_kv, Nkv, NP, heads, h, Kt, Vt);
-    __syncthreads();
-    const int q0 = blockIdx.x * AT_QCHUNK;
-    int q1 = q0 + AT_QCHUNK; if (q1 > Nq) q1 = Nq;
-    float ak[KPW], av[KPW];
-#pragma unroll
-    for (int j = 0; j < KPW; ++j) { ak[j] = 0.f; av[j] = 0.f; }
-    for (int g0 = q0; g0 < q1; g0 += 4 * QB) {
-        const int qb = g0 + wid * QB;
-        float qd[QB], dod[QB], L[QB], s[QB][NK], dp[QB][NK];
-#pragma unroll
-        for (int i = 0; i < QB; ++i) {
-            const bool ok = qb + i < q1;
-            const int qi = ok ? qb + i : q1 - 1;
-            const size_t qo = (size_t)b * Nq + qi;
-            qd[i] = ok && lane < HD ? TT<T>::ld(q + qo * ld_q + h * HD + lane) * scale : 0.f;
-            dod[i] = ok && lane < HD ? TT<T>::ld(dout + qo * ld_do + h * HD + lane) : 0.f;
-            L[i] = lse[((size_t)b * heads + h) * Nq + qi];
-#pragma unroll
-            for (int k = 0; k < NK; ++k) { s[i][k] = 0.f; dp[i][k] = 0.f; }
-        }
-#pragma unroll
-        for (int d = 0; d < HD; ++d) {
-            float kk[NK], vv[NK];
-#pragma unroll
-            for (int k = 0; k < NK; ++k) { kk[k] = Kt[d * RS + k * 64 + lane]; vv[k] = Vt[d * RS + k * 64 + lane]; }
-#pragma unroll
-            for (int i = 0; i < QB; ++i) {
-                const float qq = rdlane(qd[i], d), gg = rdlane(dod[i], d);
-#pragma unroll
-                for (int k = 0; k < NK; ++k) { s[i][k] += qq * kk[k]; dp[i][k] += gg * vv[k]; }
-            }
-        }
-        float dqd[QB];
-#pragma unroll
-        for (int i = 0; i < QB; ++i) {
-            const bool ok = qb + i < q1;
-            float delta = 0.f;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) { s[i][k] = (ok && k * 64 + lane < Nkv) ? expf(s[i][k] - L[i]) : 0.f; delta += s[i][k] * dp[i][k]; }
-            delta = wave_sum(delta);
-            const int row = wid * QB + i;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-                dp[i][k] = s[i][k] * (dp[i][k] - delta);          // dS
-                Pt[row * NP + k * 64 + lane] = s[i][k]; dSt[row * NP + k * 64 + lane] = dp[i][k];
-            }
-            if (lane < HD) { qt[row * HD + lane] = qd[i]; dot[row * HD + lane] = dod[i]; }
-            dqd[i] = 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-#pragma unroll
-            for (int l = 0; l < 64; ++l) {
-                const float kk = Kt[dl * RS + k * 64 + l];
-#pragma unroll
-                for (int i = 0; i < QB; ++i) dqd[i] += rdlane(dp[i][k], l) * kk;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < QB; ++i)
-            if (qb + i < q1 && lane < HD) TT<T>::st(dq + ((size_t)b * Nq + qb + i) * ld_dq + h * HD + lane, dqd[i] * scale);
-        __syncthreads();
-        // phase B: this wave's keys [wid*KPW, +KPW), all queries of the group
-        for (int r = 0; r < GQ; ++r) {
-            const float qv = qt[r * HD + dl], gv = dot[r * HD + dl];
-            const float* pr = Pt + r * NP + wid * KPW; const float* dr = dSt + r * NP + wid * KPW;
-#pragma unroll
-            for (int j = 0; j < KPW; ++j) { ak[j] += dr[j] * qv; av[j] += pr[j] * gv; }
-        }
-        __syncthreads();
-    }
-    float* dst = part + ((((size_t)b * heads + h) * gridDim.x + blockIdx.x) * 2) * NP * HD;
-    if (lane < HD) {
-#pragma unroll
-        for (int j = 0; j < KPW; ++j) {
-            dst[(size_t)(wid * KPW + j) * HD + lane] = ak[j];             // qd carried the softmax scale already
-            dst[(size_t)NP * HD + (size_t)(wid * KPW + j) * HD + lane] = av[j];
-        }
-    }
-}
-
-// one block of HD threads per (key, head, b): partial [B][heads][nqb][2][NP][HD]
-template <typename T, int HD>
-__global__ __launch_bounds__(HD) void attn_bwd_kv_reduce_k(const float* __restrict__ part, T* __restrict__ dkv, int ld_dkv, int Nkv, int NP, int heads, int nqb) {
-    const int l = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
-    const float* p = part + (((size_t)b * heads + h) * nqb * 2) * NP * HD + (size_t)l * HD + d;
-    float sk = 0.f, sv = 0.f;
-    for (int c = 0; c < nqb; ++c) { sk += p[(size_t)c * 2 * NP * HD]; sv += p[(size_t)c * 2 * NP * HD + (size_t)NP * HD]; }
-    T* dst = dkv + ((size_t)b * Nkv + l) * ld_dkv;
-    TT<T>::st(dst + h * HD + d, sk);
-    TT<T>::st(dst + heads * HD + h * HD + d, sv);
-}
-
-// ------------------------------------------------------------------------------------------ bf16 MFMA attention
-// Same math as attn_fwd_k / attn_bwd_k on v_mfma_f32_16x16x32_bf16.  A block = 4 waves = 64 queries of one (b, head); every wave owns 16 queries.
-// Fragment layouts (lane l): A[l&15][(l>>4)*8 + j], B[(l>>4)*8 + j][l&15], C: column l&15, rows (l>>4)*4 + r.
-// LDS tiles keep 16-byte fragment rows with an 8-element pad so the 16 lanes of a quarter-wave hit distinct banks.
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-__device__ __forceinline__ f32x4v mfma16(const uint4& a, const uint4& b, f32x4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-// Fragment (A[i][k] or B[k][i], i = lane & 15) of a 16-wide column block of a ROW-MAJOR LDS tile [k][col] whose rows are the contraction index,
-// through the transposing LDS read: k-slot (g, j) <-> tile row (j >> 2) * 16 + g * 4 + (j & 3).  The other operand of the MFMA has to walk the
-// contraction in the same order (perm_frag).  Conflict-free when the row stride is an odd multiple of 32 bytes: ATR = 80 elements for 64-wide
-// rows (head_dim 64, and the 64-query tiles of the backward), 48 for 32-wide rows (head_dim 32).
-constexpr int ATR = 80;
-template <int HD> constexpr int at_tr() { static_assert(HD == 32 || HD == 64, "head_dim 32 or 64"); return HD == 64 ? ATR : 48; }
-template <int R = ATR>
-__device__ __forceinline__ uint4 tr_frag(const bf16_t* tile, int col0, int lane) {
-    const int g = lane >> 4, i = lane & 15;
-    unsigned a = (unsigned)(size_t)(reinterpret_cast<const char*>(tile) + (g * 4 + (i >> 2)) * (R * 2) + (col0 + (i & 3) * 4) * 2);
-    asm volatile("" : "+v"(a));            // keep the tile offset out of the instruction's immediate field
-    const s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(a));
-    const s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(a + 16 * R * 2));
-    const uint2 lo = __builtin_bit_cast(uint2, v0), hi = __builtin_bit_cast(uint2, v1);
-    return make_uint4(lo.x, lo.y, hi.x, hi.y);
-}
-// f2bf of a value that may come straight from v_exp_f32: gfx950 needs one wait state between a transcendental's result and a VALU that reads it,
-// and the compiler's hazard recognizer does not look inside inline asm (f2bf's convert), so the pad is part of the asm
-__device__ __forceinline__ bf16_t f2bf_trans(float f) {
-    unsigned r;
-    asm("s_nop 0\n\tv_cvt_pk_bf16_f32 %0, %1, %1" : "=v"(r) : "v"(f));
-    return (bf16_t)r;
-}
-// the matching fragment of an operand stored with the contraction index contiguous: row[k0 + g*4 .. +3] and row[k0 + 16 + g*4 .. +3]
-__device__ __forceinline__ uint4 perm_frag(const bf16_t* row, int k0, int g) {
-    const uint2 lo = *reinterpret_cast<const uint2*>(row + k0 + g * 4), hi = *reinterpret_cast<const uint2*>(row + k0 + 16 + g * 4);
-    return make_uint4(lo.x, lo.y, hi.x, hi.y);
-}
-
-// Forward.  A block = 8 waves = 128 queries per step; K and V rows of the (b, head) are staged once (16-byte copies, no transposes) and the block
-// walks query tiles blockIdx.x, blockIdx.x + gridDim.x, ...  (the K/V staging of the one-tile-per-block version cost more than its MFMAs).
-// HD = 32: S = Q K^T is one MFMA per 16 x 16 tile (the whole contraction is one A fragment) and O = P V has 2 column blocks instead of 4.
-template <int NK, int HD>
-__global__ __launch_bounds__(512) void attn_fwd_mfma_k(const bf16_t* __restrict__ q, int ld_q, const bf16_t* __restrict__ kv, int ld_kv, bf16_t* __restrict__ out, int ld_o,
-                                                       float* __restrict__ lse, int Nq, int Nkv, int heads, float scale) {
-    constexpr int NP = NK * 64, NT = NP / 16, KR = HD + 8, VR = at_tr<HD>(), PR = NP + 8, ND = HD / 16, CH = HD / 8;
-    extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
-    bf16_t* Ks = smem;                    // [NP][KR]   key rows                   -> B operand of S = Q K^T (lane = key, 16 bytes of d)
-    bf16_t* Vs = Ks + NP * KR;            // [NP][VR]   value rows                 -> B operand of O = P V through tr_frag (contraction = keys)
-    bf16_t* Ps = Vs + NP * VR;            // [8 waves][16][PR] probabilities       -> A operand of O = P V (perm_frag)
-    const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
-    const bf16_t* kvb = kv + (size_t)b * Nkv * ld_kv;
-    for (int i = threadIdx.x; i < NP * CH; i += 512) {
-        const int key = i / CH, ch = i % CH;
-        uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
-        if (key < Nkv) { kk = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + h * HD + ch * 8);
-                         vv = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + heads * HD + h * HD + ch * 8); }
-        *reinterpret_cast<uint4*>(Ks + key * KR + ch * 8) = kk;
-        *reinterpret_cast<uint4*>(Vs + key * VR + ch * 8) = vv;
-    }
-    __syncthreads();
-    bf16_t* pw = Ps + wid * 16 * PR;
-    const int ntile = (Nq + 127) / 128;
-    for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
-        const int q0 = tile * 128 + wid * 16;
-        const int qa = min(q0 + l15, Nq - 1);                             // A-operand row of this lane
-        const bf16_t* qp = q + ((size_t)b * Nq + qa) * ld_q + h * HD + g * 8;
-        uint4 aq[HD / 32];
-#pragma unroll
-        for (int kc = 0; kc < HD / 32; ++kc) aq[kc] = *reinterpret_cast<const uint4*>(qp + kc * 32);
-        f32x4v s[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const bf16_t* kp = Ks + (nt * 16 + l15) * KR + g * 8;
-            f32x4v c = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kc = 0; kc < HD / 32; ++kc) c = mfma16(aq[kc], *reinterpret_cast<const uint4*>(kp + kc * 32), c);
-            s[nt] = c;
-        }
-        float mx[4], sum[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float m = -INFINITY;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) { const float v = (nt * 16 + l15 < Nkv) ? s[nt][r] * scale : -INFINITY; s[nt][r] = v; m = fmaxf(m, v); }
-            m = fmaxf(m, __shfl_xor(m, 1)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 4)); m = fmaxf(m, __shfl_xor(m, 8));
-            float t = 0.f;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) { const float p = __expf(s[nt][r] - m); s[nt][r] = p; t += p; }
-            t += __shfl_xor(t, 1); t += __shfl_xor(t, 2); t += __shfl_xor(t, 4); t += __shfl_xor(t, 8);
-            mx[r] = m; sum[r] = t;
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pw[(g * 4 + r) * PR + nt * 16 + l15] = f2bf_trans(s[nt][r]);
-        __syncthreads();                                                  // (every wave walks the same number of tiles)
-        f32x4v o[ND];
-#pragma unroll
-        for (int nd = 0; nd < ND; ++nd) o[nd] = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < NP / 32; ++ks) {
-            const uint4 ap = perm_frag(pw + l15 * PR, ks * 32, g);
-#pragma unroll
-            for (int nd = 0; nd < ND; ++nd) o[nd] = mfma16(ap, tr_frag<VR>(Vs + ks * 32 * VR, nd * 16, lane), o[nd]);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int qi = q0 + g * 4 + r;
-            if (qi < Nq) {
-                const float inv = 1.f / sum[r];
-                bf16_t* op = out + ((size_t)b * Nq + qi) * ld_o + h * HD + l15;
-#pragma unroll
-                for (int nd = 0; nd < ND; ++nd) op[nd * 16] = f2bf(o[nd][r] * inv);
-                if (l15 == 0) lse[((size_t)b * heads + h) * Nq + qi] = mx[r] + __logf(sum[r]);
-            }
-        }
-        __syncthreads();                                                  // the next tile's probabilities overwrite Ps
-    }
-}
-
-// delta[b][h][q] = sum_d dO[q][h*HD + d] * O[q][h*HD + d]   (= sum_keys P dP: lets the backward treat key ranges independently)
-template <typename T, int HD>
-__global__ __launch_bounds__(256) void attn_delta_k(const T* __restrict__ dout, int ld_do, const T* __restrict__ o, int ld_o, float* __restrict__ delta, int B, int Nq, int heads) {
-    const int lane = threadIdx.x & 63;
-    const size_t item = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), total = (size_t)B * Nq * heads;
-    if (item >= total) return;
-    const int h = (int)(item % heads); const size_t bq = item / heads;          // bq = b * Nq + q
-    float v = lane < HD ? TT<T>::ld(dout + bq * ld_do + h * HD + lane) * TT<T>::ld(o + bq * ld_o + h * HD + lane) : 0.f;
-    v = wave_sum(v);
-    if (lane == 0) { const size_t b = bq / Nq, qi = bq % Nq; delta[(b * heads + h) * Nq + qi] = v; }
-}
-
-// backward for the keys [key0, key0 + NKB*64) of one (b, head); the block walks 64-query tiles blockIdx.x, blockIdx.x + gridDim.x, ...:
-//   S = Q K^T, dP = dO V^T (MFMA) -> P = exp(S scale - lse), dS = P (dP - delta) scale
-//   dQ (+)= dS K ; dK += dS^T Q, dV += P^T dO accumulate in registers over the tiles of the block and leave as ONE fp32 partial [2][NPT][HD]
-//   per block (summed by attn_bwd_kv_reduce_k).  K, V, Q and dO tiles are staged row-major with 16-byte copies; every product whose contraction
-//   runs over tile rows (keys for dQ, queries for dK / dV) reads its B operand with the transposing LDS read (tr_frag), so nothing is transposed.
-//   HD = 32: S and dP are one MFMA per tile, dQ / dK / dV have 2 column blocks instead of 4.
-template <int NKB, int HD>
-__global__ __launch_bounds__(256) void attn_bwd_mfma_k(const bf16_t* __restrict__ q, int ld_q, const bf16_t* __restrict__ kv, int ld_kv, const bf16_t* __restrict__ dout, int ld_do,
-                                                       const float* __restrict__ lse, const float* __restrict__ delta, bf16_t* __restrict__ dq, int ld_dq, float* __restrict__ part,
-                                                       int Nq, int Nkv, int heads, float scale, int key0, int NPT, int dq_acc) {
-    constexpr int NP = NKB * 64, NT = NP / 16, KR = 72, TR = NP + 8, NKT = NT / 4, DR = at_tr<HD>(), VR = HD + 8, ND = HD / 16, CH = HD / 8, CHS = HD == 64 ? 3 : 2, KC = HD / 32;
-    extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
-    bf16_t* Ks = smem;                    // [NP][DR]  K rows: B of S = Q K^T (16-byte reads) and of dQ = dS K (tr_frag, contraction = keys)
-    bf16_t* Vs = Ks + NP * DR;            // [NP][VR]  V rows: B of dP = dO V^T
-    bf16_t* Qs = Vs + NP * VR;            // [64][DR]  Q tile  [q][d]: A of S, B of dK (tr_frag, contraction = queries)
-    bf16_t* Gs = Qs + 64 * DR;            // [64][DR]  dO tile [q][d]: A of dP, B of dV
-    bf16_t* Sa = Gs + 64 * DR;            // [4][16][TR] dS, A layout per wave (perm_frag over keys)
-    bf16_t* St = Sa + 64 * TR;            // [NP][KR]  dS transposed [key][q]  (perm_frag over queries)
-    bf16_t* Pt = St + NP * KR;            // [NP][KR]  P transposed  [key][q]
-    const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
-    const bf16_t* kvb = kv + (size_t)b * Nkv * ld_kv;
-    for (int i = threadIdx.x; i < NP * CH; i += 256) {
-        const int kl = i >> CHS, ch = i & (CH - 1), key = key0 + kl;
-        uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
-        if (key < Nkv) { kk = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + h * HD + ch * 8);
-                         vv = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + heads * HD + h * HD + ch * 8); }
-        *reinterpret_cast<uint4*>(Ks + kl * DR + ch * 8) = kk;
-        *reinterpret_cast<uint4*>(Vs + kl * VR + ch * 8) = vv;
-    }
-    f32x4v ak[NKT][ND], av[NKT][ND];
-#pragma unroll
-    for (int i = 0; i < NKT; ++i)
-#pragma unroll
-        for (int nd = 0; nd < ND; ++nd) { ak[i][nd] = f32x4v{0.f, 0.f, 0.f, 0.f}; av[i][nd] = ak[i][nd]; }
-    bf16_t* sa = Sa + wid * 16 * TR;
-    const int ntile = (Nq + 63) / 64;
-    for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
-        const int qt0 = tile * 64;
-        __syncthreads();                                                  // the previous tile's readers of Qs / Gs / St / Pt are done (and K / V are in)
-        for (int i = threadIdx.x; i < 64 * CH; i += 256) {
-            const int ql = i >> CHS, ch = i & (CH - 1), qi = qt0 + ql;
-            uint4 qq = make_uint4(0, 0, 0, 0), gg = qq;
-            if (qi < Nq) { qq = *reinterpret_cast<const uint4*>(q + ((size_t)b * Nq + qi) * ld_q + h * HD + ch * 8);
-                           gg = *reinterpret_cast<const uint4*>(dout + ((size_t)b * Nq + qi) * ld_do + h * HD + ch * 8); }
-            *reinterpret_cast<uint4*>(Qs + ql * DR + ch * 8) = qq;
-            *reinterpret_cast<uint4*>(Gs + ql * DR + ch * 8) = gg;
-        }
-        const int q0 = qt0 + wid * 16;
-        float L[4], D[4]; bool rok[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int qi = q0 + g * 4 + r;
-            rok[r] = qi < Nq;
-            const size_t li = ((size_t)b * heads + h) * Nq + (rok[r] ? qi : Nq - 1);
-            L[r] = lse[li]; D[r] = delta[li];
-        }
-        __syncthreads();
-        const bf16_t* qrow = Qs + (wid * 16 + l15) * DR + g * 8; const bf16_t* grow = Gs + (wid * 16 + l15) * DR + g * 8;
-        uint4 aq[KC], ag[KC];
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) aq[kc] = *reinterpret_cast<const uint4*>(qrow + kc * 32);
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) ag[kc] = *reinterpret_cast<const uint4*>(grow + kc * 32);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const bf16_t* kp = Ks + (nt * 16 + l15) * DR + g * 8; const bf16_t* vp = Vs + (nt * 16 + l15) * VR + g * 8;
-            f32x4v s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc) s = mfma16(aq[kc], *reinterpret_cast<const uint4*>(kp + kc * 32), s);
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc) dp = mfma16(ag[kc], *reinterpret_cast<const uint4*>(vp + kc * 32), dp);
-            const bool kok = key0 + nt * 16 + l15 < Nkv;
-            bf16_t pb[4], sb[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = (kok && rok[r]) ? __expf(s[r] * scale - L[r]) : 0.f;
-                const float ds = p * (dp[r] - D[r]) * scale;
-                pb[r] = f2bf_trans(p); sb[r] = f2bf(ds);
-                sa[(g * 4 + r) * TR + nt * 16 + l15] = sb[r];
-            }
-            // transposed tiles [key][query]: 4 consecutive queries of this lane -> one 8-byte store each
-            const int key = nt * 16 + l15, qc = wid * 16 + g * 4;
-            *reinterpret_cast<uint2*>(St + key * KR + qc) = make_uint2((unsigned)sb[0] | ((unsigned)sb[1] << 16), (unsigned)sb[2] | ((unsigned)sb[3] << 16));
-            *reinterpret_cast<uint2*>(Pt + key * KR + qc) = make_uint2((unsigned)pb[0] | ((unsigned)pb[1] << 16), (unsigned)pb[2] | ((unsigned)pb[3] << 16));
-        }
-        __syncthreads();
-        // dQ = dS K  (this wave's 16 queries x HD dims, contraction over the keys of this range)
-        f32x4v dqa[ND];
-#pragma unroll
-        for (int nd = 0; nd < ND; ++nd) dqa[nd] = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < NP / 32; ++ks) {
-            const uint4 a = perm_frag(sa + l15 * TR, ks * 32, g);
-#pragma unroll
-            for (int nd = 0; nd < ND; ++nd) dqa[nd] = mfma16(a, tr_frag<DR>(Ks + ks * 32 * DR, nd * 16, lane), dqa[nd]);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (rok[r]) {
-                bf16_t* dp_ = dq + ((size_t)b * Nq + q0 + g * 4 + r) * ld_dq + h * HD + l15;
-#pragma unroll
-                for (int nd = 0; nd < ND; ++nd) dp_[nd * 16] = f2bf(dq_acc ? bf2f(dp_[nd * 16]) + dqa[nd][r] : dqa[nd][r]);
-            }
-        }
-        // dK += dS^T Q, dV += P^T dO : this wave's key tiles (kt = wid, wid + 4, ...), contraction over the 64 queries of the tile
-#pragma unroll
-        for (int i = 0; i < NKT; ++i) {
-            const int kt = wid + 4 * i;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const uint4 as = perm_frag(St + (kt * 16 + l15) * KR, ks * 32, g);
-                const uint4 ap = perm_frag(Pt + (kt * 16 + l15) * KR, ks * 32, g);
-#pragma unroll
-                for (int nd = 0; nd < ND; ++nd) {
-                    ak[i][nd] = mfma16(as, tr_frag<DR>(Qs + ks * 32 * DR, nd * 16, lane), ak[i][nd]);
-                    av[i][nd] = mfma16(ap, tr_frag<DR>(Gs + ks * 32 * DR, nd * 16, lane), av[i][nd]);
-                }
-            }
-        }
-    }
-    float* dst = part + ((((size_t)b * heads + h) * gridDim.x + blockIdx.x) * 2) * (size_t)NPT * HD;
-#pragma unroll
-    for (int i = 0; i < NKT; ++i) {
-        const int kt = wid + 4 * i;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const size_t row = (size_t)(key0 + kt * 16 + g * 4 + r) * HD + l15;
-#pragma unroll
-            for (int nd = 0; nd < ND; ++nd) { dst[row + nd * 16] = ak[i][nd][r]; dst[(size_t)NPT * HD + row + nd * 16] = av[i][nd][r]; }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------ attention over 1..4096 keys (pn2_attn_long_*)
-// The keys are streamed through LDS in chunks of AL_CK; nothing on chip grows with Nkv.  Forward: online softmax.  Per chunk, with m / l / O the
-// running maximum, sum and un-normalised output of a query row:  m' = max(m, max_j s_j), a = exp(m - m') (0 for the first chunk: m = -inf, m' finite
-// because only chunks with a valid key are visited), l = l a + sum_j exp(s_j - m'), O = O a + exp(s - m') V.  out = O / l, lse = m + log l at the end.
-constexpr int AL_CK = 128;
-
-// bf16 MFMA forward: a block = 8 waves = 128 queries of one (b, head), every wave 16 of them.  K / V chunk rows use the pitches of attn_fwd_mfma_k.
-template <int HD>
-__global__ __launch_bounds__(512) void attn_long_fwd_mfma_k(const bf16_t* __restrict__ q, int ld_q, const bf16_t* __restrict__ kv, int ld_kv, bf16_t* __restrict__ out, int ld_o,
-                                                            float* __restrict__ lse, int Nq, int Nkv, int heads, float scale) {
-    constexpr int NP = AL_CK, NT = NP / 16, KR = HD + 8, VR = at_tr<HD>(), PR = NP + 8, ND = HD / 16, CH = HD / 8;
-    extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
-    bf16_t* Ks = smem;                    // [NP][KR]   key rows of the chunk
-    bf16_t* Vs = Ks + NP * KR;            // [NP][VR]   value rows of the chunk (tr_frag)
-    bf16_t* Ps = Vs + NP * VR;            // [8 waves][16][PR] probabilities of the chunk
-    const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
-    const bf16_t* kvb = kv + (size_t)b * Nkv * ld_kv;
-    bf16_t* pw = Ps + wid * 16 * PR;
-    const int q0 = blockIdx.x * 128 + wid * 16;
-    const int qa = min(q0 + l15, Nq - 1);                                 // A-operand row of this lane
-    const bf16_t* qp = q + ((size_t)b * Nq + qa) * ld_q + h * HD + g * 8;
-    uint4 aq[HD / 32];
-#pragma unroll
-    for (int kc = 0; kc < HD / 32; ++kc) aq[kc] = *reinterpret_cast<const uint4*>(qp + kc * 32);
-    float mrun[4], lrun[4];
-    f32x4v o[ND];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { mrun[r] = -INFINITY; lrun[r] = 0.f; }
-#pragma unroll
-    for (int nd = 0; nd < ND; ++nd) o[nd] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    for (int key0 = 0; key0 < Nkv; key0 += NP) {                          // every visited chunk holds key0 < Nkv: at least one valid key
-        if (key0) __syncthreads();                                        // the previous chunk's readers of Ks / Vs are done
-        for (int i = threadIdx.x; i < NP * CH; i += 512) {
-            const int kl = i / CH, ch = i % CH, key = key0 + kl;
-            uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
-            if (key < Nkv) { kk = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + h * HD + ch * 8);
-                             vv = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + heads * HD + h * HD + ch * 8); }
-            *reinterpret_cast<uint4*>(Ks + kl * KR + ch * 8) = kk;
-            *reinterpret_cast<uint4*>(Vs + kl * VR + ch * 8) = vv;
-        }
-        __syncthreads();
-        f32x4v s[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const bf16_t* kp = Ks + (nt * 16 + l15) * KR + g * 8;
-            f32x4v c = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kc = 0; kc < HD / 32; ++kc) c = mfma16(aq[kc], *reinterpret_cast<const uint4*>(kp + kc * 32), c);
-            s[nt] = c;
-        }
-        float al[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float m = -INFINITY;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) { const float v = (key0 + nt * 16 + l15 < Nkv) ? s[nt][r] * scale : -INFINITY; s[nt][r] = v; m = fmaxf(m, v); }
-            m = fmaxf(m, __shfl_xor(m, 1)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 4)); m = fmaxf(m, __shfl_xor(m, 8));
-            m = fmaxf(m, mrun[r]);                                        // finite
-            al[r] = mrun[r] == -INFINITY ? 0.f : __expf(mrun[r] - m);
-            float t = 0.f;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) { const float p = __expf(s[nt][r] - m); s[nt][r] = p; t += p; }
-            t += __shfl_xor(t, 1); t += __shfl_xor(t, 2); t += __shfl_xor(t, 4); t += __shfl_xor(t, 8);
-            mrun[r] = m; lrun[r] = lrun[r] * al[r] + t;
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pw[(g * 4 + r) * PR + nt * 16 + l15] = f2bf_trans(s[nt][r]);
-        __syncthreads();
-#pragma unroll
-        for (int nd = 0; nd < ND; ++nd)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[nd][r] *= al[r];
-#pragma unroll
-        for (int ks = 0; ks < NP / 32; ++ks) {
-            const uint4 ap = perm_frag(pw + l15 * PR, ks * 32, g);
-#pragma unroll
-            for (int nd = 0; nd < ND; ++nd) o[nd] = mfma16(ap, tr_frag<VR>(Vs + ks * 32 * VR, nd * 16, lane), o[nd]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int qi = q0 + g * 4 + r;
-        if (qi < Nq) {
-            const float inv = 1.f / lrun[r];
-            bf16_t* op = out + ((size_t)b * Nq + qi) * ld_o + h * HD + l15;
-#pragma unroll
-            for (int nd = 0; nd < ND; ++nd) op[nd * 16] = f2bf(o[nd][r] * inv);
-            if (l15 == 0) lse[((size_t)b * heads + h) * Nq + qi] = mrun[r] + __logf(lrun[r]);
-        }
-    }
-}
-
-// scalar forward (fp32 storage, bf16 views with an ld that is no multiple of 8): the walks of attn_fwd_k over one chunk at a time.  A block = 4 waves
-// = AL_QPB queries, a wave 16 of them in 4 groups of AT_QB; the running m / l / O of the block's queries live in LDS between chunks (wave-private rows).
-constexpr int AL_QPB = 64;
-
-template <typename T, int HD>
-__global__ __launch_bounds__(256) void attn_long_fwd_k(const T* __restrict__ q, int ld_q, const T* __restrict__ kv, int ld_kv, T* __restrict__ out, int ld_o,
-                                                       float* __restrict__ lse, int Nq, int Nkv, int heads, float scale) {
-    extern __shared__ float lds[];
-    constexpr int NK = AL_CK / 64, NP = AL_CK, RS = NP + 1;
-    float* Kt = lds; float* Vt = Kt + HD * RS;
-    float* Os = Vt + HD * RS;             // [AL_QPB][HD] un-normalised outputs
-    float* Ms = Os + AL_QPB * HD;         // [AL_QPB] running maxima
-    float* Ls = Ms + AL_QPB;              // [AL_QPB] running sums
-    const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int dl = lane & (HD - 1);
-    const int q0 = blockIdx.x * AL_QPB;
-    int q1 = q0 + AL_QPB; if (q1 > Nq) q1 = Nq;
-    for (int i = threadIdx.x; i < AL_QPB * HD; i += 256) Os[i] = 0.f;
-    if (threadIdx.x < AL_QPB) { Ms[threadIdx.x] = -INFINITY; Ls[threadIdx.x] = 0.f; }
-    for (int key0 = 0; key0 < Nkv; key0 += NP) {
-        __syncthreads();                                                  // the previous chunk's walks are done, its m / l / O stores visible
-        attn_stage_kv<T, HD>(kv + ((size_t)b * Nkv + key0) * ld_kv, ld_kv, Nkv - key0, NP, heads, h, Kt, Vt);
-        __syncthreads();
-#pragma unroll 1
-        for (int grp = 0; grp < 16 / AT_QB; ++grp) {
-            const int ql = wid * 16 + grp * AT_QB, qb = q0 + ql;
-            if (qb >= q1) break;
-            float qd[AT_QB], s[AT_QB][NK];
-#pragma unroll
-            for (int i = 0; i < AT_QB; ++i) {
-                const int qi = qb + i < q1 ? qb + i : q1 - 1;
-                qd[i] = TT<T>::ld(q + ((size_t)b * Nq + qi) * ld_q + h * HD + dl) * scale;
-#pragma unroll
-                for (int k = 0; k < NK; ++k) s[i][k] = 0.f;
-            }
-#pragma unroll
-            for (int d = 0; d < HD; ++d) {
-                float kk[NK];
-#pragma unroll
-                for (int k = 0; k < NK; ++k) kk[k] = Kt[d * RS + k * 64 + lane];
-#pragma unroll
-                for (int i = 0; i < AT_QB; ++i) {
-                    const float qq = rdlane(qd[i], d);
-#pragma unroll
-                    for (int k = 0; k < NK; ++k) s[i][k] += qq * kk[k];
-                }
-            }
-            float o_[AT_QB], mn[AT_QB], ln[AT_QB];
-#pragma unroll
-            for (int i = 0; i < AT_QB; ++i) {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int k = 0; k < NK; ++k) if (key0 + k * 64 + lane < Nkv) mx = fmaxf(mx, s[i][k]);
-                for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-                const float mo = Ms[ql + i];
-                mx = fmaxf(mx, mo);                                       // finite: the chunk has a valid key
-                const float al = mo == -INFINITY ? 0.f : expf(mo - mx);
-                float sum = 0.f;
-#pragma unroll
-                for (int k = 0; k < NK; ++k) { s[i][k] = (key0 + k * 64 + lane < Nkv) ? expf(s[i][k] - mx) : 0.f; sum += s[i][k]; }
-                sum = wave_sum(sum);
-                mn[i] = mx; ln[i] = Ls[ql + i] * al + sum;
-                o_[i] = Os[(ql + i) * HD + dl] * al;
-            }
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-#pragma unroll
-                for (int l = 0; l < 64; ++l) {
-                    const float vv = Vt[dl * RS + k * 64 + l];
-#pragma unroll
-                    for (int i = 0; i < AT_QB; ++i) o_[i] += rdlane(s[i][k], l) * vv;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < AT_QB; ++i) {
-                if (lane < HD) Os[(ql + i) * HD + lane] = o_[i];
-                if (lane == 0) { Ms[ql + i] = mn[i]; Ls[ql + i] = ln[i]; }
-            }
-        }
-    }
-    __syncthreads();
-    for (int ql = wid * 16; ql < wid * 16 + 16 && q0 + ql < q1; ++ql) {
-        const float l = Ls[ql];
-        if (lane < HD) TT<T>::st(out + ((size_t)b * Nq + q0 + ql) * ld_o + h * HD + lane, Os[ql * HD + lane] / l);
-        if (lane == 0) lse[((size_t)b * heads + h) * Nq + q0 + ql] = Ms[ql] + logf(l);
-    }
-}
-
-// Backward, both routes: one launch per range of AL_CK keys from lse and delta, as attn_bwd_mfma_k.  dQ accumulates over the ranges in an fp32
-// workspace dqw [B][Nq][heads*HD] (written by the first range, added to by the later ones: every element belongs to one block per launch) and is
-// converted once by attn_long_dq_store_k.  The dK / dV partial holds ONE range, [B][heads][slots][2][AL_CK][HD], rows local to the range, and is summed
-// in slot order by attn_long_kv_reduce_k after each launch.
-//
-// attn_long_bwd_mfma_k<HD> is a copy of attn_bwd_mfma_k<2, HD> (whose instantiations must not change); keep the two in step.  The differences, all of them:
-//   1. NP is the constant AL_CK (= the NKB = 2 case); the NPT argument is gone;
-//   2. dQ: `float* dqw`, row pitch heads * HD, fp32 `old + dqa` when dq_acc, instead of the bf16 `dq` with ld_dq and a re-rounded bf16 read-modify-write;
-//   3. the partial: slot stride 2 * AL_CK * HD and rows LOCAL to the range (kt * 16 + ...), instead of 2 * NPT * HD and rows key0 + kt * 16 + ...
-// Staging, S / dP, P / dS and their transposes, the dQ / dK / dV products and every LDS pitch are line for line the same.
-template <int HD>
-__global__ __launch_bounds__(256) void attn_long_bwd_mfma_k(const bf16_t* __restrict__ q, int ld_q, const bf16_t* __restrict__ kv, int ld_kv, const bf16_t* __restrict__ dout, int ld_do,
-                                                            const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dqw, float* __restrict__ part,
-                                                            int Nq, int Nkv, int heads, float scale, int key0, int dq_acc) {
-    constexpr int NP = AL_CK, NT = NP / 16, KR = 72, TR = NP + 8, NKT = NT / 4, DR = at_tr<HD>(), VR = HD + 8, ND = HD / 16, CH = HD / 8, CHS = HD == 64 ? 3 : 2, KC = HD / 32;
-    extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
-    bf16_t* Ks = smem;                    // [NP][DR]  K rows: B of S = Q K^T and of dQ = dS K (tr_frag)
-    bf16_t* Vs = Ks + NP * DR;            // [NP][VR]  V rows: B of dP = dO V^T
-    bf16_t* Qs = Vs + NP * VR;            // [64][DR]  Q tile: A of S, B of dK (tr_frag)
-    bf16_t* Gs = Qs + 64 * DR;            // [64][DR]  dO tile: A of dP, B of dV
-    bf16_t* Sa = Gs + 64 * DR;            // [4][16][TR] dS, A layout per wave
-    bf16_t* St = Sa + 64 * TR;            // [NP][KR]  dS transposed [key][q]
-    bf16_t* Pt = St + NP * KR;            // [NP][KR]  P transposed  [key][q]
-    const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
-    const bf16_t* kvb = kv + (size_t)b * Nkv * ld_kv;
-    for (int i = threadIdx.x; i < NP * CH; i += 256) {
-        const int kl = i >> CHS, ch = i & (CH - 1), key = key0 + kl;
-        uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
-        if (key < Nkv) { kk = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + h * HD + ch * 8);
-                         vv = *reinterpret_cast<const uint4*>(kvb + (size_t)key * ld_kv + heads * HD + h * HD + ch * 8); }
-        *reinterpret_cast<uint4*>(Ks + kl * DR + ch * 8) = kk;
-        *reinterpret_cast<uint4*>(Vs + kl * VR + ch * 8) = vv;
-    }
-    f32x4v ak[NKT][ND], av[NKT][ND];
-#pragma unroll
-    for (int i = 0; i < NKT; ++i)
-#pragma unroll
-        for (int nd = 0; nd < ND; ++nd) { ak[i][nd] = f32x4v{0.f, 0.f, 0.f, 0.f}; av[i][nd] = ak[i][nd]; }
-    bf16_t* sa = Sa + wid * 16 * TR;
-    const int ntile = (Nq + 63) / 64;
-    for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
-        const int qt0 = tile * 64;
-        __syncthreads();                                                  // the previous tile's readers of Qs / Gs / St / Pt are done (and K / V are in)
-        for (int i = threadIdx.x; i < 64 * CH; i += 256) {
-            const int ql = i >> CHS, ch = i & (CH - 1), qi = qt0 + ql;
-            uint4 qq = make_uint4(0, 0, 0, 0), gg = qq;
-            if (qi < Nq) { qq = *reinterpret_cast<const uint4*>(q + ((size_t)b * Nq + qi) * ld_q + h * HD + ch * 8);
-                           gg = *reinterpret_cast<const uint4*>(dout + ((size_t)b * Nq + qi) * ld_do + h * HD + ch * 8); }
-            *reinterpret_cast<uint4*>(Qs + ql * DR + ch * 8) = qq;
-            *reinterpret_cast<uint4*>(Gs + ql * DR + ch * 8) = gg;
-        }
-        const int q0 = qt0 + wid * 16;
-        float L[4], D[4]; bool rok[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int qi = q0 + g * 4 + r;
-            rok[r] = qi < Nq;
-            const size_t li = ((size_t)b * heads + h) * Nq + (rok[r] ? qi : Nq - 1);
-            L[r] = lse[li]; D[r] = delta[li];
-        }
-        __syncthreads();
-        const bf16_t* qrow = Qs + (wid * 16 + l15) * DR + g * 8; const bf16_t* grow = Gs + (wid * 16 + l15) * DR + g * 8;
-        uint4 aq[KC], ag[KC];
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) aq[kc] = *reinterpret_cast<const uint4*>(qrow + kc * 32);
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) ag[kc] = *reinterpret_cast<const uint4*>(grow + kc * 32);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const bf16_t* kp = Ks + (nt * 16 + l15) * DR + g * 8; const bf16_t* vp = Vs + (nt * 16 + l15) * VR + g * 8;
-            f32x4v s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc) s = mfma16(aq[kc], *reinterpret_cast<const uint4*>(kp + kc * 32), s);
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc) dp = mfma16(ag[kc], *reinterpret_cast<const uint4*>(vp + kc * 32), dp);
-            const bool kok = key0 + nt * 16 + l15 < Nkv;
-            bf16_t pb[4], sb[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = (kok && rok[r]) ? __expf(s[r] * scale - L[r]) : 0.f;
-                const float ds = p * (dp[r] - D[r]) * scale;
-                pb[r] = f2bf_trans(p); sb[r] = f2bf(ds);
-                sa[(g * 4 + r) * TR + nt * 16 + l15] = sb[r];
-            }
-            const int key = nt * 16 + l15, qc = wid * 16 + g * 4;
-            *reinterpret_cast<uint2*>(St + key * KR + qc) = make_uint2((unsigned)sb[0] | ((unsigned)sb[1] << 16), (unsigned)sb[2] | ((unsigned)sb[3] << 16));
-            *reinterpret_cast<uint2*>(Pt + key * KR + qc) = make_uint2((unsigned)pb[0] | ((unsigned)pb[1] << 16), (unsigned)pb[2] | ((unsigned)pb[3] << 16));
-        }
-        __syncthreads();
-        // dQ (+)= dS K in fp32
-        f32x4v dqa[ND];
-#pragma unroll
-        for (int nd = 0; nd < ND; ++nd) dqa[nd] = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < NP / 32; ++ks) {
-            const uint4 a = perm_frag(sa + l15 * TR, ks * 32, g);
-#pragma unroll
-            for (int nd = 0; nd < ND; ++nd) dqa[nd] = mfma16(a, tr_frag<DR>(Ks + ks * 32 * DR, nd * 16, lane), dqa[nd]);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (rok[r]) {
-                float* dp_ = dqw + ((size_t)b * Nq + q0 + g * 4 + r) * (heads * HD) + h * HD + l15;
-#pragma unroll
-                for (int nd = 0; nd < ND; ++nd) dp_[nd * 16] = dq_acc ? dp_[nd * 16] + dqa[nd][r] : dqa[nd][r];
-            }
-        }
-        // dK += dS^T Q, dV += P^T dO
-#pragma unroll
-        for (int i = 0; i < NKT; ++i) {
-            const int kt = wid + 4 * i;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const uint4 as = perm_frag(St + (kt * 16 + l15) * KR, ks * 32, g);
-                const uint4 ap = perm_frag(Pt + (kt * 16 + l15) * KR, ks * 32, g);
-#pragma unroll
-                for (int nd = 0; nd < ND; ++nd) {
-                    ak[i][nd] = mfma16(as, tr_frag<DR>(Qs + ks * 32 * DR, nd * 16, lane), ak[i][nd]);
-                    av[i][nd] = mfma16(ap, tr_frag<DR>(Gs + ks * 32 * DR, nd * 16, lane), av[i][nd]);
-                }
-            }
-        }
-    }
-    float* dst = part + ((((size_t)b * heads + h) * gridDim.x + blockIdx.x) * 2) * (size_t)NP * HD;
-#pragma unroll
-    for (int i = 0; i < NKT; ++i) {
-        const int kt = wid + 4 * i;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const size_t row = (size_t)(kt * 16 + g * 4 + r) * HD + l15;
-#pragma unroll
-            for (int nd = 0; nd < ND; ++nd) { dst[row + nd * 16] = ak[i][nd][r]; dst[(size_t)NP * HD + row + nd * 16] = av[i][nd][r]; }
-        }
-    }
-}
-
-// scalar route: the phases of attn_bwd_k on one key range; delta = rowsum(dO * out) comes from attn_delta_k instead of the full-row sum p dP.
-// The block walks the 256-query chunks blockIdx.x, blockIdx.x + gridDim.x, ... and leaves one partial.
-template <typename T, int HD>
-__global__ __launch_bounds__(256) void attn_long_bwd_k(const T* __restrict__ q, int ld_q, const T* __restrict__ kv, int ld_kv, const T* __restrict__ dout, int ld_do,
-                                                       const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dqw, float* __restrict__ part,
-                                                       int Nq, int Nkv, int heads, float scale, int key0, int dq_acc) {
-    extern __shared__ float lds[];
-    constexpr int NK = AL_CK / 64, NP = AL_CK, RS = NP + 1, KPW = NP / 4, QB = AT_QB, GQ = 4 * QB;
-    float* Kt = lds; float* Vt = Kt + HD * RS;
-    float* Pt = Vt + HD * RS; float* dSt = Pt + GQ * NP; float* qt = dSt + GQ * NP; float* dot = qt + GQ * HD;
-    const int b = blockIdx.z, h = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int dl = lane & (HD - 1);
-    attn_stage_kv<T, HD>(kv + ((size_t)b * Nkv + key0) * ld_kv, ld_kv, Nkv - key0, NP, heads, h, Kt, Vt);
-    __syncthreads();
-    float ak[KPW], av[KPW];
-#pragma unroll
-    for (int j = 0; j < KPW; ++j) { ak[j] = 0.f; av[j] = 0.f; }
-    const int nqc = (Nq + AT_QCHUNK - 1) / AT_QCHUNK;
-    for (int qc = blockIdx.x; qc < nqc; qc += gridDim.x) {
-        const int q0 = qc * AT_QCHUNK;
-        int q1 = q0 + AT_QCHUNK; if (q1 > Nq) q1 = Nq;
-        for (int g0 = q0; g0 < q1; g0 += GQ) {
-            const int qb = g0 + wid * QB;
-            float qd[QB], dod[QB], L[QB], D[QB], s[QB][NK], dp[QB][NK];
-#pragma unroll
-            for (int i = 0; i < QB; ++i) {
-                const bool ok = qb + i < q1;
-                const int qi = ok ? qb + i : q1 - 1;
-                const size_t qo = (size_t)b * Nq + qi;
-                qd[i] = ok && lane < HD ? TT<T>::ld(q + qo * ld_q + h * HD + lane) * scale : 0.f;
-                dod[i] = ok && lane < HD ? TT<T>::ld(dout + qo * ld_do + h * HD + lane) : 0.f;
-                L[i] = lse[((size_t)b * heads + h) * Nq + qi]; D[i] = delta[((size_t)b * heads + h) * Nq + qi];
-#pragma unroll
-                for (int k = 0; k < NK; ++k) { s[i][k] = 0.f; dp[i][k] = 0.f; }
-            }
-#pragma unroll
-            for (int d = 0; d < HD; ++d) {
-                float kk[NK], vv[NK];
-#pragma unroll
-                for (int k = 0; k < NK; ++k) { kk[k] = Kt[d * RS + k * 64 + lane]; vv[k] = Vt[d * RS + k * 64 + lane]; }
-#pragma unroll
-                for (int i = 0; i < QB; ++i) {
-                    const float qq = rdlane(qd[i], d), gg = rdlane(dod[i], d);
-#pragma unroll
-                    for (int k = 0; k < NK; ++k) { s[i][k] += qq * kk[k]; dp[i][k] += gg * vv[k]; }
-                }
-            }
-            float dqd[QB];
-#pragma unroll
-            for (int i = 0; i < QB; ++i) {
-                const bool ok = qb + i < q1;
-                const int row = wid * QB + i;
-#pragma unroll
-                for (int k = 0; k < NK; ++k) {
-                    s[i][k] = (ok && key0 + k * 64 + lane < Nkv) ? expf(s[i][k] - L[i]) : 0.f;
-                    dp[i][k] = s[i][k] * (dp[i][k] - D[i]);           // dS
-                    Pt[row * NP + k * 64 + lane] = s[i][k]; dSt[row * NP + k * 64 + lane] = dp[i][k];
-                }
-                if (lane < HD) { qt[row * HD + lane] = qd[i]; dot[row * HD + lane] = dod[i]; }
-                dqd[i] = 0.f;
-            }
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-#pragma unroll
-                for (int l = 0; l < 64; ++l) {
-                    const float kk = Kt[dl * RS + k * 64 + l];
-#pragma unroll
-                    for (int i = 0; i < QB; ++i) dqd[i] += rdlane(dp[i][k], l) * kk;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < QB; ++i)
-                if (qb + i < q1 && lane < HD) {
-                    float* dp_ = dqw + ((size_t)b * Nq + qb + i) * (heads * HD) + h * HD + lane;
-                    *dp_ = dq_acc ? *dp_ + dqd[i] * scale : dqd[i] * scale;
-                }
-            __syncthreads();
-            // phase B: this wave's keys [wid*KPW, +KPW), all queries of the group
-            for (int r = 0; r < GQ; ++r) {
-                const float qv = qt[r * HD + dl], gv = dot[r * HD + dl];
-                const float* pr = Pt + r * NP + wid * KPW; const float* dr = dSt + r * NP + wid * KPW;
-#pragma unroll
-                for (int j = 0; j < KPW; ++j) { ak[j] += dr[j] * qv; av[j] += pr[j] * gv; }
-            }
-            __syncthreads();
-        }
-    }
-    float* dst = part + ((((size_t)b * heads + h) * gridDim.x + blockIdx.x) * 2) * NP * HD;
-    if (lane < HD) {
-#pragma unroll
-        for (int j = 0; j < KPW; ++j) {
-            dst[(size_t)(wid * KPW + j) * HD + lane] = ak[j];
-            dst[(size_t)NP * HD + (size_t)(wid * KPW + j) * HD + lane] = av[j];
-        }
-    }
-}
-
-// one block of HD threads per (key of the range, head, b): partial [B][heads][slots][2][AL_CK][HD], summed in slot order
-template <typename T, int HD>
-__global__ __launch_bounds__(HD) void attn_long_kv_reduce_k(const float* __restrict__ part, T* __restrict__ dkv, int ld_dkv, int Nkv, int key0, int heads, int slots) {
-    const int l = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
-    const float* p = part + (((size_t)b * heads + h) * slots * 2) * AL_CK * HD + (size_t)l * HD + d;
-    float sk = 0.f, sv = 0.f;
-    for (int c = 0; c < slots; ++c) { sk += p[(size_t)c * 2 * AL_CK * HD]; sv += p[(size_t)c * 2 * AL_CK * HD + (size_t)AL_CK * HD]; }
-    T* dst = dkv + ((size_t)b * Nkv + key0 + l) * ld_dkv;
-    TT<T>::st(dst + h * HD + d, sk);
-    TT<T>::st(dst + heads * HD + h * HD + d, sv);
-}
-
-// dq [rows][ld_dq] <- dqw [rows][Cc] fp32, one rounding
-template <typename T>
-__global__ __launch_bounds__(256) void attn_long_dq_store_k(const float* __restrict__ dqw, T* __restrict__ dq, int ld_dq, size_t rows, int Cc) {
-    const size_t n = rows * Cc;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) TT<T>::st(dq + (i / Cc) * ld_dq + i % Cc, dqw[i]);
-}
-
 // y[n][r][c] = x[n][r][c] * s[n]   (DropPath: per-sample keep mask / keep_prob, timm.models.layers.DropPath used at pvtv2.py:125,148-149)
 template <typename T>
 __global__ __launch_bounds__(256) void scale_samples_k(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ s, const T* __restrict__ res,
@@ -1926,198 +1026,6 @@ int pn2_dwconv3x3_wgrad(int dt, const void* dz, const void* x, float* partial, i
             return pn2_launch<dwconv3x3_wgrad_row_k<T, decltype(vt)::value>>(grid, dim3(256), lds, 0, st, (const T*)dz, (const T*)x, partial, N, H, W, C, p.SEG, p.SPR, p.SPC, p.cvp, (const T*)zpre, (T*)dz_out);
         });
     });
-}
-
-static int attn_geom(int Nkv, int heads, int head_dim) { return ((head_dim == 32 || head_dim == 64) && Nkv >= 1 && Nkv <= 64 * AT_MAXK && heads >= 1) ? 0 : -2; }
-
-// persistent attention blocks per launch: the blocks of one (b, head) share its K / V and walk the query tiles between them
-static int attn_target_blocks() { return 512; }
-static int attn_bwd_gx(int B, int heads, int Nq) {
-    const int ntile = (Nq + 63) / 64;
-    // backward: one block per CU measured best (the block state - K, V, two 64-query tiles, dS / P and their transposes - fills the LDS anyway)
-    int gx = (attn_target_blocks() / 2 + B * heads - 1) / (B * heads);
-    return gx > ntile ? ntile : (gx < 1 ? 1 : gx);
-}
-
-}  // extern "C"
-
-template <int HD>
-static int attn_fwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads,
-                         float scale, hipStream_t st) {
-    const int NK = (Nkv + 63) / 64, NP = NK * 64;
-    const size_t lds = (size_t)2 * HD * (NP + 1) * 4;
-    const int qpb = 64;
-    const dim3 grid((Nq + qpb - 1) / qpb, heads, B);
-#define PN2_ATTN_FWD(NKV) return pn2_launch<attn_fwd_k<T, NKV, HD>>(grid, dim3(256), lds, (int)lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (T*)out, ld_o, lse, Nq, Nkv, heads, scale, qpb);
-    constexpr bool use_mfma = true;
-    if (dt == PN2_BF16 && use_mfma && (ld_q % 8) == 0 && (ld_kv % 8) == 0 && (ld_o % 8) == 0) {
-        const int NPK = NK == 3 ? 256 : NP;                        // 129..192 keys run the 256-key instantiation (zero-padded keys are masked)
-        const size_t lm = ((size_t)NPK * (HD + 8) + (size_t)NPK * at_tr<HD>() + 8 * 16 * (NPK + 8)) * 2;
-        const int ntile = (Nq + 127) / 128;
-        int gx = (attn_target_blocks() + B * heads - 1) / (B * heads); if (gx > ntile) gx = ntile; if (gx < 1) gx = 1;
-        const dim3 gm(gx, heads, B);
-#define PN2_ATTN_FWD_M(NKV) return pn2_launch<attn_fwd_mfma_k<NKV, HD>>(gm, dim3(512), lm, (int)lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (bf16_t*)out, ld_o, lse, Nq, Nkv, heads, scale);
-        if (NK == 1) PN2_ATTN_FWD_M(1) else if (NK == 2) PN2_ATTN_FWD_M(2) else PN2_ATTN_FWD_M(4)
-#undef PN2_ATTN_FWD_M
-    }
-    return with_storage_dtype(dt, [&](auto ty) { using T = type_of<decltype(ty)>; if (NK == 1) PN2_ATTN_FWD(1) else if (NK == 2) PN2_ATTN_FWD(2) else if (NK == 3) PN2_ATTN_FWD(3) else PN2_ATTN_FWD(4) });
-#undef PN2_ATTN_FWD
-}
-
-static bool attn_use_mfma(int dt, int ld_a, int ld_b) {
-    constexpr bool on = true;
-    return on && dt == PN2_BF16 && (ld_a % 8) == 0 && (ld_b % 8) == 0;
-}
-
-template <int HD>
-static int attn_bwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld_kv, const void* out, int ld_o, const void* dout, int ld_do, const float* lse, void* dq, int ld_dq,
-                         void* dkv, int ld_dkv, float* partial, float* delta, int B, int Nq, int Nkv, int heads, float scale, hipStream_t st) {
-    const int NK = (Nkv + 63) / 64, NP = NK * 64;
-    if (attn_use_mfma(dt, ld_q, ld_kv) && (ld_do % 8) == 0 && (ld_dq % 8) == 0) {
-        const int nqt = attn_bwd_gx(B, heads, Nq);                   // persistent blocks (= partial slots) per (b, head)
-        hipLaunchKernelGGL((attn_delta_k<bf16_t, HD>), dim3((unsigned)(((size_t)B * Nq * heads + 3) / 4)), dim3(256), 0, st, (const bf16_t*)dout, ld_do, (const bf16_t*)out, ld_o, delta, B, Nq, heads);
-        const dim3 grid(nqt, heads, B);
-        // 128 keys per launch at both head dims: at HD = 32 a 256-key block would need 161 KiB of LDS (its dS / P transposes are 64 queries wide
-        // whatever HD is), one KiB over the CU's 160
-        for (int key0 = 0; key0 < NP; key0 += 128) {
-            const int nkb = NP - key0 >= 128 ? 2 : 1;
-            const int np = nkb * 64;
-            const size_t lm = ((size_t)np * at_tr<HD>() + (size_t)np * (HD + 8) + 2 * 64 * at_tr<HD>() + 64 * (np + 8) + 2 * (size_t)np * 72) * 2;
-            const int rc = nkb == 2 ? pn2_launch<attn_bwd_mfma_k<2, HD>>(grid, dim3(256), lm, (int)lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta,
-                                                                         (bf16_t*)dq, ld_dq, partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0)
-                                    : pn2_launch<attn_bwd_mfma_k<1, HD>>(grid, dim3(256), lm, (int)lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse, delta,
-                                                                         (bf16_t*)dq, ld_dq, partial, Nq, Nkv, heads, scale, key0, NP, key0 > 0 ? 1 : 0);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL((attn_bwd_kv_reduce_k<bf16_t, HD>), dim3(Nkv, heads, B), dim3(HD), 0, st, partial, (bf16_t*)dkv, ld_dkv, Nkv, NP, heads, nqt);
-        PN2_CHECK_LAUNCH();
-        return 0;
-    }
-    const int nqb = (Nq + AT_QCHUNK - 1) / AT_QCHUNK;
-    // a bf16 view that the MFMA kernels cannot take: its partial has pn2_attn_bwd_blocks(bf16) = attn_bwd_gx slots, fewer than nqb for many (b, head)
-    if (dt == PN2_BF16 && nqb > attn_bwd_gx(B, heads, Nq)) return -2;
-    const int QB = NK == 4 ? 2 : AT_QB;                 // 256 keys: smaller query groups so that K, V and the tiles fit the 160 KiB of LDS
-    const size_t lds = ((size_t)2 * HD * (NP + 1) + 2 * 4 * QB * NP + 2 * 4 * QB * HD) * 4;
-    const dim3 grid(nqb, heads, B);
-#define PN2_ATTN_BWD(NKV, QBV) rc = pn2_launch<attn_bwd_k<T, NKV, QBV, HD>>(grid, dim3(256), lds, (int)lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (const T*)dout, ld_do, lse, (T*)dq, ld_dq, \
-                                                                          partial, Nq, Nkv, heads, scale);
-    return with_storage_dtype(dt, [&](auto ty) {
-        using T = type_of<decltype(ty)>;
-        int rc;
-        if (NK == 1) PN2_ATTN_BWD(1, AT_QB) else if (NK == 2) PN2_ATTN_BWD(2, AT_QB) else if (NK == 3) PN2_ATTN_BWD(3, AT_QB) else PN2_ATTN_BWD(4, 2)
-        if (rc) return rc;
-        return pn2_launch<attn_bwd_kv_reduce_k<T, HD>>(dim3(Nkv, heads, B), dim3(HD), 0, 0, st, partial, (T*)dkv, ld_dkv, Nkv, NP, heads, nqb);
-    });
-#undef PN2_ATTN_BWD
-}
-
-extern "C" {
-
-int pn2_attn_fwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads, int head_dim,
-                 float scale, void* stream) {
-    if (!q || !kv || !out || !lse) return -1;
-    if (int rc = attn_geom(Nkv, heads, head_dim)) return rc;
-    return head_dim == 32 ? attn_fwd_impl<32>(dt, q, ld_q, kv, ld_kv, out, ld_o, lse, B, Nq, Nkv, heads, scale, (hipStream_t)stream)
-                          : attn_fwd_impl<64>(dt, q, ld_q, kv, ld_kv, out, ld_o, lse, B, Nq, Nkv, heads, scale, (hipStream_t)stream);
-}
-
-int pn2_attn_bwd_blocks(int dt, int B, int heads, int Nq) {
-    if (Nq < 1 || B < 1 || heads < 1) return -1;
-    return dt == PN2_BF16 ? attn_bwd_gx(B, heads, Nq) : (Nq + AT_QCHUNK - 1) / AT_QCHUNK;
-}
-
-int pn2_attn_bwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, const void* out, int ld_o, const void* dout, int ld_do, const float* lse, void* dq, int ld_dq,
-                 void* dkv, int ld_dkv, float* partial, float* delta, int B, int Nq, int Nkv, int heads, int head_dim, float scale, void* stream) {
-    if (!q || !kv || !out || !dout || !lse || !dq || !dkv || !partial || !delta) return -1;
-    if (int rc = attn_geom(Nkv, heads, head_dim)) return rc;
-    return head_dim == 32 ? attn_bwd_impl<32>(dt, q, ld_q, kv, ld_kv, out, ld_o, dout, ld_do, lse, dq, ld_dq, dkv, ld_dkv, partial, delta, B, Nq, Nkv, heads, scale, (hipStream_t)stream)
-                          : attn_bwd_impl<64>(dt, q, ld_q, kv, ld_kv, out, ld_o, dout, ld_do, lse, dq, ld_dq, dkv, ld_dkv, partial, delta, B, Nq, Nkv, heads, scale, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ---- pn2_attn_long_*: 1..4096 keys streamed in chunks of AL_CK
-constexpr int AL_MAXKV = 4096;
-static int attn_long_geom(int Nkv, int heads, int head_dim) { return ((head_dim == 32 || head_dim == 64) && Nkv >= 1 && Nkv <= AL_MAXKV && heads >= 1) ? 0 : -2; }
-// partial slots per (b, head) = blocks per (b, head) of one backward launch.  bf16: the one-block-per-CU rule of attn_bwd_gx on both routes (the scalar
-// kernel walks its 256-query chunks the same way); fp32: one block per 256-query chunk
-static int attn_long_slots(int dt, int B, int heads, int Nq) { return dt == PN2_BF16 ? attn_bwd_gx(B, heads, Nq) : (Nq + AT_QCHUNK - 1) / AT_QCHUNK; }
-
-template <int HD>
-static int attn_long_fwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads,
-                              float scale, hipStream_t st) {
-    if (attn_use_mfma(dt, ld_q, ld_kv) && (ld_o % 8) == 0) {
-        constexpr size_t lm = ((size_t)AL_CK * (HD + 8) + (size_t)AL_CK * at_tr<HD>() + 8 * 16 * (AL_CK + 8)) * 2;
-        return pn2_launch<attn_long_fwd_mfma_k<HD>>(dim3((Nq + 127) / 128, heads, B), dim3(512), lm, (int)lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (bf16_t*)out, ld_o,
-                                                    lse, Nq, Nkv, heads, scale);
-    }
-    constexpr size_t lds = ((size_t)2 * HD * (AL_CK + 1) + AL_QPB * HD + 2 * AL_QPB) * 4;
-    return with_storage_dtype(dt, [&](auto ty) {
-        using T = type_of<decltype(ty)>;
-        return pn2_launch<attn_long_fwd_k<T, HD>>(dim3((Nq + AL_QPB - 1) / AL_QPB, heads, B), dim3(256), lds, (int)lds, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (T*)out, ld_o,
-                                                  lse, Nq, Nkv, heads, scale);
-    });
-}
-
-template <int HD>
-static int attn_long_bwd_impl(int dt, const void* q, int ld_q, const void* kv, int ld_kv, const void* out, int ld_o, const void* dout, int ld_do, const float* lse, void* dq, int ld_dq,
-                              void* dkv, int ld_dkv, float* partial, float* delta, float* dqw, int B, int Nq, int Nkv, int heads, float scale, hipStream_t st) {
-    const bool mfma = attn_use_mfma(dt, ld_q, ld_kv) && (ld_do % 8) == 0;
-    const int slots = attn_long_slots(dt, B, heads, Nq);
-    const dim3 grid(slots, heads, B);
-    const unsigned nd = (unsigned)(((size_t)B * Nq * heads + 3) / 4);
-    constexpr size_t lm = ((size_t)AL_CK * at_tr<HD>() + (size_t)AL_CK * (HD + 8) + 2 * 64 * at_tr<HD>() + 64 * (AL_CK + 8) + 2 * (size_t)AL_CK * 72) * 2;
-    constexpr size_t ls = ((size_t)2 * HD * (AL_CK + 1) + 2 * 4 * AT_QB * AL_CK + 2 * 4 * AT_QB * HD) * 4;
-    return with_storage_dtype(dt, [&](auto ty) {
-        using T = type_of<decltype(ty)>;
-        if (int rc = pn2_launch<attn_delta_k<T, HD>>(dim3(nd), dim3(256), 0, 0, st, (const T*)dout, ld_do, (const T*)out, ld_o, delta, B, Nq, heads)) return rc;
-        for (int key0 = 0; key0 < Nkv; key0 += AL_CK) {              // plain launches in stream order: fixed summation order, no atomics
-            int rc;
-            if (mfma) rc = pn2_launch<attn_long_bwd_mfma_k<HD>>(grid, dim3(256), lm, (int)lm, st, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, (const bf16_t*)dout, ld_do, lse,
-                                                                (const float*)delta, dqw, partial, Nq, Nkv, heads, scale, key0, key0 > 0 ? 1 : 0);
-            else rc = pn2_launch<attn_long_bwd_k<T, HD>>(grid, dim3(256), ls, (int)ls, st, (const T*)q, ld_q, (const T*)kv, ld_kv, (const T*)dout, ld_do, lse, (const float*)delta, dqw, partial,
-                                                         Nq, Nkv, heads, scale, key0, key0 > 0 ? 1 : 0);
-            if (rc) return rc;
-            const int nk = Nkv - key0 < AL_CK ? Nkv - key0 : AL_CK;
-            if ((rc = pn2_launch<attn_long_kv_reduce_k<T, HD>>(dim3(nk, heads, B), dim3(HD), 0, 0, st, (const float*)partial, (T*)dkv, ld_dkv, Nkv, key0, heads, slots))) return rc;
-        }
-        const size_t rows = (size_t)B * Nq;
-        return pn2_launch<attn_long_dq_store_k<T>>(dim3(grid_for(rows * heads * HD, GRID_CAP)), dim3(256), 0, 0, st, (const float*)dqw, (T*)dq, ld_dq, rows, heads * HD);
-    });
-}
-
-extern "C" {
-
-int pn2_attn_long_fwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, void* out, int ld_o, float* lse, int B, int Nq, int Nkv, int heads, int head_dim,
-                      float scale, void* stream) {
-    if (!q || !kv || !out || !lse) return -1;
-    if (int rc = attn_long_geom(Nkv, heads, head_dim)) return rc;
-    if (B < 1 || Nq < 1) return -2;
-    return head_dim == 32 ? attn_long_fwd_impl<32>(dt, q, ld_q, kv, ld_kv, out, ld_o, lse, B, Nq, Nkv, heads, scale, (hipStream_t)stream)
-                          : attn_long_fwd_impl<64>(dt, q, ld_q, kv, ld_kv, out, ld_o, lse, B, Nq, Nkv, heads, scale, (hipStream_t)stream);
-}
-
-int pn2_attn_long_bwd_blocks(int dt, int B, int heads, int Nq) {
-    if (Nq < 1 || B < 1 || heads < 1) return -1;
-    return attn_long_slots(dt, B, heads, Nq);
-}
-
-int pn2_attn_long_bwd_workspace(int dt, int B, int Nq, int heads, int head_dim, long long* floats) {
-    if (!floats) return -1;
-    if (Nq < 1 || B < 1 || attn_long_geom(1, heads, head_dim)) return -2;
-    floats[0] = (long long)B * heads * attn_long_slots(dt, B, heads, Nq) * 2 * AL_CK * head_dim;
-    floats[1] = (long long)B * heads * Nq;
-    floats[2] = (long long)B * Nq * heads * head_dim;
-    return 0;
-}
-
-int pn2_attn_long_bwd(int dt, const void* q, int ld_q, const void* kv, int ld_kv, const void* out, int ld_o, const void* dout, int ld_do, const float* lse, void* dq, int ld_dq,
-                      void* dkv, int ld_dkv, float* partial, float* delta, float* dq_acc, int B, int Nq, int Nkv, int heads, int head_dim, float scale, void* stream) {
-    if (!q || !kv || !out || !dout || !lse || !dq || !dkv || !partial || !delta || !dq_acc) return -1;
-    if (int rc = attn_long_geom(Nkv, heads, head_dim)) return rc;
-    if (B < 1 || Nq < 1) return -2;
-    return head_dim == 32 ? attn_long_bwd_impl<32>(dt, q, ld_q, kv, ld_kv, out, ld_o, dout, ld_do, lse, dq, ld_dq, dkv, ld_dkv, partial, delta, dq_acc, B, Nq, Nkv, heads, scale, (hipStream_t)stream)
-                          : attn_long_bwd_impl<64>(dt, q, ld_q, kv, ld_kv, out, ld_o, dout, ld_do, lse, dq, ld_dq, dkv, ld_dkv, partial, delta, dq_acc, B, Nq, Nkv, heads, scale, (hipStream_t)stream);
 }
 
 int pn2_scale_samples(int dt, const void* x, void* y, const float* scale, const void* res, int N, long long per_sample, void* stream) {

@@ -1,4 +1,4 @@
-"""float64 restatement of what the streamed attention kernels (csrc/pn2_vit.hip, pn2_attn_long_*) compute, and the rows built to break a streaming
+"""float64 restatement of what the streamed attention kernels (csrc/pn2_attn.hip, pn2_attn_long_*) compute, and the rows built to break a streaming
 softmax that the CPU and GPU tests share.  Not a test module.
 
 Forward, per chunk of `chunk` keys with m / l / O the running maximum, sum and un-normalised output of a row:

@@ -1,6 +1,6 @@
-"""GPU tests of attention over more than 256 keys (pn2_attn_long_fwd / pn2_attn_long_bwd, csrc/pn2_vit.hip: keys streamed in 128-key chunks with an
+"""GPU tests of attention over more than 256 keys (pn2_attn_long_fwd / pn2_attn_long_bwd, csrc/pn2_attn.hip: keys streamed in 128-key chunks with an
 online softmax): the C ABI against float64 torch at head_dim 32 and 64, fp32 and bf16, on shapes at the edges of the chunking and on rows built to
-break a streaming softmax (tests/attnlongref.py); refusals; both kernel families on one input; determinism; the fp32 dQ accumulation;
+break a streaming softmax (tests/attnlongref.py); refusals; both kernel families on one input (and bit for bit up to one chunk); determinism; the fp32 dQ accumulation;
 Engine.attention's routing; and the PVTv2 models, Trainer capture / replay and VolumePredictor at 544^2 and 288 x 960."""
 import ctypes as C
 import os
@@ -20,7 +20,7 @@ import emcad_b0ref as R  # noqa: E402
 from test_gpu_pvt import relmax, rell2  # noqa: E402
 
 dev = "cuda"
-CHUNK = 128                                             # AL_CK of csrc/pn2_vit.hip, both kernel routes, forward and backward
+CHUNK = 128                                             # AL_CK of csrc/pn2_attn.hip, both kernel routes, forward and backward
 P_ = lambda t: C.c_void_p(t.data_ptr())
 
 
@@ -180,6 +180,24 @@ def test_attention_long_refusals():
 def test_both_families_meet_the_float64_bounds_on_one_input(Nkv, hd, dtn):
     for long in (False, True):
         _all_views(long, dtn, hd, 2, 130, Nkv)
+
+
+@pytest.mark.parametrize("pads", [(0, 0), (16, 8)])
+@pytest.mark.parametrize("hd", [32, 64])
+@pytest.mark.parametrize("case", [(2, 130, 128), (1, 63, 100), (5, 70, 49)])
+def test_both_families_give_the_same_bits_up_to_one_chunk(case, hd, pads):
+    """bf16 MFMA route, at most 128 keys: one key range, a first-chunk factor of 0, the same slot count and slot order - the two families run the same
+    arithmetic on every row, so out, lse, dq and dkv agree bit for bit."""
+    heads, Nq, Nkv = case
+    q, kv, do = _data(heads, hd, Nq, Nkv)
+    short = _launch(False, "bf16", hd, heads, q, kv, do, *pads)
+    long = _launch(True, "bf16", hd, heads, q, kv, do, *pads)
+    Cc = heads * hd
+    for name, x, y, n in zip(("out", "dq", "dkv", "lse"), short, long, (Cc, Cc, 2 * Cc, Nq)):
+        x, y = x[..., :n].float(), y[..., :n].float()
+        print(f"\n{name} hd{hd} {case} pad{pads}: max |short - long| {float((x - y).abs().max()):.3e}, {int((x != y).sum())} of {x.numel()} differ")
+    for name, x, y, n in zip(("out", "dq", "dkv", "lse"), short, long, (Cc, Cc, 2 * Cc, Nq)):
+        assert torch.equal(x[..., :n], y[..., :n]), name
 
 
 @pytest.mark.parametrize("dtn", ["fp32", "bf16"])
