@@ -367,17 +367,24 @@ __global__ __launch_bounds__(256) void dwconv3x3_row_k(const T* __restrict__ x, 
         float a[VT], xv[VT];
 #pragma unroll
         for (int e = 0; e < VT; ++e) a[e] = br[e];
+        // bf16: every product a written-out fused multiply-add, row-major taps on top of the bias - the fp32 sum of dwconv3x3_win_k bit for bit, so the two bf16
+        // routes store the same values (left to the compiler, a few products stayed unfused, and where the ten terms cancel the last fp32 bit was up to 29
+        // bf16 ulps of the result).  fp32 has no window twin and keeps the compiler's contraction.
+        auto mac = [](float w_, float x_, float a_) {
+            if constexpr (sizeof(T) == 2) return __builtin_fmaf(w_, x_, a_);
+            else return a_ + w_ * x_;
+        };
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             c0[r].unpack(xv);
 #pragma unroll
-            for (int e = 0; e < VT; ++e) a[e] += wr[r * 3][e] * xv[e];
+            for (int e = 0; e < VT; ++e) a[e] = mac(wr[r * 3][e], xv[e], a[e]);
             c1[r].unpack(xv);
 #pragma unroll
-            for (int e = 0; e < VT; ++e) a[e] += wr[r * 3 + 1][e] * xv[e];
+            for (int e = 0; e < VT; ++e) a[e] = mac(wr[r * 3 + 1][e], xv[e], a[e]);
             c2[r].unpack(xv);
 #pragma unroll
-            for (int e = 0; e < VT; ++e) a[e] += wr[r * 3 + 2][e] * xv[e];
+            for (int e = 0; e < VT; ++e) a[e] = mac(wr[r * 3 + 2][e], xv[e], a[e]);
         }
         const size_t o = ((size_t)row * W + ox) * C + cv * VT;
         Vec ov;
@@ -408,9 +415,10 @@ __global__ __launch_bounds__(256) void dwconv3x3_row_k(const T* __restrict__ x, 
 //     rotation of both), so nothing is moved and a column is fetched three steps before it is unpacked;
 //   * halo rows, image border and segment end are buffer-descriptor range checks (offset with bit 31 set: loads return zeros, stores are dropped) - plain
 //     integer arithmetic on byte offsets, no branches in the walk.  Tensors below 2 GB (host).
-// Same order of the nine products per channel as dwconv3x3_row_k (row-major taps on top of the bias), every one a fused multiply-add; the compiler had left
-// a few of the old walk's products unfused (v_pk_mul + v_pk_add), so the two agree to the last fp32 bit or two - 1-ulp flips of the bf16 outputs
-// (tools/dw_check.py: both sit at the bf16 rounding error against a float64 conv).
+// Same order of the nine products per channel as dwconv3x3_row_k (row-major taps on top of the bias), every one a fused multiply-add; the row walk
+// writes its fused multiply-adds out too (the compiler had left a few of its products unfused, v_pk_mul + v_pk_add), so the two form the same fp32 sum and
+// store the same bf16 values (tests/test_gpu_vit_kernels.py: accumulate = 1 onto zeros against accumulate = 0; both sit at the bf16 rounding error against
+// a float64 conv).
 // Measured (tools/dw_micro.py, 16 x 88 x 88 x 512): conv + GELU 130 -> 108 us, data gradient 84 -> 62, weight gradient 100 -> 71, with dz = dy * gelu'(z) 155 -> 122;
 // PVT_PraNet_V2 bs 16: 10.93 -> 10.69 ms per step.  The instruction count fell 2.5-3x, the time by a quarter: with loads and stores switched off the walk still
 // takes 52 of 55 us (tools/dw_dbg.py) - what is left is issue-bound at roughly twice the ideal 4 cycles per wave instruction.

@@ -1,4 +1,5 @@
-"""GPU parity tests of the PVTv2 encoder path (config 4): every new op through the C ABI against torch on the CPU (float64), one
+"""GPU parity tests of the PVTv2 encoder path (config 4): every new op through `Engine` against torch on the CPU (float64) with one
+global number per tensor (the kernels themselves are driven through the C ABI, entry by entry, in test_gpu_vit_kernels.py), one
 transformer Block against the oracle, and the whole PVT_PraNet_V2 training forward/backward against the vectors the imported reference
 produced (tests/golden/pvt_pranet_v2_96.npz, DropPath off).  Tolerances as in test_gpu_parity.py."""
 import os
