@@ -486,6 +486,19 @@ int pn2_upsample_nearest2x_bwd(int dt, const void* dy, void* dx, int N, int H, i
 /* y[p][c] = a[p][perm[c]] + b[p][perm[c]] + c[p][perm[c]]   (b, c optional): the MSDC branch sum written through channel_shuffle, and (with the
  * inverse permutation, b = c = null) its adjoint */
 int pn2_gather_sum(int dt, const void* a, const void* b, const void* c, const int* perm, void* y, long long M, int C, void* stream);
+/* The MSCB combine step for every decoder switch: channel_shuffle(sum or cat of n MSDC branches, groups) in one pass, without a permutation table.
+ *   parts p0 .. p(n-1), 1 <= n <= 4, each [M][Cpart] in dt (bf16 / fp32), the rest ignored;  src(j) = (j % groups) * (Cw / groups) + j / groups
+ *   mode 0 (sum): y [M][Cpart], Cw = Cpart     : y[p][j] = ((p0 + p1) + p2) + p3 at [p][src(j)], summed in fp32 in that order, rounded once (n = 1: a move)
+ *   mode 1 (cat): y [M][n*Cpart], Cw = n*Cpart : y[p][j] = cat(p0 .. p(n-1))[p][src(j)], bit for bit
+ * pn2_msdc_combine_bwd is the adjoint of mode 1 with the FORWARD's groups: d_i[p][c] (+)= dy[p][dst(i*Cpart + c)], dst = src^-1, acc_i = 1 adds (in fp32,
+ * rounded once) to what d_i holds.  The adjoint of mode 0 is mode 0 itself on dy with n = 1 and groups' = Cw / groups.
+ * 16-byte global loads and stores; the [groups][Cw/groups] transpose of a tile of pn2_msdc_combine_tile(dt, Cw, groups) pixels x Cw channels goes through at
+ * most 64 KiB of LDS.  -1: a null pointer among p0 .. p(n-1), y, dy, d0 .. d(n-1).  -2: n outside 1..4, mode outside 0..1, Cpart not a multiple of the
+ * 16-byte vector (8 bf16 / 4 fp32), Cw % groups != 0, Cw > 16384, M < 1 or more than 2^31 - 1 tiles.  -3: dt.  Indexing is 64-bit. */
+int pn2_msdc_combine_tile(int dt, int Cw, int groups);      /* pixels per workgroup (the adjoint runs with Cw / groups of the forward); -2 = not built */
+int pn2_msdc_combine(int dt, int mode, int n, const void* p0, const void* p1, const void* p2, const void* p3, void* y, long long M, int Cpart, int groups, void* stream);
+int pn2_msdc_combine_bwd(int dt, int n, const void* dy, void* d0, void* d1, void* d2, void* d3, int acc0, int acc1, int acc2, int acc3, long long M, int Cpart,
+                         int groups, void* stream);
 /* y = sigmoid(x) as fp32 [n] from a [rows][ld] map with C used channels; dx (+)= dy * y * (1 - y) */
 int pn2_sigmoid(int dt_in, const void* x, int ld, int C, float* y, long long n, void* stream);
 int pn2_sigmoid_bwd(int dt_out, const float* dy, const float* y, void* dx, int ld, int C, long long n, int accumulate, void* stream);

@@ -5,6 +5,7 @@
 //   global average + max pooling, channel mean + max             CAB :234-237, SAB :253-255
 //   nearest x2 up-sampling                                       EUCB :171
 //   sum of the three MSDC branches written through channel_shuffle   MSCB.forward :147-154 with channel_shuffle :69-77
+//   sum / concatenation of up to four branches, shuffled through LDS  the same step for the other decoder switches (add = False, four kernel sizes)
 //   sigmoid on small fp32 maps                                   CAB / SAB / LGAG.psi
 // All element-wise / memory-bound; BatchNorm statistics come out of the producing kernel as per-block partial rows, like the conv
 // epilogue of pn2_conv.hip, so pn2_bn_finalize / pn2_affine_act / pn2_bn_bwd_* are reused unchanged.  Deterministic (no atomics).
@@ -593,6 +594,117 @@ __global__ __launch_bounds__(256) void gather_sum_k(const T* __restrict__ a, con
         if (c3) v += TT<T>::ld(c3 + s);
         TT<T>::st(y + idx, v);
     }
+}
+
+// ------------------------------------------------------------------------------------------ MSDC combine: sum / concatenation of up to 4 branches through channel_shuffle
+// y[p][j] = in[p][src(j)], src(j) = (j % groups) * cpg + j / groups, cpg = Cw / groups: per pixel the [groups][cpg] matrix `in` is written as its transpose.
+//   MC_SUM    in = ((p0 + p1) + p2) + p3 in fp32, rounded once (Cw = Cpart)          MC_CAT   in = cat(p0 .. p3) (Cw = n * Cpart), a move
+//   MC_SPLIT  in = one tensor of width Cw, y = cat(out0 .. out3), each out (+)= its slice: the adjoint of MC_CAT when launched with groups' = cpg
+// A block owns TP pixels x the whole row.  Phase 1: 16-byte global loads, the sum, and a scalar scatter into LDS IN OUTPUT ORDER; phase 2: ds_read_b128 of
+// consecutive output channels and 16-byte global stores.  LDS row of a pixel = cpg transposed rows of `groups` elements; where that pitch is a multiple of
+// 128 bytes (all 32 banks of a store) every transposed row starts on bank 0 and the lanes of a scatter store, which differ in their transposed row, pile up
+// on one bank - each row is then padded by 16 bytes (4 banks; a multiple of the vector, so phase 2 stays aligned).  Other pitches are left linear.
+enum { MC_SUM = 0, MC_CAT = 1, MC_SPLIT = 2 };
+constexpr int MC_MAX_CW = 16384, MC_TILE_BYTES = 16384, MC_MAX_TP = 256;
+struct McArgs { const void* in[4]; void* out[4]; int acc[4]; };
+template <typename T> struct McRaw { typedef unsigned short type; };
+template <> struct McRaw<float> { typedef unsigned type; };
+__device__ __forceinline__ void mc_unpack(const uint4& q, unsigned short* r) {
+    r[0] = (unsigned short)q.x; r[1] = (unsigned short)(q.x >> 16); r[2] = (unsigned short)q.y; r[3] = (unsigned short)(q.y >> 16);
+    r[4] = (unsigned short)q.z; r[5] = (unsigned short)(q.z >> 16); r[6] = (unsigned short)q.w; r[7] = (unsigned short)(q.w >> 16);
+}
+__device__ __forceinline__ void mc_unpack(const uint4& q, unsigned* r) { r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w; }
+template <typename P> __device__ __forceinline__ P mc_pick(P const (&a)[4], int i) { return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3]; }
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void msdc_combine_k(McArgs A, int n, size_t M, int Cpart, int Cw, int groups, int padE, int TP) {
+    typedef typename McRaw<T>::type R;
+    constexpr int V = TT<T>::VEC;
+    extern __shared__ uint4 mc_sh[];
+    R* sh = reinterpret_cast<R*>(mc_sh);
+    const int cpg = Cw / groups, CV = Cw / V, pitch = groups + padE, rowE = cpg * pitch;
+    const size_t p0 = (size_t)blockIdx.x * TP;
+    const int nvec = (int)min((size_t)TP, M - p0) * CV;
+    for (int v = threadIdx.x; v < nvec; v += 256) {
+        const int pl = v / CV, s = (v - pl * CV) * V;
+        const size_t p = p0 + pl;
+        uint4 q;
+        if (MODE == MC_SUM && n > 1) {
+            float a[V], b[V];
+            ldv<T>((const T*)A.in[0] + p * Cw + s, a);
+            ldv<T>((const T*)A.in[1] + p * Cw + s, b);
+#pragma unroll
+            for (int e = 0; e < V; ++e) a[e] += b[e];
+            if (n > 2) { ldv<T>((const T*)A.in[2] + p * Cw + s, b);
+#pragma unroll
+                for (int e = 0; e < V; ++e) a[e] += b[e]; }
+            if (n > 3) { ldv<T>((const T*)A.in[3] + p * Cw + s, b);
+#pragma unroll
+                for (int e = 0; e < V; ++e) a[e] += b[e]; }
+            q = TT<T>::pack(a);
+        } else if (MODE == MC_CAT) {
+            const int i = s / Cpart;          // Cpart is a multiple of V: a vector lies in one part
+            q = *reinterpret_cast<const uint4*>((const T*)mc_pick(A.in, i) + p * Cpart + (s - i * Cpart));
+        } else {
+            q = *reinterpret_cast<const uint4*>((const T*)A.in[0] + p * Cw + s);
+        }
+        R r[V];
+        mc_unpack(q, r);
+        R* row = sh + pl * rowE;
+        int a = s % cpg, g = s / cpg;          // source channel s = g * cpg + a goes to output channel a * groups + g
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            row[a * pitch + g] = r[e];
+            if (++a == cpg) { a = 0; ++g; }
+        }
+    }
+    __syncthreads();
+    for (int v = threadIdx.x; v < nvec; v += 256) {
+        const int pl = v / CV, j = (v - pl * CV) * V;
+        const size_t p = p0 + pl;
+        const uint4 q = *reinterpret_cast<const uint4*>(sh + pl * rowE + (padE ? j + (j / groups) * padE : j));      // padE > 0 only where groups % V == 0
+        if (MODE != MC_SPLIT) {
+            *reinterpret_cast<uint4*>((T*)A.out[0] + p * Cw + j) = q;
+        } else {
+            const int i = j / Cpart;
+            T* d = (T*)mc_pick(A.out, i) + p * Cpart + (j - i * Cpart);
+            if (mc_pick(A.acc, i)) {
+                float x[V], o[V];
+                TT<T>::unpack(q, x);
+                ldv<T>(d, o);
+#pragma unroll
+                for (int e = 0; e < V; ++e) o[e] += x[e];
+                stv<T>(d, o);
+            } else {
+                *reinterpret_cast<uint4*>(d) = q;
+            }
+        }
+    }
+}
+
+/* tile of msdc_combine_k for rows of Cw channels shuffled in `groups`: row padding (elements), pixels per block, LDS bytes; -2 = not built */
+inline int mc_geometry(int dt, int Cw, int groups, int& padE, int& TP, size_t& lds) {
+    const int V = vec_of(dt), sz = 16 / V;
+    if (Cw < V || Cw % V || Cw > MC_MAX_CW || groups < 1 || Cw % groups) return -2;
+    const int cpg = Cw / groups;
+    padE = (cpg > 1 && ((size_t)groups * sz) % 128 == 0) ? V : 0;
+    size_t row = (size_t)(Cw + cpg * padE) * sz;
+    if (row > 64 * 1024) { padE = 0; row = (size_t)Cw * sz; }          // (fp32 rows of 16384 channels: exactly the default LDS, unpadded)
+    const size_t tp = MC_TILE_BYTES / row;
+    TP = tp < 1 ? 1 : (tp > (size_t)MC_MAX_TP ? MC_MAX_TP : (int)tp);
+    lds = (size_t)TP * row;
+    return 0;
+}
+template <int MODE>
+inline int mc_launch(int dt, const McArgs& A, int n, long long M, int Cpart, int Cw, int groups, void* stream) {
+    int padE, TP; size_t lds;
+    if (mc_geometry(dt, Cw, groups, padE, TP, lds)) return -2;
+    const long long nblk = (M + TP - 1) / TP;
+    if (nblk > 0x7fffffffLL) return -2;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<msdc_combine_k<T, MODE>>(dim3((unsigned)nblk), dim3(256), lds, 0, (hipStream_t)stream, A, n, (size_t)M, Cpart, Cw, groups, padE, TP);
+    });
 }
 
 // ------------------------------------------------------------------------------------------ sigmoid on small maps
@@ -1418,6 +1530,37 @@ int pn2_gather_sum(int dt, const void* a, const void* b, const void* c, const in
         using T = type_of<decltype(ty)>;
         return pn2_launch<gather_sum_k<T>>(dim3(grid_for((size_t)M * C, GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)a, (const T*)b, (const T*)c, perm, (T*)y, (size_t)M, C);
     });
+}
+
+/* pixels per workgroup of pn2_msdc_combine / pn2_msdc_combine_bwd at an output width of Cw channels shuffled in `groups` (the kernel's own `groups`: Cw / groups
+ * of the forward for the adjoint); -2 where the shape is not built */
+int pn2_msdc_combine_tile(int dt, int Cw, int groups) {
+    int padE, TP; size_t lds;
+    return mc_geometry(dt, Cw, groups, padE, TP, lds) ? -2 : TP;
+}
+
+/* channel_shuffle(sum or cat of n MSDC branches, groups) in one pass: pn2.h */
+int pn2_msdc_combine(int dt, int mode, int n, const void* p0, const void* p1, const void* p2, const void* p3, void* y, long long M, int Cpart, int groups, void* stream) {
+    if (n < 1 || n > 4 || (mode != MC_SUM && mode != MC_CAT)) return -2;
+    McArgs A = {{p0, p1, p2, p3}, {y, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};
+    for (int i = 0; i < n; ++i) if (!A.in[i]) return -1;
+    if (!y) return -1;
+    if (M < 1 || Cpart < 1 || Cpart % vec_of(dt) || Cpart > MC_MAX_CW) return -2;
+    const int Cw = mode == MC_CAT ? n * Cpart : Cpart;
+    return mode == MC_CAT ? mc_launch<MC_CAT>(dt, A, n, M, Cpart, Cw, groups, stream) : mc_launch<MC_SUM>(dt, A, n, M, Cpart, Cw, groups, stream);
+}
+
+/* adjoint of the cat mode: d_i[p][c] (+)= dy[p][dst(i * Cpart + c)], dst the inverse of the forward's src */
+int pn2_msdc_combine_bwd(int dt, int n, const void* dy, void* d0, void* d1, void* d2, void* d3, int acc0, int acc1, int acc2, int acc3, long long M, int Cpart,
+                         int groups, void* stream) {
+    if (n < 1 || n > 4) return -2;
+    McArgs A = {{dy, nullptr, nullptr, nullptr}, {d0, d1, d2, d3}, {acc0, acc1, acc2, acc3}};
+    if (!dy) return -1;
+    for (int i = 0; i < n; ++i) if (!A.out[i]) return -1;
+    if (M < 1 || Cpart < 1 || Cpart % vec_of(dt) || Cpart > MC_MAX_CW || groups < 1) return -2;
+    const int Cw = n * Cpart;
+    if (Cw % groups) return -2;
+    return mc_launch<MC_SPLIT>(dt, A, n, M, Cpart, Cw, Cw / groups, stream);
 }
 
 /* y = sigmoid(x) as fp32 [n] from a [rows][ld] map with C used channels; dx (+)= dy * y * (1 - y) */

@@ -2,9 +2,19 @@
 
 Same class names, constructor signatures and parameter names (state_dict keys) as the reference; the computation is expressed in
 engine ops (pn2/engine.py + ops_*.py): 1x1 / 3x3 / 7x7 convs on the implicit-GEMM kernels, BatchNorm on pn2_bn_*, and the depth-wise, grouped,
-gating, pooling, shuffle and up-sampling pieces on csrc/pn2_emcad.hip.  Only the configuration the reference trains (train_synapse.py:
-kernel_sizes [1,3,5], expansion 2, dw_parallel, add, stride 1, lgag_ks 3, relu6 in the MSCBs) is built; other switches raise.
-No PyTorch fallback: forward needs the GPU library.
+gating, pooling, shuffle and up-sampling pieces on csrc/pn2_emcad.hip.  No PyTorch fallback: forward needs the GPU library.
+
+The decoder switches of the reference's train_synapse.py (--kernel_sizes, --expansion_factor, --lgag_ks, --no_dw_parallel, --concatenation) are built
+within these limits; anything else raises NotImplementedError (or the assert named below):
+  kernel_sizes      1 to 4 sizes drawn from {1, 3, 5}, repeats allowed ([3,3,3], [5], [1,3,5,5]); a size of 7 or more, or a fifth branch, raises
+  dw_parallel       True (every branch sees the same input) or False (sequential: branch i + 1 sees x + the outputs of branches 0..i)
+  add               True: the branches are summed (three or fewer on pn2_gather_sum, four on pn2_msdc_combine); False: concatenated and shuffled in one
+                    pass (pn2_msdc_combine, cat mode), pconv2 takes the n_scales * ex_channels wide input
+  expansion_factor  any integer that keeps ex_channels a multiple of 8
+  lgag_ks           3 (grouped 3x3 pair convs) or 1 (the reference then forces groups = 1: dense biased 1x1 convs on the pointwise conv path)
+  activation        relu / relu6; leakyrelu, prelu, gelu and hswish raise
+  MSCB              stride 1 and in_channels == out_channels stay asserted: EMCADNet builds nothing else
+The default configuration ([1,3,5], expansion 2, parallel, add, lgag_ks 3, relu6) runs exactly the launches it ran before the switches were built.
 """
 import math
 
@@ -64,11 +74,19 @@ def _act_code(m):
 
 
 class MSDC(nn.Module):
-    """Multi-scale depth-wise convolutions (:83-102): parallel k x k depth-wise conv + BN + act for every k."""
+    """Multi-scale depth-wise convolutions (:83-102): k x k depth-wise conv + BN + act for every k, on the same input (dw_parallel) or each on the
+    input plus the outputs of the branches before it (sequential, :117-126)."""
+    MAX_BRANCHES, SIZES = 4, (1, 3, 5)
 
     def __init__(self, in_channels, kernel_sizes, stride, activation='relu6', dw_parallel=True):
         super().__init__()
-        assert stride == 1 and dw_parallel, "only the stride-1 parallel configuration is built"
+        assert stride == 1, "only the stride-1 configuration is built"
+        kernel_sizes = list(kernel_sizes)
+        if not 1 <= len(kernel_sizes) <= self.MAX_BRANCHES:
+            raise NotImplementedError('MSDC with %d branches is not built (1 to %d kernel sizes)' % (len(kernel_sizes), self.MAX_BRANCHES))
+        for k in kernel_sizes:
+            if k not in self.SIZES:
+                raise NotImplementedError('depth-wise kernel size %r is not built: the depth-wise kernels stop at 5 x 5 (sizes 1, 3, 5)' % (k,))
         self.in_channels, self.kernel_sizes, self.activation, self.dw_parallel = in_channels, kernel_sizes, activation, dw_parallel
         self.dwconvs = nn.ModuleList([
             nn.Sequential(nn.Conv2d(in_channels, in_channels, k, stride, k // 2, groups=in_channels, bias=False), nn.BatchNorm2d(in_channels), act_layer(activation, inplace=True))
@@ -76,7 +94,14 @@ class MSDC(nn.Module):
         _init_weights(self)
 
     def _build(self, eng, x):
-        return [eng.dwconv_bn_act(x, seq[0], seq[1], relu=_act_code(seq[2])) for seq in self.dwconvs]
+        if self.dw_parallel:
+            return [eng.dwconv_bn_act(x, seq[0], seq[1], relu=_act_code(seq[2])) for seq in self.dwconvs]
+        outs = []
+        for i, seq in enumerate(self.dwconvs):
+            outs.append(eng.dwconv_bn_act(x, seq[0], seq[1], relu=_act_code(seq[2])))
+            if i + 1 < len(self.dwconvs):         # (the reference also forms the sum behind the last branch and drops it)
+                x = eng.add(x, outs[-1])
+        return outs
 
 
 class MSCB(nn.Module):
@@ -84,21 +109,27 @@ class MSCB(nn.Module):
 
     def __init__(self, in_channels, out_channels, stride, kernel_sizes=[1, 3, 5], expansion_factor=2, dw_parallel=True, add=True, activation='relu6'):
         super().__init__()
-        assert stride == 1 and add and in_channels == out_channels, "only the stride-1 / add / in == out configuration is built"
+        assert stride == 1 and in_channels == out_channels, "only the stride-1 / in == out configuration is built"
         self.in_channels, self.out_channels, self.stride, self.kernel_sizes = in_channels, out_channels, stride, kernel_sizes
         self.expansion_factor, self.dw_parallel, self.add, self.activation = expansion_factor, dw_parallel, add, activation
         self.n_scales = len(kernel_sizes)
         self.use_skip_connection = True
         self.ex_channels = int(in_channels * expansion_factor)
+        if expansion_factor != int(expansion_factor) or self.ex_channels < 8 or self.ex_channels % 8:
+            raise NotImplementedError('expansion_factor %r is not built: an integer that keeps ex_channels (%d) a multiple of 8' % (expansion_factor, self.ex_channels))
         self.pconv1 = nn.Sequential(nn.Conv2d(in_channels, self.ex_channels, 1, 1, 0, bias=False), nn.BatchNorm2d(self.ex_channels), act_layer(activation, inplace=True))
         self.msdc = MSDC(self.ex_channels, kernel_sizes, stride, activation, dw_parallel=dw_parallel)
-        self.combined_channels = self.ex_channels
+        self.combined_channels = self.ex_channels if add else self.ex_channels * self.n_scales
         self.pconv2 = nn.Sequential(nn.Conv2d(self.combined_channels, out_channels, 1, 1, 0, bias=False), nn.BatchNorm2d(out_channels))
         _init_weights(self)
 
     def _build(self, eng, x):
         t = eng.conv_bn_act(x, self.pconv1[0], self.pconv1[1], relu=_act_code(self.pconv1[2]))
-        dout = eng.shuffled_sum(self.msdc._build(eng, t), gcd(self.combined_channels, self.out_channels))
+        parts, groups = self.msdc._build(eng, t), gcd(self.combined_channels, self.out_channels)
+        if self.add:         # a sequential branch output has a second consumer (the next branch's input): no shared gradient tensor then
+            dout = eng.shuffled_sum(parts, groups, shared_grad=self.dw_parallel or len(parts) == 1)
+        else:
+            dout = eng.shuffled_cat(parts, groups)
         return eng.conv_bn_act(dout, self.pconv2[0], self.pconv2[1], residual=x)
 
 
@@ -133,7 +164,11 @@ class LGAG(nn.Module):
         super().__init__()
         if kernel_size == 1:
             groups = 1
-        assert kernel_size == 3 and groups == F_int and F_g == 2 * F_int and F_l == 2 * F_int and activation == 'relu', "only the EMCAD configuration (3x3, groups = F_int = C/2) is built"
+        if kernel_size not in (1, 3):
+            raise NotImplementedError('LGAG kernel size %r is not built (1 or 3)' % (kernel_size,))
+        assert F_g == F_l and activation == 'relu' and (kernel_size == 1 or (groups == F_int and F_g == 2 * F_int)), \
+            "only the EMCAD configurations (3x3 with groups = F_int = C/2, or dense 1x1) are built"
+        self.kernel_size = kernel_size
         self.W_g = nn.Sequential(nn.Conv2d(F_g, F_int, kernel_size=kernel_size, stride=1, padding=kernel_size // 2, groups=groups, bias=True), nn.BatchNorm2d(F_int))
         self.W_x = nn.Sequential(nn.Conv2d(F_l, F_int, kernel_size=kernel_size, stride=1, padding=kernel_size // 2, groups=groups, bias=True), nn.BatchNorm2d(F_int))
         self.psi = nn.Sequential(nn.Conv2d(F_int, 1, kernel_size=1, stride=1, padding=0, bias=True), nn.BatchNorm2d(1), nn.Sigmoid())
@@ -141,8 +176,12 @@ class LGAG(nn.Module):
         _init_weights(self)
 
     def _build(self, eng, g, x):
-        g1 = eng.pairconv_bn(g, self.W_g[0], self.W_g[1])
-        t = eng.pairconv_bn(x, self.W_x[0], self.W_x[1], relu=True, residual=g1)             # relu(g1 + x1)
+        if self.kernel_size == 1:           # dense biased 1x1 convs
+            g1 = eng.conv_bn_act(g, self.W_g[0], self.W_g[1], bias=self.W_g[0].bias)
+            t = eng.conv_bn_act(x, self.W_x[0], self.W_x[1], bias=self.W_x[0].bias, relu=True, residual=g1)
+        else:
+            g1 = eng.pairconv_bn(g, self.W_g[0], self.W_g[1])
+            t = eng.pairconv_bn(x, self.W_x[0], self.W_x[1], relu=True, residual=g1)             # relu(g1 + x1)
         pre = eng.conv_bn_act(t, self.psi[0], self.psi[1], bias=self.psi[0].bias, out_map=(1, 8), y_dt=F32, y_C=1)
         return eng.sigmoid_gate(x, pre, 1)
 

@@ -248,6 +248,9 @@ SIGNATURES = {
     "pn2_upsample_nearest2x": [I, P, P, I, I, I, I, P],
     "pn2_upsample_nearest2x_bwd": [I, P, P, I, I, I, I, I, P],
     "pn2_gather_sum": [I, P, P, P, P, P, LL, I, P],
+    "pn2_msdc_combine_tile": [I, I, I],
+    "pn2_msdc_combine": [I, I, I, P, P, P, P, P, LL, I, I, P],
+    "pn2_msdc_combine_bwd": [I, I, P, P, P, P, P, I, I, I, I, LL, I, I, P],
     "pn2_sigmoid": [I, P, I, I, P, LL, P],
     "pn2_sigmoid_bwd": [I, P, P, P, I, I, LL, I, P],
     "pn2_mutation_loss_blocks": [LL],
@@ -298,7 +301,7 @@ _VALUE_FUNCS = {"pn2_copy_job_blocks", "pn2_conv_gemm_tile", "pn2_conv_gemm_job_
                 "pn2_bn_bwd_apply_job_blocks", "pn2_bn_bwd_reduce_job_blocks", "pn2_dwconv3x3_colsum_blocks", "pn2_resize_ksize", "pn2_colsum_job_blocks", "pn2_colsum_finalize_blocks", "pn2_dwconv3x3_wgrad_blocks", "pn2_conv_tile_n", "pn2_wgrad_tile_co", "pn2_conv_stat_blocks", "pn2_conv_tile_m", "pn2_bn_bwd_blocks", "pn2_loss_blocks",
                 "pn2_pack_blocks", "pn2_wgrad_reduce_blocks", "pn2_conv_wgrad_variant", "pn2_conv_wgrad_blocks",
                 "pn2_dsra_tail_blocks", "pn2_dsra_tail_scratch", "pn2_dsra_tail_fused_ok", "pn2_dsra_tail_fused_scratch", "pn2_ln_slots", "pn2_rows_blocks", "pn2_colsum_unit", "pn2_attn_bwd_blocks", "pn2_attn_long_bwd_blocks", "pn2_mutation_loss_blocks", "pn2_mutation_loss_width", "pn2_dual_loss_width", "pn2_seg_loss_width",
-                "pn2_dwconv_blocks", "pn2_pairconv_blocks", "pn2_gate_blocks", "pn2_eval_wfm_blocks", "pn2_seg_surface_hist_len"}
+                "pn2_dwconv_blocks", "pn2_pairconv_blocks", "pn2_msdc_combine_tile", "pn2_gate_blocks", "pn2_eval_wfm_blocks", "pn2_seg_surface_hist_len"}
 
 _lib = None
 WORK = {}     # profiling annotation for the next launch (algorithmic flops / tag), consumed by pn2.profile.Recorder

@@ -288,32 +288,71 @@ class EncoderOps:
         self.record(bwd)
         return y
 
-    def shuffled_sum(self, parts, groups):
-        """channel_shuffle(sum(parts), groups)  (MSCB.forward decoders.py:147-154, channel_shuffle :69-77) in one pass; the backward is one gather whose
-        result is the gradient of every part."""
+    def shuffled_sum(self, parts, groups, shared_grad=True):
+        """channel_shuffle(sum(parts), groups)  (MSCB.forward decoders.py:147-154, channel_shuffle :69-77) in one pass.  Up to three parts go through
+        pn2_gather_sum, four through pn2_msdc_combine.  shared_grad: every part has this op as its ONLY consumer - the backward is then one gather whose
+        result is the gradient of every part; otherwise (sequential MSDC: a branch output also feeds the next branch's input) the shuffled gradient is
+        accumulated into each part's own gradient."""
         a = parts[0]
         Cc, M = a.C, a.M
-        assert all(p.C == Cc and p.Cp == Cc and p.ld == Cc for p in parts) and 1 <= len(parts) <= 3 and Cc % groups == 0
+        assert all(p.C == Cc and p.Cp == Cc and p.ld == Cc for p in parts) and 1 <= len(parts) <= 4 and Cc % groups == 0
         cpg = Cc // groups
-        key = ("perm", Cc, groups)
-        if key not in _PERMS:
-            fwd = torch.tensor([(j % groups) * cpg + j // groups for j in range(Cc)], dtype=torch.int32)
-            inv = torch.empty_like(fwd); inv[fwd.long()] = torch.arange(Cc, dtype=torch.int32)
-            _PERMS[key] = (fwd.to(self.dev), inv.to(self.dev))
-        fwd, inv = _PERMS[key]
         y = Act(self, self.empty(a.N, a.H, a.W, Cc), Cc, Cc, Cc, self.dt)
-        ps = [p.ptr for p in parts] + [C.c_void_p(0)] * (3 - len(parts))
-        call.pn2_gather_sum(self.dt, ps[0], ps[1], ps[2], _p(fwd), y.ptr, M, Cc, _stream())
+        ps = [p.ptr for p in parts] + [C.c_void_p(0)] * (4 - len(parts))
+        fwd = inv = None
+        if len(parts) <= 3:
+            key = ("perm", Cc, groups)
+            if key not in _PERMS:
+                fwd = torch.tensor([(j % groups) * cpg + j // groups for j in range(Cc)], dtype=torch.int32)
+                inv = torch.empty_like(fwd); inv[fwd.long()] = torch.arange(Cc, dtype=torch.int32)
+                _PERMS[key] = (fwd.to(self.dev), inv.to(self.dev))
+            fwd, inv = _PERMS[key]
+            call.pn2_gather_sum(self.dt, ps[0], ps[1], ps[2], _p(fwd), y.ptr, M, Cc, _stream())
+        else:
+            call.pn2_msdc_combine(self.dt, 0, len(parts), ps[0], ps[1], ps[2], ps[3], y.ptr, M, Cc, groups, _stream())
 
         def bwd():
             gy = y.grad_buf()
             assert y.grad_written and gy.stride(2) == Cc
+            null = C.c_void_p(0)
+            if not shared_grad:
+                for p in parts:         # d(part) += shuffle^-1(dy): the adjoint of the cat mode with one part
+                    gp, acc = p.grad_sink()
+                    assert gp.stride(2) == Cc
+                    call.pn2_msdc_combine_bwd(self.dt, 1, _p(gy), _p(gp), null, null, null, acc, 0, 0, 0, M, Cc, groups, _stream())
+                return
             g = self.empty(a.N, a.H, a.W, Cc)
-            call.pn2_gather_sum(self.dt, _p(gy), C.c_void_p(0), C.c_void_p(0), _p(inv), _p(g), M, Cc, _stream())
+            if inv is not None:
+                call.pn2_gather_sum(self.dt, _p(gy), null, null, _p(inv), _p(g), M, Cc, _stream())
+            else:               # the adjoint of the sum: the sum of one tensor through the inverse shuffle
+                call.pn2_msdc_combine(self.dt, 0, 1, _p(gy), null, null, null, _p(g), M, Cc, cpg, _stream())
             for p in parts:         # single-consumer BN outputs: the shared tensor is only read
                 assert not p.grad_written
                 p.grad = g
                 p.grad_written = True
+        self.record(bwd)
+        return y
+
+    def shuffled_cat(self, parts, groups):
+        """channel_shuffle(torch.cat(parts, 1), groups)  (MSCB.forward with add=False, decoders.py:155-156) in one pass; the backward un-shuffles the
+        gradient into every part's own gradient (accumulating where the part has another consumer)."""
+        a = parts[0]
+        Cc, M, n = a.C, a.M, len(parts)
+        Cw = n * Cc
+        assert all(p.C == Cc and p.Cp == Cc and p.ld == Cc and p.M == M for p in parts) and 1 <= n <= 4 and Cw % groups == 0
+        y = Act(self, self.empty(a.N, a.H, a.W, Cw), Cw, Cw, Cw, self.dt)
+        null = C.c_void_p(0)
+        ps = [p.ptr for p in parts] + [null] * (4 - n)
+        call.pn2_msdc_combine(self.dt, 1, n, ps[0], ps[1], ps[2], ps[3], y.ptr, M, Cc, groups, _stream())
+
+        def bwd():
+            gy = y.grad_buf()
+            assert y.grad_written and gy.stride(2) == Cw
+            sinks = [p.grad_sink() for p in parts]
+            assert all(g.stride(2) == Cc for g, _ in sinks)
+            gs = [_p(g) for g, _ in sinks] + [null] * (4 - n)
+            acc = [k for _, k in sinks] + [0] * (4 - n)
+            call.pn2_msdc_combine_bwd(self.dt, n, _p(gy), gs[0], gs[1], gs[2], gs[3], acc[0], acc[1], acc[2], acc[3], M, Cc, groups, _stream())
         self.record(bwd)
         return y
 

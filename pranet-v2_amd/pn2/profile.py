@@ -111,6 +111,10 @@ def _shape(name, a):
             return f"nblk{a[1]} C{a[2]}"
         if name == "pn2_gather_sum":
             return f"n{a[6]} k{a[7]}"
+        if name == "pn2_msdc_combine":
+            return f"mode{a[1]} parts{a[2]} n{a[8]} k{a[9]} g{a[10]}"
+        if name == "pn2_msdc_combine_bwd":
+            return f"parts{a[1]} n{a[11]} k{a[12]} g{a[13]}"
         if name in ("pn2_upsample_nearest2x", "pn2_upsample_nearest2x_bwd"):
             return f"{a[3]}x{a[4]}x{a[5]}x{a[6]}"
     except Exception:
