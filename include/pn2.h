@@ -589,6 +589,32 @@ int pn2_eval_region_sums(const unsigned char* pred_u8, const float* gt, int H, i
 int pn2_eval_wfm_blocks(int H, int W);
 int pn2_eval_wfm(const unsigned char* pred_u8, const float* gt, int H, int W, const double* K49, double c5, int* work_i, double* work_d, double* part, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- ragged-batch test tail and metrics (csrc/pn2_eval.hip)
+ * test_with_eval (MyTest_med.py:15-46) for a batch of images whose ground truths all differ in size (pn2/evaltail.py, pn2.infer.Predictor.test_with_eval).
+ * One DEVICE table describes the batch: row b = { H, W of image b's ground truth; off = its first pixel in the packed buffers (images back to back, so offsets
+ * are aligned to nothing); rh, rw = the double quotients h / H, w / W rounded once to fp32, as pn2_bilinear_fwd receives them }.  A row with H == 0 is an empty
+ * slot (the filler of a short last batch): skipped, none of its bytes read or written.  maxH, maxW >= every row's H, W size the grids and `total` (pixels of the
+ * packed buffers) bounds them; a row that exceeds them is skipped like an empty slot.  Packed buffers: predictions u8 [total], ground truths fp32 [total]
+ * (binarised with > 0.5f as everywhere).  Every entry validates its arguments first and launches nothing when it returns non-zero (-1: null pointer / empty
+ * size, -2: outside the built range: B > 65535, maxW * 4 bytes above the 60 KB of LDS of the feature transform's row pass, nmaps other than 1 or 4).
+ * pn2_eval_tail_batch: `maps` is a HOST array of nmaps (1 or 4) device pointers to dense fp32 maps [B][h][w] (the model's K = 1 outputs).  Per image:
+ *   m0 or ((m0 + m1) + m2) + m3 -> bilinear resize (align_corners = 0) to H x W -> sigmoid -> min / max over the image -> (s - mn) / (mx - mn + 1e-8f) * 255
+ *   truncated to a byte at out[off ..].  The resized map is never stored: pass 1 reduces min and max (integer atomics on an order-preserving code: exact under
+ *   any order), pass 2 recomputes every value.  Bit for bit pn2_binary(add) x3 -> pn2_bilinear_fwd -> pn2_eval_tail of each image (one set of inlined
+ *   expressions, csrc/pn2_evalcore.h).  minmax: scratch [B][2] unsigned.
+ * pn2_eval_counts_batch: hist [B][512] = pn2_eval_hist of every image; out25 [B][25] = pn2_eval_region_sums of every image (NULL: not computed).  Integer
+ *   atomics only: exact.  Two launches (one without out25).
+ * pn2_eval_wfm_batch: pn2_eval_wfm of every image in three launches.  work_i: total ints, work_d: 2 * total doubles, part [B][PN2_EVAL_WFM_MAX_BLOCKS][2]: image b
+ *   fills its first pn2_eval_wfm_blocks(H, W) rows with the per-image entry's block sums (same blocks, same order: the same bits). */
+#define PN2_EVAL_WFM_MAX_BLOCKS 2048
+typedef struct { int H, W; long long off; float rh, rw; } pn2_eval_img;   /* 24 bytes */
+int pn2_eval_tail_batch(const float* const* maps, int nmaps, int B, int h, int w, const pn2_eval_img* table_dev, int maxH, int maxW, long long total,
+                        unsigned char* out, unsigned* minmax, void* stream);
+int pn2_eval_counts_batch(const unsigned char* pred_u8, const float* gt, const pn2_eval_img* table_dev, int B, int maxH, int maxW, long long total,
+                          unsigned* hist, unsigned long long* out25, void* stream);
+int pn2_eval_wfm_batch(const unsigned char* pred_u8, const float* gt, const pn2_eval_img* table_dev, int B, int maxH, int maxW, long long total,
+                       const double* K49, double c5, int* work_i, double* work_d, double* part, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- multi-class volume evaluation (csrc/pn2_seg.hip)
  * test_single_volume / val_single_volume of multiclass_seg/EMCAD/utils/utils.py:140-301 (pn2/voleval.py).  Every entry validates its arguments first and launches
  * nothing when it returns non-zero (-1: null pointer / empty size, -2: outside the built range).

@@ -10,6 +10,7 @@
 //   F.interpolate(scale_factor,bilinear)         pranet.py:349-354,370-376,392-398,414-415
 //   torch.split/cat, `sp + spx[i]`, `a * b`      Res2Net_v1b.py:65-80 ; pranet.py:111-119
 #include "pn2_common.h"
+#include "pn2_evalcore.h"
 #include "../../include/pn2.h"
 
 namespace {
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_k(const T* __restrict__ x, i
         VL<T, W>::load(b + (size_t)(y0 * Wd + x0) * ld_x, a); VL<T, W>::load(b + (size_t)(y0 * Wd + x1) * ld_x, bq);
         VL<T, W>::load(b + (size_t)(y1 * Wd + x0) * ld_x, c); VL<T, W>::load(b + (size_t)(y1 * Wd + x1) * ld_x, d);
 #pragma unroll
-        for (int e = 0; e < W; ++e) o[e] = ly0 * (lx0 * a[e] + lx1 * bq[e]) + ly1 * (lx0 * c[e] + lx1 * d[e]);
+        for (int e = 0; e < W; ++e) o[e] = bl_tap4(ly0, ly1, lx0, lx1, a[e], bq[e], c[e], d[e]);
         VL<T, W>::store(y + ((size_t)(n * OH + oy) * OW + ox) * ld_y + cv * W, o);
     }
 }

@@ -9,6 +9,7 @@
 //   clip + Adam      /root/reference/binary_seg/utils/utils.py:7-17 ; MyTrain_med.py:85-86,149
 //   eval tail        /root/reference/binary_seg/MyTest_med.py:104-111
 #include "pn2_common.h"
+#include "pn2_evalcore.h"
 #include "../../include/pn2.h"
 
 namespace {
@@ -1220,14 +1221,9 @@ __global__ __launch_bounds__(256) void eval_hist_k(const unsigned char* __restri
     __shared__ unsigned h[512];
     h[threadIdx.x] = 0; h[threadIdx.x + 256] = 0;
     __syncthreads();
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const unsigned v = pred[i];
-        atomicAdd(&h[v], 1u);
-        if (gt[i] > 0.5f) atomicAdd(&h[256 + v], 1u);
-    }
+    eval_hist_accum(pred, gt, n, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, h);
     __syncthreads();
-    if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
-    if (h[threadIdx.x + 256]) atomicAdd(&hist[threadIdx.x + 256], h[threadIdx.x + 256]);
+    eval_hist_flush(h, hist);
 }
 
 // ------------------------------------------------------------------------------------------ eval tail
@@ -1235,7 +1231,7 @@ __global__ __launch_bounds__(256) void minmax_k(const float* __restrict__ x, lon
     __shared__ float smn[4], smx[4];
     float mn = INFINITY, mx = -INFINITY;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float s = 1.f / (1.f + expf(-x[i])); mn = fminf(mn, s); mx = fmaxf(mx, s);
+        const float s = eval_sigmoid(x[i]); mn = fminf(mn, s); mx = fmaxf(mx, s);
     }
     for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
     if ((threadIdx.x & 63) == 0) { smn[threadIdx.x >> 6] = mn; smx[threadIdx.x >> 6] = mx; }
@@ -1255,8 +1251,7 @@ __global__ void minmax_final_k(float* part, int nb) {
 __global__ __launch_bounds__(256) void eval_u8_k(const float* __restrict__ x, unsigned char* __restrict__ out, const float* __restrict__ mm, long long n) {
     const float mn = mm[0], den = mm[1] - mm[0] + 1e-8f;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float s = 1.f / (1.f + expf(-x[i]));
-        out[i] = (unsigned char)(((s - mn) / den) * 255.f);
+        out[i] = eval_byte(eval_sigmoid(x[i]), mn, den);
     }
 }
 

@@ -281,6 +281,9 @@ SIGNATURES = {
     "pn2_eval_region_sums": [P, P, I, I, P, P],
     "pn2_eval_wfm_blocks": [I, I],
     "pn2_eval_wfm": [P, P, I, I, P, C.c_double, P, P, P, P],
+    "pn2_eval_tail_batch": [P, I, I, I, I, P, I, I, LL, P, P, P],
+    "pn2_eval_counts_batch": [P, P, P, I, I, I, LL, P, P, P],
+    "pn2_eval_wfm_batch": [P, P, P, I, I, I, LL, P, C.c_double, P, P, P, P],
     "pn2_seg_labels": [P, I, I, I, I, I, I, P, P],
     "pn2_seg_labels_up": [C.POINTER(SegUpMap), I, I, I, I, I, I, P, P],
     "pn2_seg_counts": [P, P, LL, I, P, P],

@@ -6,6 +6,7 @@ import ctypes as C
 
 import torch
 
+from . import evaltail
 from .capi import call, F32
 from .engine import Act, BnFoldCache, Engine, PackCache, StepArena, TUNER, _p, _stream
 from .graph import get_compute_dtype
@@ -15,7 +16,8 @@ from .voleval import MODES, predict_labels_up, volume_dice, volume_metrics
 
 class Predictor:
     """p = Predictor(model.eval()); outs = p(images)            # the model's output tuple, fp32 NCHW GPU tensors (valid until the next call)
-                                      u8 = p.postprocess(images, (H, W))   # MyTest_med.py:104-111 -> uint8 (H, W) map for one image"""
+                                      u8 = p.postprocess(images, (H, W))   # MyTest_med.py:104-111 -> uint8 (H, W) map for one image
+                                      res_i, mean = p.test_with_eval(loader, opt, batch_size=16)   # MyTest_med.py:26-45 for one data set, batched (ragged ground-truth sizes)"""
 
     def __init__(self, model, dtype=None):
         self.model = model
@@ -85,19 +87,74 @@ class Predictor:
         st["graph"].replay()
         return st["out"]
 
-    def postprocess(self, images, gt_shape):
-        """uint8 (H, W) prediction map of one image, as MyTest_med.py:104-111 writes it to disk."""
+    def postprocess(self, images, gt_shape, maps="sum4"):
+        """uint8 (H, W) prediction map of one image, as MyTest_med.py:104-111 writes it to disk.  maps="sum4": res2 + res3 + res4 + res5 (the V2 branch, :104-108);
+        maps="last": the last map of the model's tuple alone (the V1 branch's res2, :98-102)."""
         assert images.shape[0] == 1
+        if maps not in ("sum4", "last"):
+            raise ValueError(f"maps {maps!r}: 'sum4' or 'last'")
         outs = self(images)
         H, W = int(gt_shape[0]), int(gt_shape[1])
         eng = Engine(F32, False, need_grad=False)
-        maps = [eng.from_nchw(o, dt=F32) if o.shape[1] != 1 else Act(eng, o.reshape(o.shape[0], o.shape[2], o.shape[3], 1), 1, 1, 1, F32, requires_grad=False) for o in outs[:4]]
-        s_ = eng.add(eng.add(eng.add(maps[0], maps[1]), maps[2]), maps[3])              # res2 + res3 + res4 + res5 (MyTest_med.py:104)
+        src = outs[:4] if maps == "sum4" else outs[-1:]
+        maps = [eng.from_nchw(o, dt=F32) if o.shape[1] != 1 else Act(eng, o.reshape(o.shape[0], o.shape[2], o.shape[3], 1), 1, 1, 1, F32, requires_grad=False) for o in src]
+        s_ = eng.add(eng.add(eng.add(maps[0], maps[1]), maps[2]), maps[3]) if len(maps) == 4 else maps[0]              # res2 + res3 + res4 + res5 (MyTest_med.py:104)
         r = eng.resize_to(s_, H, W, align_corners=False)
         u8 = torch.empty((H, W), dtype=torch.uint8, device=images.device)
         scratch = torch.empty(2 + 2 * 512, dtype=torch.float32, device=images.device)
         call.pn2_eval_tail(r.ptr, _p(u8), _p(scratch), r.M, _stream())
         return u8
+
+    def postprocess_batch(self, images, gt_shapes, maps="sum4"):
+        """postprocess for a batch: images [B][3][S][S], gt_shapes up to B sizes (H, W), None = a filler slot.  One graph replay, then the two launches of
+        pn2_eval_tail_batch.  Returns (packed uint8 predictions, RaggedViews of (H, W) views, one per slot): pn2.evaltail.postprocess_batch."""
+        return evaltail.postprocess_batch(self(images), gt_shapes, maps)
+
+    def evaluate(self, images, gts, opt, maps="sum4"):
+        """The metric rows of one batch: images [B][3][S][S], gts up to B ground truths (H, W) on the GPU, already scaled to [0, 1] (None = a filler slot) ->
+        ndarray [len(gts) without fillers][len(opt["metrics"])], eval_for_testAllInOne of every image (pn2.evaltail.eval_batch)."""
+        gts = list(gts)
+        for g in gts:
+            if g is not None and not g.is_cuda:
+                raise RuntimeError("pn2.infer needs GPU tensors (no CPU fallback)")
+        packed, views = self.postprocess_batch(images, [None if g is None else tuple(g.shape[-2:]) for g in gts], maps)
+        return evaltail.eval_batch(opt, packed, views, gts + [None] * (images.shape[0] - len(gts)))
+
+    def test_with_eval(self, loader, opt, batch_size=16, maps="sum4"):
+        """MyTest_med.py:26-45 for one data set: loader yields (image [1][3][S][S], gt, name) as utils.dataloader.test_dataset.load_data does (gt: a PIL image,
+        an array or a tensor [H][W]); gt /= gt.max() + 1e-8 as :31-32.  Returns (res_i [n][len(opt["metrics"])], its column mean).  Images go through the graph of
+        ONE batch shape: the last batch is filled with zero images whose table slots are empty (eval-mode BatchNorm keeps the samples independent), so a
+        second pass over the set captures nothing."""
+        import numpy as np
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError("batch_size >= 1")
+        dev = next(self.model.parameters()).device
+        rows, imgs, gts = [], [], []
+
+        def flush():
+            x = torch.cat(imgs)
+            if len(imgs) < B:
+                x = torch.cat([x, x.new_zeros((B - len(imgs),) + tuple(x.shape[1:]))])
+            rows.append(self.evaluate(x, gts, opt, maps))
+            imgs.clear()
+            gts.clear()
+        for image, gt, _name in loader:
+            if isinstance(gt, torch.Tensor):
+                g = gt.to(dev).float().reshape(gt.shape[-2], gt.shape[-1])
+                g = g / (g.max() + 1e-8)
+            else:
+                g = np.asarray(gt, np.float32).copy()
+                g /= (g.max() + 1e-8)
+                g = torch.from_numpy(g).to(dev)
+            imgs.append(image.to(dev).float())
+            gts.append(g)
+            if len(imgs) == B:
+                flush()
+        if imgs:
+            flush()
+        res_i = np.concatenate(rows) if rows else np.zeros((0, len(opt["metrics"])))
+        return res_i, np.mean(res_i, axis=0)
 
 
 class VolumePredictor(Predictor):
