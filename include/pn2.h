@@ -656,6 +656,31 @@ int pn2_resize_u8_pass(const unsigned char* src, unsigned char* dst, int H, int 
                        const int* xmin_dev, const int* count_dev, const int* kk_dev, int ksize, void* stream);
 int pn2_u8_to_tensor(const unsigned char* src, float* dst_chw, int H, int W, int C, const float* mean_dev, const float* std_dev, void* stream);
 
+/* The same transform for a ragged batch of n slots - images [H][W][3] and masks [H][W][1] of any sizes together - in TWO launches whatever n is
+ * (pn2/input.py: DeviceTransform.batch).  One table describes the batch, row i = {
+ *   H, W, C        the slot's uint8 source [H][W][C], C = 1 or 3; H == 0 is an empty slot: skipped, its destination is left untouched
+ *   dst, norm      the sample it fills in out_rgb [n_rgb][3][S][S] (C == 3) or out_mask [n_mask][1][S][S] (C == 1); whether Normalize applies
+ *   kw, kh         pn2_resize_ksize(W, S), pn2_resize_ksize(H, S) (unused where that pass is a copy)
+ *   blk            the first block of the slot in the width pass: the running sum of pn2_input_batch_blocks(H, S) over the rows before it
+ *   src, tmp       byte offsets of the source in the packed source arena and of the intermediate [H][S][C] image in the scratch arena
+ *   tap_w, tap_h   int32 offsets, in the tap arena, of the slot's width-axis and height-axis tap blocks.  A tap block of an axis of length L is
+ *                  xmin[S] | count[S] | kk[S][pn2_resize_ksize(L, S)] as pn2_resize_coeffs(L, S) returns them; slots of one size share a block }.
+ * The entries take the table twice: the HOST copy is validated before anything is launched and sizes the grid, the DEVICE copy is what the kernels read.
+ * pn2_input_batch_width: scratch[tmp ..] = the width pass of every slot (a copy where W == S, as Pillow skips that pass).
+ * pn2_input_batch_height: forms each byte of the height pass exactly as pn2_resize_u8_pass does (the scratch byte itself where H == S) and, without storing it,
+ *   applies pn2_u8_to_tensor's two fp32 operations: the bits of pn2_resize_u8_pass x2 -> pn2_u8_to_tensor (one set of inlined expressions, csrc/pn2_inputcore.h).
+ * Status: -1 null pointer, n < 0, out_size < 1 or a negative size; -2 outside the built range (C not 1 or 3, a slot or an output sample of 2^31 bytes or more);
+ * -3 a row that disagrees with the arenas (an offset outside them, kw / kh / blk not the values above, dst outside the outputs).  n == 0 succeeds and launches
+ * nothing.  Every check is made on the host, without a device. */
+#define PN2_INPUT_PX 4          /* adjacent output pixels of one row per thread, both passes */
+typedef struct { int H, W, C, dst, norm, kw, kh, blk; long long src, tmp, tap_w, tap_h; } pn2_input_slot;   /* 64 bytes */
+int pn2_input_batch_blocks(int rows, int out_size);          /* value: 256-thread blocks of rows x out_size output pixels; -1 for a negative size */
+int pn2_input_batch_width(const pn2_input_slot* table_host, const pn2_input_slot* table_dev, int n, int out_size, const unsigned char* src, long long src_bytes,
+                          unsigned char* tmp, long long tmp_bytes, const int* taps, long long tap_ints, void* stream);
+int pn2_input_batch_height(const pn2_input_slot* table_host, const pn2_input_slot* table_dev, int n, int out_size, const unsigned char* tmp, long long tmp_bytes,
+                           const int* taps, long long tap_ints, float* out_rgb, int n_rgb, float* out_mask, int n_mask, const float* mean_dev, const float* std_dev,
+                           void* stream);
+
 /* ---------------------------------------------------------------------------------------------- Synapse slice transform
  * multiclass_seg/EMCAD/utils/dataset_synapse.py:12-47 (RandomGenerator) and utils/utils.py:179-181,197-198 (test_single_volume) on device [N][H][W] batches,
  * bit for bit with scipy.ndimage at its defaults (mode='constant', cval=0, prefilter=True, grid_mode=False).  Every axis <= 1024 (-2 beyond).

@@ -6,11 +6,10 @@
 #include <cmath>
 #include <cstdint>
 #include "pn2_common.h"
+#include "pn2_inputcore.h"
 #include "../../include/pn2.h"
 
 namespace {
-
-constexpr int RS_PREC = 32 - 8 - 2;
 
 // one separable pass: dst[o][i][c] = clip8((2^21 + sum_x src[..][xmin[o] + x][..] * kk[o][x]) >> 22) along `axis` (1: width, 0: height)
 __global__ __launch_bounds__(256) void resize_pass_k(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int H, int W, int C, int out_size, int axis,
@@ -20,13 +19,10 @@ __global__ __launch_bounds__(256) void resize_pass_k(const unsigned char* __rest
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int c = (int)(i % C), ox = (int)((i / C) % OW), oy = (int)(i / ((size_t)C * OW));
         const int o = axis == 1 ? ox : oy;
-        const int x0 = xmin[o], n = cnt[o];
-        const int* k = kk + (size_t)o * ksize;
-        int acc = 1 << (RS_PREC - 1);
-        if (axis == 1) { const unsigned char* s = src + ((size_t)oy * W + x0) * C + c; for (int x = 0; x < n; ++x) acc += (int)s[(size_t)x * C] * k[x]; }
-        else { const unsigned char* s = src + ((size_t)x0 * W + ox) * C + c; for (int x = 0; x < n; ++x) acc += (int)s[(size_t)x * W * C] * k[x]; }
-        acc >>= RS_PREC;
-        dst[i] = (unsigned char)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
+        const int x0 = xmin[o];
+        int acc[1];
+        rs_tap_sum<1, false>(acc, axis == 1 ? src + ((size_t)oy * W + x0) * C + c : src + ((size_t)x0 * W + ox) * C + c, axis == 1 ? C : W * C, kk + (size_t)o * ksize, cnt[o]);
+        dst[i] = rs_byte(acc[0]);
     }
 }
 
@@ -34,15 +30,186 @@ __global__ __launch_bounds__(256) void resize_pass_k(const unsigned char* __rest
 __global__ __launch_bounds__(256) void to_tensor_k(const unsigned char* __restrict__ src, float* __restrict__ dst, int H, int W, int C, const float* __restrict__ mean,
                                                    const float* __restrict__ std) {
     const size_t total = (size_t)H * W * C;
+    const bool norm = mean != nullptr;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int x = (int)(i % W), y = (int)((i / W) % H), c = (int)(i / ((size_t)W * H));
-        float t = (float)src[((size_t)y * W + x) * C + c] / 255.0f;
-        if (mean) t = (t - mean[c]) / std[c];
-        dst[i] = t;
+        dst[i] = u8_to_tensor(src[((size_t)y * W + x) * C + c], norm, norm ? mean[c] : 0.f, norm ? std[c] : 1.f);
     }
 }
 
 inline unsigned grid_of(size_t total) { const size_t g = (total + 255) / 256; return (unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
+
+// ------------------------------------------------------------------------------------------------ ragged batch
+// Both passes give a thread PN2_INPUT_PX adjacent output pixels of one row (4 or 12 bytes); the index arithmetic inside a slot is 32-bit (the entries refuse a
+// slot of 2^31 bytes).  `wide`: out_size is a multiple of 4 and every base is aligned, so a thread's run of the [.][S][C] scratch image starts on a dword.
+constexpr int PX = PN2_INPUT_PX;
+
+// width pass of one slot: src [H][W][C] -> tmp [H][S][C]; a copy where W == S (Pillow skips that pass)
+template <int C>
+__device__ __forceinline__ void width_slot(const pn2_input_slot& r, int local, int S, const unsigned char* __restrict__ src, unsigned char* __restrict__ tmp,
+                                           const int* __restrict__ taps, bool wide) {
+    const int G = (S + PX - 1) / PX;
+    if (local >= r.H * G) return;
+    const int y = local / G, px0 = (local - y * G) * PX;
+    const unsigned char* srow = src + r.src + y * r.W * C;
+    unsigned char b[PX * C];
+    if (r.W == S) {
+#pragma unroll
+        for (int p = 0; p < PX; ++p)
+            if (px0 + p < S) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) b[p * C + c] = srow[(px0 + p) * C + c];
+            }
+    } else {
+        const int* xmin = taps + r.tap_w;
+        const int* cnt = xmin + S;
+        const int* kk = cnt + S;
+#pragma unroll
+        for (int p = 0; p < PX; ++p)
+            if (px0 + p < S) {
+                const int ox = px0 + p;          // xmin / count: read once per output column
+                int acc[C];
+                rs_tap_sum<C, false>(acc, srow + xmin[ox] * C, C, kk + ox * r.kw, cnt[ox]);
+#pragma unroll
+                for (int c = 0; c < C; ++c) b[p * C + c] = rs_byte(acc[c]);
+            }
+    }
+    unsigned char* d = tmp + r.tmp + (y * S + px0) * C;
+    if (wide) {
+#pragma unroll
+        for (int w = 0; w < C; ++w)
+            reinterpret_cast<unsigned*>(d)[w] = (unsigned)b[4 * w] | ((unsigned)b[4 * w + 1] << 8) | ((unsigned)b[4 * w + 2] << 16) | ((unsigned)b[4 * w + 3] << 24);
+    } else {
+#pragma unroll
+        for (int p = 0; p < PX; ++p)
+            if (px0 + p < S) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) d[p * C + c] = b[p * C + c];
+            }
+    }
+}
+
+__global__ __launch_bounds__(256) void input_batch_width_k(const pn2_input_slot* __restrict__ table, int n, int S, const unsigned char* __restrict__ src,
+                                                           unsigned char* __restrict__ tmp, const int* __restrict__ taps, int wide) {
+    // the slot of this block: the last one whose first block is <= blockIdx.x (empty slots own no block and share the next slot's prefix)
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].blk <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const pn2_input_slot r = table[lo];
+    if (r.H <= 0) return;
+    const int local = ((int)blockIdx.x - r.blk) * 256 + (int)threadIdx.x;
+    if (r.C == 3) width_slot<3>(r, local, S, src, tmp, taps, wide != 0);
+    else width_slot<1>(r, local, S, src, tmp, taps, wide != 0);
+}
+
+// height pass of one slot fused with ToTensor / Normalize: tmp [H][S][C] -> out [C][S][S] fp32; the byte of resize_pass_k is formed and never stored
+template <int C, bool WIDE>
+__device__ __forceinline__ void height_slot(const pn2_input_slot& r, int local, int S, const unsigned char* __restrict__ tmp, const int* __restrict__ taps,
+                                            float* __restrict__ out, const float* __restrict__ mean, const float* __restrict__ std) {
+    const int G = (S + PX - 1) / PX;
+    if (local >= S * G) return;
+    const int oy = local / G, px0 = (local - oy * G) * PX;
+    const int pitch = S * C;
+    const unsigned char* t = tmp + r.tmp + px0 * C;
+    unsigned char b[PX * C];
+    if (r.H == S) {
+        t += oy * pitch;
+        if constexpr (WIDE) {
+#pragma unroll
+            for (int w = 0; w < C; ++w) {
+                const unsigned v = reinterpret_cast<const unsigned*>(t)[w];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) b[4 * w + j] = (unsigned char)((v >> (8 * j)) & 255u);
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < PX; ++p)
+                if (px0 + p < S) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) b[p * C + c] = t[p * C + c];
+                }
+        }
+    } else {
+        const int* xmin = taps + r.tap_h;
+        const int* cnt = xmin + S;
+        const int* k = cnt + S + oy * r.kh;
+        const int n = cnt[oy];
+        t += xmin[oy] * pitch;
+        if constexpr (WIDE) {
+            int acc[PX * C];
+            rs_tap_sum<PX * C, true>(acc, t, pitch, k, n);
+#pragma unroll
+            for (int i = 0; i < PX * C; ++i) b[i] = rs_byte(acc[i]);
+        } else {
+#pragma unroll
+            for (int p = 0; p < PX; ++p)
+                if (px0 + p < S) {
+                    int acc[C];
+                    rs_tap_sum<C, false>(acc, t + p * C, pitch, k, n);
+#pragma unroll
+                    for (int c = 0; c < C; ++c) b[p * C + c] = rs_byte(acc[c]);
+                }
+        }
+    }
+    const bool norm = r.norm != 0;
+    float* o = out + (size_t)r.dst * C * S * S + oy * S + px0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float m = norm ? mean[c] : 0.f, s = norm ? std[c] : 1.f;
+        if constexpr (WIDE) {
+            *reinterpret_cast<float4*>(o + c * S * S) = make_float4(u8_to_tensor(b[c], norm, m, s), u8_to_tensor(b[C + c], norm, m, s), u8_to_tensor(b[2 * C + c], norm, m, s),
+                                                                   u8_to_tensor(b[3 * C + c], norm, m, s));
+        } else {
+#pragma unroll
+            for (int p = 0; p < PX; ++p)
+                if (px0 + p < S) o[c * S * S + p] = u8_to_tensor(b[p * C + c], norm, m, s);
+        }
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void input_batch_height_k(const pn2_input_slot* __restrict__ table, int S, int bps, const unsigned char* __restrict__ tmp,
+                                                            const int* __restrict__ taps, float* __restrict__ out_rgb, float* __restrict__ out_mask,
+                                                            const float* __restrict__ mean, const float* __restrict__ std) {
+    const int slot = (int)blockIdx.x / bps;          // every slot has the same S x S outputs: bps blocks each
+    const pn2_input_slot r = table[slot];
+    if (r.H <= 0) return;
+    const int local = ((int)blockIdx.x - slot * bps) * 256 + (int)threadIdx.x;
+    if (r.C == 3) height_slot<3, WIDE>(r, local, S, tmp, taps, out_rgb, mean, std);
+    else height_slot<1, WIDE>(r, local, S, tmp, taps, out_mask, mean, std);
+}
+
+inline long long slot_blocks(int rows, int S) { return ((long long)rows * ((S + PX - 1) / PX) + 255) / 256; }
+
+// HOST check of a batch's table, before anything is launched.  Sizes < 0: that arena is not used by the calling pass and its offsets are not checked.
+int check_table(const pn2_input_slot* t, int n, int S, long long src_bytes, long long tmp_bytes, long long tap_ints, int n_rgb, int n_mask, bool outputs,
+                long long* width_blocks, bool* aligned4) {
+    if ((long long)S * S * 3 > INT_MAX) return -2;
+    long long blk = 0;
+    *aligned4 = true;
+    for (int i = 0; i < n; ++i) {
+        const pn2_input_slot& r = t[i];
+        if (r.H < 0 || (r.H > 0 && r.W < 1)) return -1;
+        if (r.blk != blk) return -3;
+        if (r.H == 0) continue;
+        if (r.C != 1 && r.C != 3) return -2;
+        const long long nsrc = (long long)r.H * r.W * r.C, ntmp = (long long)r.H * S * r.C;
+        if (nsrc > INT_MAX || ntmp > INT_MAX) return -2;
+        if (src_bytes >= 0 && (r.src < 0 || r.src > src_bytes - nsrc)) return -3;
+        if (r.tmp < 0 || r.tmp > tmp_bytes - ntmp) return -3;
+        if (r.tmp & 3) *aligned4 = false;
+        const long long blkw = 2LL * S + (long long)S * r.kw, blkh = 2LL * S + (long long)S * r.kh;
+        if (src_bytes >= 0 && r.W != S && (r.kw != pn2_resize_ksize(r.W, S) || r.tap_w < 0 || r.tap_w > tap_ints - blkw)) return -3;
+        if (outputs && r.H != S && (r.kh != pn2_resize_ksize(r.H, S) || r.tap_h < 0 || r.tap_h > tap_ints - blkh)) return -3;
+        if (outputs && (r.dst < 0 || r.dst >= (r.C == 3 ? n_rgb : n_mask))) return -3;
+        blk += slot_blocks(r.H, S);
+        if (blk > INT_MAX) return -2;
+    }
+    *width_blocks = blk;
+    return 0;
+}
 
 }  // namespace
 
@@ -100,6 +267,54 @@ int pn2_resize_u8_pass(const unsigned char* src, unsigned char* dst, int H, int 
 int pn2_u8_to_tensor(const unsigned char* src, float* dst, int H, int W, int C, const float* mean_dev, const float* std_dev, void* stream) {
     if (!src || !dst || H < 1 || W < 1 || C < 1 || ((mean_dev == nullptr) != (std_dev == nullptr))) return -1;
     hipLaunchKernelGGL(to_tensor_k, dim3(grid_of((size_t)H * W * C)), dim3(256), 0, (hipStream_t)stream, src, dst, H, W, C, mean_dev, std_dev);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+int pn2_input_batch_blocks(int rows, int out_size) {
+    if (rows < 0 || out_size < 1) return -1;
+    const long long b = slot_blocks(rows, out_size);
+    return b > INT_MAX ? -1 : (int)b;
+}
+
+/* width pass of a ragged batch: ONE launch, src arena -> scratch arena [H][S][C] per slot */
+int pn2_input_batch_width(const pn2_input_slot* table_host, const pn2_input_slot* table_dev, int n, int out_size, const unsigned char* src, long long src_bytes,
+                          unsigned char* tmp, long long tmp_bytes, const int* taps, long long tap_ints, void* stream) {
+    if (!table_host || !table_dev || !src || !tmp || !taps || n < 0 || out_size < 1 || src_bytes < 0 || tmp_bytes < 0 || tap_ints < 0) return -1;
+    if (n == 0) return 0;
+    long long blocks = 0;
+    bool aligned4 = false;
+    const int rc = check_table(table_host, n, out_size, src_bytes, tmp_bytes, tap_ints, 0, 0, false, &blocks, &aligned4);
+    if (rc) return rc;
+    if (blocks == 0) return 0;          // every slot is empty
+    const int wide = out_size % 4 == 0 && aligned4 && ((uintptr_t)tmp & 3) == 0;
+    hipLaunchKernelGGL(input_batch_width_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n, out_size, src, tmp, taps, wide);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+/* height pass + ToTensor + Normalize of a ragged batch: ONE launch, scratch arena -> out_rgb [n_rgb][3][S][S] / out_mask [n_mask][1][S][S] fp32 */
+int pn2_input_batch_height(const pn2_input_slot* table_host, const pn2_input_slot* table_dev, int n, int out_size, const unsigned char* tmp, long long tmp_bytes,
+                           const int* taps, long long tap_ints, float* out_rgb, int n_rgb, float* out_mask, int n_mask, const float* mean_dev, const float* std_dev,
+                           void* stream) {
+    if (!table_host || !table_dev || !tmp || !taps || !mean_dev || !std_dev || n < 0 || out_size < 1 || tmp_bytes < 0 || tap_ints < 0 || n_rgb < 0 || n_mask < 0 ||
+        (n_rgb > 0 && !out_rgb) || (n_mask > 0 && !out_mask))
+        return -1;
+    if (n == 0) return 0;
+    long long blocks = 0;
+    bool aligned4 = false;
+    const int rc = check_table(table_host, n, out_size, -1, tmp_bytes, tap_ints, n_rgb, n_mask, true, &blocks, &aligned4);
+    if (rc) return rc;
+    if (blocks == 0) return 0;
+    const long long bps = slot_blocks(out_size, out_size);
+    if (bps * n > INT_MAX) return -2;
+    const bool wide = out_size % 4 == 0 && aligned4 && ((uintptr_t)tmp & 3) == 0 && ((uintptr_t)out_rgb & 15) == 0 && ((uintptr_t)out_mask & 15) == 0;
+    if (wide)
+        hipLaunchKernelGGL(input_batch_height_k<true>, dim3((unsigned)(bps * n)), dim3(256), 0, (hipStream_t)stream, table_dev, out_size, (int)bps, tmp, taps, out_rgb, out_mask,
+                           mean_dev, std_dev);
+    else
+        hipLaunchKernelGGL(input_batch_height_k<false>, dim3((unsigned)(bps * n)), dim3(256), 0, (hipStream_t)stream, table_dev, out_size, (int)bps, tmp, taps, out_rgb, out_mask,
+                           mean_dev, std_dev);
     PN2_CHECK_LAUNCH();
     return 0;
 }

@@ -124,7 +124,7 @@ class Predictor:
         """MyTest_med.py:26-45 for one data set: loader yields (image [1][3][S][S], gt, name) as utils.dataloader.test_dataset.load_data does (gt: a PIL image,
         an array or a tensor [H][W]); gt /= gt.max() + 1e-8 as :31-32.  Returns (res_i [n][len(opt["metrics"])], its column mean).  Images go through the graph of
         ONE batch shape: the last batch is filled with zero images whose table slots are empty (eval-mode BatchNorm keeps the samples independent), so a
-        second pass over the set captures nothing."""
+        second pass over the set captures nothing.  A loader with load_batch(k) (test_dataset) is asked for whole batches instead: one input transform per batch."""
         import numpy as np
         B = int(batch_size)
         if B < 1:
@@ -134,21 +134,31 @@ class Predictor:
 
         def flush():
             x = torch.cat(imgs)
-            if len(imgs) < B:
-                x = torch.cat([x, x.new_zeros((B - len(imgs),) + tuple(x.shape[1:]))])
+            if x.shape[0] < B:
+                x = torch.cat([x, x.new_zeros((B - x.shape[0],) + tuple(x.shape[1:]))])
             rows.append(self.evaluate(x, gts, opt, maps))
             imgs.clear()
             gts.clear()
-        for image, gt, _name in loader:
+
+        def scaled(gt):
             if isinstance(gt, torch.Tensor):
                 g = gt.to(dev).float().reshape(gt.shape[-2], gt.shape[-1])
-                g = g / (g.max() + 1e-8)
-            else:
-                g = np.asarray(gt, np.float32).copy()
-                g /= (g.max() + 1e-8)
-                g = torch.from_numpy(g).to(dev)
+                return g / (g.max() + 1e-8)
+            g = np.asarray(gt, np.float32).copy()
+            g /= (g.max() + 1e-8)
+            return torch.from_numpy(g).to(dev)
+        if hasattr(loader, "load_batch"):          # utils.dataloader.test_dataset: the rest of the set, a batch per transform call
+            while True:
+                images, batch_gts, _names = loader.load_batch(B)
+                if not batch_gts:
+                    break
+                imgs.append(images.to(dev).float())
+                gts.extend(scaled(gt) for gt in batch_gts)
+                flush()
+            loader = ()
+        for image, gt, _name in loader:
             imgs.append(image.to(dev).float())
-            gts.append(g)
+            gts.append(scaled(gt))
             if len(imgs) == B:
                 flush()
         if imgs:

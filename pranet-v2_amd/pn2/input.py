@@ -21,9 +21,94 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ------------------------------------------------------------------------------------------------ ragged batch: the host side, pure numpy
+# one row of the device table of the batch entries (pn2_input_slot, include/pn2.h)
+SLOT = np.dtype([("H", "<i4"), ("W", "<i4"), ("C", "<i4"), ("dst", "<i4"), ("norm", "<i4"), ("kw", "<i4"), ("kh", "<i4"), ("blk", "<i4"),
+                 ("src", "<i8"), ("tmp", "<i8"), ("tap_w", "<i8"), ("tap_h", "<i8")])
+PX = 4                 # PN2_INPUT_PX (include/pn2.h): adjacent output pixels per thread
+ALIGN = 16             # every slot of the source and scratch arenas starts on a multiple of this
+
+
+def _up(v, a):
+    return -(-int(v) // a) * a
+
+
+def slot_blocks(rows, S):
+    """pn2_input_batch_blocks: 256-thread blocks of rows x S output pixels, PX pixels per thread."""
+    return -(-(int(rows) * -(-int(S) // PX)) // 256)
+
+
+def tap_block(in_size, S):
+    """(block, ksize): the taps of one axis of length in_size resized to S, as the kernels read them - int32 xmin[S] | count[S] | kk[S][ksize], filled by
+    pn2_resize_coeffs (host code of the library: Pillow's coefficient arithmetic exists once)."""
+    ks = int(call.pn2_resize_ksize(int(in_size), int(S)))
+    if ks < 0:
+        raise ValueError(f"resize of an axis of {in_size} to {S}")
+    blk = np.zeros(2 * S + S * ks, np.int32)
+    call.pn2_resize_coeffs(int(in_size), int(S), C.c_void_p(blk.ctypes.data), C.c_void_p(blk[S:].ctypes.data), C.c_void_p(blk[2 * S:].ctypes.data))
+    return blk, ks
+
+
+class TapArena:
+    """Host copy of the growing tap arena of one output size: .blocks[in_size] = (int32 offset, ksize), .data[:.ints] the blocks back to back in the order they
+    were first asked for.  A size is computed once; get() of a known size changes nothing."""
+
+    def __init__(self, size):
+        self.size = int(size)
+        self.blocks = {}
+        self.data = np.zeros(0, np.int32)
+        self.ints = 0
+
+    def get(self, in_size):
+        hit = self.blocks.get(int(in_size))
+        if hit is None:
+            blk, ks = tap_block(in_size, self.size)
+            if self.ints + len(blk) > len(self.data):
+                grown = np.zeros(max(2 * len(self.data), self.ints + len(blk)), np.int32)
+                grown[:self.ints] = self.data[:self.ints]
+                self.data = grown
+            self.data[self.ints:self.ints + len(blk)] = blk
+            hit = self.blocks[int(in_size)] = (self.ints, ks)
+            self.ints += len(blk)
+        return hit
+
+
+def batch_table(shapes, S, taps, dst=None, norm=None, gap=0):
+    """The table of a ragged batch (pn2_input_slot rows, include/pn2.h) for sources of the shapes [(H, W, C) or None, ...] (None, or H == 0: an empty slot, which
+    takes no byte of either arena and no block).  Sources are packed in slot order, each on a multiple of ALIGN bytes, the [H][S][C] scratch images likewise;
+    gap: bytes left free before every slot and after the last in both arenas (tests put canaries there).  taps: the TapArena of S - sizes it has not seen are
+    added, slots of one size share a block; an axis that already has length S gets no block (that pass is a copy).  dst: the output sample of every slot
+    (default: images and masks each count from 0 in slot order); norm: whether Normalize applies (default: where C == 3).
+    Returns (rows, src_bytes, tmp_bytes): a numpy array of dtype SLOT and the sizes of the two arenas."""
+    S = int(S)
+    if taps.size != S:
+        raise ValueError(f"a tap arena for size {taps.size}, asked for {S}")
+    rows = np.zeros(len(shapes), dtype=SLOT)
+    src = tmp = int(gap)
+    blk = 0
+    seen = {1: 0, 3: 0}
+    for i, s in enumerate(shapes):
+        rows[i]["blk"] = blk
+        if s is None or int(s[0]) == 0:
+            continue
+        H, W, Cc = (int(v) for v in s)
+        if H < 0 or W < 1 or Cc not in (1, 3):
+            raise ValueError(f"slot {i}: a uint8 image [H][W][1 or 3], got {tuple(s)}")
+        src, tmp = _up(src, ALIGN), _up(tmp, ALIGN)
+        tw, kw = taps.get(W) if W != S else (0, 0)
+        th, kh = taps.get(H) if H != S else (0, 0)
+        rows[i] = (H, W, Cc, seen[Cc] if dst is None else int(dst[i]), int(Cc == 3) if norm is None else int(bool(norm[i])), kw, kh, blk, src, tmp, tw, th)
+        seen[Cc] += 1
+        src += H * W * Cc + int(gap)
+        tmp += H * S * Cc + int(gap)
+        blk += slot_blocks(H, S)
+    return rows, src, tmp
+
+
 class DeviceTransform:
     """t = DeviceTransform(352); x, gt = t(images_u8, masks_u8) with lists of uint8 tensors [H][W][3] / [H][W] (any sizes)
-    -> x fp32 [N][3][S][S] normalised, gt fp32 [N][1][S][S] in [0, 1]: the batch PolypDataset + DataLoader would collate."""
+    -> x fp32 [N][3][S][S] normalised, gt fp32 [N][1][S][S] in [0, 1]: the batch PolypDataset + DataLoader would collate.
+    t.batch(images_u8, masks_u8) gives the same tensors for the whole list in two launches and one host-to-device copy."""
 
     def __init__(self, size, mean=_MEAN, std=_STD, device=None):
         if not torch.cuda.is_available():
@@ -34,6 +119,95 @@ class DeviceTransform:
         self.mean = torch.tensor(mean, dtype=torch.float32, device=self.dev)
         self.std = torch.tensor(std, dtype=torch.float32, device=self.dev)
         self._coeffs = {}
+        # state of batch(): host tap arena and its device mirror, the reused buffers, and the event after which the pinned staging buffer may be rewritten
+        self.taps = TapArena(self.size)
+        self.tap_uploads = 0          # host-to-device copies of tap blocks so far (a batch without a new size makes none)
+        self._taps_dev, self._taps_up = None, 0
+        self._bufs = {}
+        self._staged = None
+
+    def _buf(self, name, nbytes, pinned=False):
+        t = self._bufs.get(name)
+        if t is None or t.numel() < nbytes:
+            nbytes = max(int(nbytes), 2 * t.numel() if t is not None else 256)
+            t = self._bufs[name] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) if pinned else torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        return t
+
+    def _sync_taps(self):
+        """the device mirror of self.taps: only the blocks added since the last call go up (all of them after the mirror had to grow)"""
+        a = self.taps
+        if self._taps_dev is None or self._taps_dev.numel() < a.ints:
+            self._taps_dev, self._taps_up = torch.empty(max(len(a.data), 1), dtype=torch.int32, device=self.dev), 0
+        if self._taps_up < a.ints:
+            self._taps_dev[self._taps_up:a.ints].copy_(torch.from_numpy(a.data[self._taps_up:a.ints]))
+            self._taps_up = a.ints
+            self.tap_uploads += 1
+        return self._taps_dev
+
+    def batch(self, images, masks=None, out=None):
+        """__call__ for the whole list at once: the same x (and g), bit for bit, from two kernel launches (pn2_input_batch_width / _height) whatever the list's
+        length.  images / masks: uint8 arrays [H][W][3] / [H][W] of any sizes - numpy arrays, CPU tensors or tensors on this device; None is an empty slot,
+        whose output sample is left as it was (out=(x, g) or out=x: tensors to fill instead of new ones).  Host inputs are packed behind the table in one pinned
+        staging buffer and go up in ONE copy; device inputs are gathered with device copies and only the table goes up.  Tap blocks are cached per input size
+        (self.taps), scratch is reused between calls; calls of one DeviceTransform belong on one stream."""
+        S, st = self.size, _stream()
+        n_img = len(images)
+        items = list(images) + (list(masks) if masks is not None else [])
+        arrs, shapes = [], []
+        for i, a in enumerate(items):
+            if a is not None:
+                if isinstance(a, torch.Tensor):
+                    if a.dtype != torch.uint8 or (a.is_cuda and a.device != self.dev):
+                        raise RuntimeError("DeviceTransform.batch needs uint8 arrays on the host or on its own device")
+                    a = (a[:, :, None] if a.dim() == 2 else a).contiguous()
+                    if not a.is_cuda:
+                        a = a.numpy()
+                else:
+                    a = np.asarray(a)
+                    if a.dtype != np.uint8:
+                        raise RuntimeError("DeviceTransform.batch needs uint8 arrays on the host or on its own device")
+                    a = np.ascontiguousarray(a[:, :, None] if a.ndim == 2 else a)
+                if len(a.shape) != 3 or a.shape[2] != (3 if i < n_img else 1):
+                    raise RuntimeError("images must be RGB (rgb_loader converts to 'RGB', dataloader.py:133-136)" if i < n_img else "masks must have one channel")
+            arrs.append(a)
+            shapes.append(None if a is None else tuple(a.shape))
+        x, g = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
+        if x is None:
+            x = torch.empty((n_img, 3, S, S), dtype=torch.float32, device=self.dev)
+        if g is None and masks is not None:
+            g = torch.empty((len(masks), 1, S, S), dtype=torch.float32, device=self.dev)
+        for t, n, c in ((x, n_img, 3), (g, len(items) - n_img, 1)):
+            if t is not None and (tuple(t.shape) != (n, c, S, S) or t.dtype != torch.float32 or t.device != self.dev or not t.is_contiguous()):
+                raise ValueError(f"out: contiguous fp32 [{n}][{c}][{S}][{S}] on {self.dev}")
+        n = len(items)
+        if n:
+            rows, src_bytes, tmp_bytes = batch_table(shapes, S, self.taps, dst=[i if i < n_img else i - n_img for i in range(n)], norm=[i < n_img for i in range(n)])
+            tb = _up(n * SLOT.itemsize, 256)          # the table leads the arena: host inputs and table travel in one copy
+            if self._staged is not None:
+                self._staged.synchronize()            # the previous batch's copy has left the staging buffer
+            stage = self._buf("stage", tb + src_bytes, pinned=True)
+            host = stage.numpy()
+            host[:n * SLOT.itemsize] = rows.view(np.uint8).reshape(-1)
+            up = n * SLOT.itemsize
+            for r, a in zip(rows, arrs):
+                if a is not None and r["H"] > 0 and not isinstance(a, torch.Tensor):
+                    lo = tb + int(r["src"])
+                    host[lo:lo + a.size] = a.reshape(-1)
+                    up = tb + src_bytes
+            arena, tmp = self._buf("arena", tb + src_bytes), self._buf("tmp", tmp_bytes)
+            arena[:up].copy_(stage[:up], non_blocking=True)
+            if self._staged is None:
+                self._staged = torch.cuda.Event()
+            self._staged.record()
+            for r, a in zip(rows, arrs):
+                if isinstance(a, torch.Tensor) and r["H"] > 0:
+                    lo = tb + int(r["src"])
+                    arena[lo:lo + a.numel()].copy_(a.reshape(-1))
+            taps = self._sync_taps()
+            th, td, src = C.c_void_p(rows.ctypes.data), C.c_void_p(arena.data_ptr()), C.c_void_p(arena.data_ptr() + tb)
+            call.pn2_input_batch_width(th, td, n, S, src, src_bytes, _p(tmp), tmp_bytes, _p(taps), self.taps.ints, st)
+            call.pn2_input_batch_height(th, td, n, S, _p(tmp), tmp_bytes, _p(taps), self.taps.ints, _p(x), n_img, _p(g), n - n_img, _p(self.mean), _p(self.std), st)
+        return x if masks is None else (x, g)
 
     def _taps(self, in_size):
         hit = self._coeffs.get(in_size)

@@ -53,24 +53,29 @@ def _keep_separate(items):
 
 
 class _DeviceBatches:
-    """iterates a host DataLoader and hands every batch through the device transform"""
+    """iterates a host DataLoader and hands every batch through the device transform: batched, the whole host batch goes to DeviceTransform.batch (one copy
+    and two launches); otherwise every array is copied and transformed on its own.  The workers only decode either way."""
 
-    def __init__(self, loader, transform):
-        self.loader, self.transform = loader, transform
+    def __init__(self, loader, transform, batched=True):
+        self.loader, self.transform, self.batched = loader, transform, batched
 
     def __len__(self):
         return len(self.loader)
 
     def __iter__(self):
         for images, masks in self.loader:
-            yield self.transform([t.cuda(non_blocking=True) for t in images], [t.cuda(non_blocking=True) for t in masks])
+            if self.batched:
+                yield self.transform.batch(images, masks)
+            else:
+                yield self.transform([t.cuda(non_blocking=True) for t in images], [t.cuda(non_blocking=True) for t in masks])
 
 
-def get_loader(image_root, gt_root, batchsize, trainsize, shuffle=True, num_workers=4, pin_memory=True):
-    """Same signature as the reference's; iterating yields (images [N][3][S][S], gts [N][1][S][S]) fp32 GPU tensors."""
+def get_loader(image_root, gt_root, batchsize, trainsize, shuffle=True, num_workers=4, pin_memory=True, batched=True):
+    """The reference's signature (and `batched`: False transforms image by image); iterating yields (images [N][3][S][S], gts [N][1][S][S]) fp32 GPU tensors,
+    the same bits either way."""
     host = DataLoader(PolypDataset(image_root, gt_root, trainsize), batch_size=batchsize, shuffle=shuffle, num_workers=num_workers,
                       pin_memory=pin_memory, collate_fn=_keep_separate)
-    return _DeviceBatches(host, DeviceTransform(trainsize))
+    return _DeviceBatches(host, DeviceTransform(trainsize), batched)
 
 
 class test_dataset:
@@ -91,6 +96,21 @@ class test_dataset:
         image = self.transform([_pixels(path, 'RGB').cuda()])
         with Image.open(self.gts[self.index]) as im:
             gt = im.convert('L')
-        stem, ext = os.path.splitext(os.path.basename(path))
         self.index += 1
-        return image, gt, (stem + '.png' if ext == '.jpg' else stem + ext)
+        return image, gt, self._name(path)
+
+    @staticmethod
+    def _name(path):
+        stem, ext = os.path.splitext(os.path.basename(path))
+        return stem + '.png' if ext == '.jpg' else stem + ext
+
+    def load_batch(self, k):
+        """The next min(k, images left) calls of load_data() at once -> (images [m][3][S][S], [m masks], [m names]): one transform call for the batch."""
+        lo, hi = self.index, min(self.index + int(k), self.size)
+        images = self.transform.batch([_pixels(p, 'RGB') for p in self.images[lo:hi]])
+        gts = []
+        for p in self.gts[lo:hi]:
+            with Image.open(p) as im:
+                gts.append(im.convert('L'))
+        self.index = hi
+        return images, gts, [self._name(p) for p in self.images[lo:hi]]
