@@ -680,6 +680,22 @@ int pn2_input_batch_width(const pn2_input_slot* table_host, const pn2_input_slot
 int pn2_input_batch_height(const pn2_input_slot* table_host, const pn2_input_slot* table_dev, int n, int out_size, const unsigned char* tmp, long long tmp_bytes,
                            const int* taps, long long tap_ints, float* out_rgb, int n_rgb, float* out_mask, int n_mask, const float* mean_dev, const float* std_dev,
                            void* stream);
+/* The width pass behind the polyp loaders' augmentation (multiclass_seg/EMCAD/utils/dataloader.py:24-39: RandomRotation(90) with nearest sampling, expand=False and
+ * fill 0, RandomVerticalFlip, RandomHorizontalFlip in front of Resize): the rotation and the flips are a gather at source resolution, and the width pass reads
+ * every source pixel through it - the rotated image is never written and the batch is still two launches (pn2_input_batch_height follows unchanged).
+ * A second table, host and device copies like the first, has one row per slot:
+ *   mode 0         the slot is read directly: the bytes pn2_input_batch_width writes
+ *   mode 1         source pixel (y, x) of every read of the pass - the tap sums, and the copy where W == S - is replaced by src[yin][xin] with
+ *                  xin = (a[2] + a[0] * x + a[1] * y) >> 16, yin = (a[5] + a[3] * x + a[4] * y) >> 16 (int32, arithmetic shift), or by 0 when xin is outside
+ *                  0 .. W-1 or yin outside 0 .. H-1: Pillow's nearest-neighbour affine transform in 16.16 fixed point (Geometry.c affine_fixed), bit for bit
+ *                  when a[] comes from pn2.input.rotate_coeffs.
+ * Status as pn2_input_batch_width, and: -1 a null second table; -3 a mode outside 0 and 1; -2 a mode-1 slot with H or W above PN2_INPUT_AUG_MAX_AXIS, or whose
+ * a[] takes either sum outside int32 at a corner of the slot (the sums are affine: the corners bound them). */
+#define PN2_INPUT_AUG_MAX_AXIS 16384          /* the largest power of two for which rotate_coeffs' sums provably stay inside int32 (derived in csrc/pn2_input.hip) */
+typedef struct { int a[6]; int mode; int reserved; } pn2_input_aug;   /* 32 bytes */
+int pn2_input_batch_width_aug(const pn2_input_slot* table_host, const pn2_input_slot* table_dev, const pn2_input_aug* aug_host, const pn2_input_aug* aug_dev, int n,
+                              int out_size, const unsigned char* src, long long src_bytes, unsigned char* tmp, long long tmp_bytes, const int* taps,
+                              long long tap_ints, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- Synapse slice transform
  * multiclass_seg/EMCAD/utils/dataset_synapse.py:12-47 (RandomGenerator) and utils/utils.py:179-181,197-198 (test_single_volume) on device [N][H][W] batches,

@@ -45,15 +45,47 @@ inline unsigned grid_of(size_t total) { const size_t g = (total + 255) / 256; re
 constexpr int PX = PN2_INPUT_PX;
 
 // width pass of one slot: src [H][W][C] -> tmp [H][S][C]; a copy where W == S (Pillow skips that pass)
-template <int C>
-__device__ __forceinline__ void width_slot(const pn2_input_slot& r, int local, int S, const unsigned char* __restrict__ src, unsigned char* __restrict__ tmp,
-                                           const int* __restrict__ taps, bool wide) {
+// AUG: the slot's row of the second table is given, and in its mode 1 every source pixel is read through the map (rs_map_px / rs_tap_sum_map)
+template <int C, bool AUG>
+__device__ __forceinline__ void width_slot(const pn2_input_slot& r, const pn2_input_aug& g, int local, int S, const unsigned char* __restrict__ src,
+                                           unsigned char* __restrict__ tmp, const int* __restrict__ taps, bool wide) {
     const int G = (S + PX - 1) / PX;
     if (local >= r.H * G) return;
     const int y = local / G, px0 = (local - y * G) * PX;
     const unsigned char* srow = src + r.src + y * r.W * C;
     unsigned char b[PX * C];
-    if (r.W == S) {
+    bool mapped = false;
+    if constexpr (AUG) mapped = g.mode != 0;
+    if (mapped) {
+        if constexpr (AUG) {
+            const unsigned char* img = src + r.src;
+            const int a0 = g.a[0], a3 = g.a[3];
+            const int xx0 = g.a[2] + g.a[1] * y, yy0 = g.a[5] + g.a[4] * y;          // the two sums at column 0 of this row
+            if (r.W == S) {
+#pragma unroll
+                for (int p = 0; p < PX; ++p)
+                    if (px0 + p < S) {
+                        int px[C];
+                        rs_map_px<C>(px, img, r.H, r.W, xx0 + a0 * (px0 + p), yy0 + a3 * (px0 + p));
+#pragma unroll
+                        for (int c = 0; c < C; ++c) b[p * C + c] = (unsigned char)px[c];
+                    }
+            } else {
+                const int* xmin = taps + r.tap_w;
+                const int* cnt = xmin + S;
+                const int* kk = cnt + S;
+#pragma unroll
+                for (int p = 0; p < PX; ++p)
+                    if (px0 + p < S) {
+                        const int ox = px0 + p, x0 = xmin[ox];
+                        int acc[C];
+                        rs_tap_sum_map<C>(acc, img, r.H, r.W, xx0 + a0 * x0, yy0 + a3 * x0, a0, a3, kk + ox * r.kw, cnt[ox]);
+#pragma unroll
+                        for (int c = 0; c < C; ++c) b[p * C + c] = rs_byte(acc[c]);
+                    }
+            }
+        }
+    } else if (r.W == S) {
 #pragma unroll
         for (int p = 0; p < PX; ++p)
             if (px0 + p < S) {
@@ -89,8 +121,9 @@ __device__ __forceinline__ void width_slot(const pn2_input_slot& r, int local, i
     }
 }
 
-__global__ __launch_bounds__(256) void input_batch_width_k(const pn2_input_slot* __restrict__ table, int n, int S, const unsigned char* __restrict__ src,
-                                                           unsigned char* __restrict__ tmp, const int* __restrict__ taps, int wide) {
+template <bool AUG>
+__global__ __launch_bounds__(256) void input_batch_width_k(const pn2_input_slot* __restrict__ table, const pn2_input_aug* __restrict__ aug, int n, int S,
+                                                           const unsigned char* __restrict__ src, unsigned char* __restrict__ tmp, const int* __restrict__ taps, int wide) {
     // the slot of this block: the last one whose first block is <= blockIdx.x (empty slots own no block and share the next slot's prefix)
     int lo = 0, hi = n - 1;
     while (lo < hi) {
@@ -100,8 +133,10 @@ __global__ __launch_bounds__(256) void input_batch_width_k(const pn2_input_slot*
     const pn2_input_slot r = table[lo];
     if (r.H <= 0) return;
     const int local = ((int)blockIdx.x - r.blk) * 256 + (int)threadIdx.x;
-    if (r.C == 3) width_slot<3>(r, local, S, src, tmp, taps, wide != 0);
-    else width_slot<1>(r, local, S, src, tmp, taps, wide != 0);
+    pn2_input_aug g = {};
+    if constexpr (AUG) g = aug[lo];
+    if (r.C == 3) width_slot<3, AUG>(r, g, local, S, src, tmp, taps, wide != 0);
+    else width_slot<1, AUG>(r, g, local, S, src, tmp, taps, wide != 0);
 }
 
 // height pass of one slot fused with ToTensor / Normalize: tmp [H][S][C] -> out [C][S][S] fp32; the byte of resize_pass_k is formed and never stored
@@ -211,6 +246,31 @@ int check_table(const pn2_input_slot* t, int n, int S, long long src_bytes, long
     return 0;
 }
 
+// HOST check of the second table of pn2_input_batch_width_aug.
+// Why PN2_INPUT_AUG_MAX_AXIS = 16384.  Image.rotate's matrix is m0 = m4 = c, m1 = -m3 = s with |c|, |s| <= 1 (cos and sin rounded to 15 decimals) and
+// m2 = W/2 - c * W/2 - s * H/2, so the real sum at (x, y) is v = c * (x + 1/2 - W/2) + s * (y + 1/2 - H/2) + W/2 (the halves are the ones FIX folds into a2), and
+// for 0 <= x <= W, 0 <= y <= H (the kernel's running sums stop one step past the last column):  |v| <= (W + 1)/2 + (H + 1)/2 + W/2 <= 1.5 B + 1  for axes <= B.
+// The integers are a_i = 65536 * m_i + e_i with |e_i| <= 1/2 (FIX rounds; the doubles of m2 add < 1e-5), so |a2 + a0 x + a1 y| <= 65536 * (1.5 B + 1) + (1 + W + H)/2
+// <= 65536 * (1.5 B + 2), and this is < 2^31 = 65536 * 32768 for B = 16384 (24578 < 32768).  The other sum is the same with W and H exchanged.  The flips are
+// the exact integer substitutions x -> W-1-x, y -> H-1-y: the folded integers take the same values on the same set of pixels, the folded a2 / a5 are the sums at a
+// corner pixel, and every partial sum the kernel forms (a2 + a1 y, then + a0 x) is the sum at a pixel of that set.  B = 32768 is not safe: at 45 degrees the sum at a
+// corner is 65536 * (1/2 + 0.7071) * 32768 > 2^31.  Pillow itself leaves this arithmetic for a slower one where |v| >= 32768; below B = 16384 it never does.
+// A table from elsewhere gets the direct test: the sums are affine in (x, y), so their values at the four corners bound them over the slot.
+int check_aug(const pn2_input_slot* t, const pn2_input_aug* g, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (g[i].mode != 0 && g[i].mode != 1) return -3;
+        if (g[i].mode == 0 || t[i].H == 0) continue;
+        if (t[i].H > PN2_INPUT_AUG_MAX_AXIS || t[i].W > PN2_INPUT_AUG_MAX_AXIS) return -2;
+        for (int k = 0; k < 6; k += 3)
+            for (int corner = 0; corner < 4; ++corner) {
+                const long long dx = (long long)g[i].a[k] * ((corner & 1) ? t[i].W : 0), dy = (long long)g[i].a[k + 1] * ((corner & 2) ? t[i].H : 0);
+                const long long v = (long long)g[i].a[k + 2] + dx + dy;
+                if (dx != (int)dx || dy != (int)dy || v != (int)v) return -2;
+            }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -288,7 +348,27 @@ int pn2_input_batch_width(const pn2_input_slot* table_host, const pn2_input_slot
     if (rc) return rc;
     if (blocks == 0) return 0;          // every slot is empty
     const int wide = out_size % 4 == 0 && aligned4 && ((uintptr_t)tmp & 3) == 0;
-    hipLaunchKernelGGL(input_batch_width_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n, out_size, src, tmp, taps, wide);
+    hipLaunchKernelGGL(input_batch_width_k<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table_dev, (const pn2_input_aug*)nullptr, n, out_size, src,
+                       tmp, taps, wide);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+/* the same launch with every source pixel of a mode-1 slot read through the slot's map: rotation and flips never materialise */
+int pn2_input_batch_width_aug(const pn2_input_slot* table_host, const pn2_input_slot* table_dev, const pn2_input_aug* aug_host, const pn2_input_aug* aug_dev, int n,
+                              int out_size, const unsigned char* src, long long src_bytes, unsigned char* tmp, long long tmp_bytes, const int* taps,
+                              long long tap_ints, void* stream) {
+    if (!table_host || !table_dev || !aug_host || !aug_dev || !src || !tmp || !taps || n < 0 || out_size < 1 || src_bytes < 0 || tmp_bytes < 0 || tap_ints < 0) return -1;
+    if (n == 0) return 0;
+    long long blocks = 0;
+    bool aligned4 = false;
+    int rc = check_aug(table_host, aug_host, n);
+    if (rc) return rc;
+    rc = check_table(table_host, n, out_size, src_bytes, tmp_bytes, tap_ints, 0, 0, false, &blocks, &aligned4);
+    if (rc) return rc;
+    if (blocks == 0) return 0;
+    const int wide = out_size % 4 == 0 && aligned4 && ((uintptr_t)tmp & 3) == 0;
+    hipLaunchKernelGGL(input_batch_width_k<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table_dev, aug_dev, n, out_size, src, tmp, taps, wide);
     PN2_CHECK_LAUNCH();
     return 0;
 }

@@ -1,7 +1,8 @@
 // pn2_inputcore.h - the device arithmetic that the per-image input transform (pn2_resize_u8_pass x2 -> pn2_u8_to_tensor) and the ragged-batch transform
 // (pn2_input_batch_width / pn2_input_batch_height, pn2_input.hip) must agree on bit for bit.  Each expression is written ONCE here and inlined into both paths.
 // The tap sum is integer arithmetic (exact in any order: bilinear taps are non-negative and sum to 2^22, so 255 * sum < 2^31); the two fp32 operations of
-// ToTensor / Normalize are true divisions, which no contraction can change.
+// ToTensor / Normalize are true divisions, which no contraction can change.  The augmented width pass (pn2_input_batch_width_aug) adds one variant of the tap sum
+// that reads its pixels through a 16.16 fixed-point map (rs_tap_sum_map over rs_map_px); rounding, clipping and stores are the ones below.
 #pragma once
 #include "pn2_common.h"
 
@@ -27,6 +28,32 @@ __device__ __forceinline__ void rs_tap_sum(int (&acc)[NB], const unsigned char* 
 #pragma unroll
             for (int b = 0; b < NB; ++b) acc[b] += (int)s[b] * kx;
         }
+    }
+}
+
+// The pixel a 16.16 fixed-point map sends a read to (Pillow's Geometry.c affine_fixed, nearest): px[b] = img[yy >> 16][xx >> 16][b] of the [H][W][NB] image,
+// or 0 when either index is outside it.  xx / yy: the two affine sums at the pixel that is asked for.
+template <int NB>
+__device__ __forceinline__ void rs_map_px(int (&px)[NB], const unsigned char* __restrict__ img, int H, int W, int xx, int yy) {
+    const int xin = xx >> 16, yin = yy >> 16;
+    const bool in = xin >= 0 && xin < W && yin >= 0 && yin < H;
+    const unsigned char* s = img + (in ? (yin * W + xin) * NB : 0);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) px[b] = in ? (int)s[b] : 0;
+}
+
+// rs_tap_sum along a row of an image that is read through such a map: tap x multiplies the pixel the sums (xx + x * dx, yy + x * dy) select
+template <int NB>
+__device__ __forceinline__ void rs_tap_sum_map(int (&acc)[NB], const unsigned char* __restrict__ img, int H, int W, int xx, int yy, int dx, int dy,
+                                               const int* __restrict__ k, int n) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = 1 << (RS_PREC - 1);
+    for (int x = 0; x < n; ++x, xx += dx, yy += dy) {
+        const int kx = k[x];
+        int px[NB];
+        rs_map_px<NB>(px, img, H, W, xx, yy);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[b] += px[b] * kx;
     }
 }
 

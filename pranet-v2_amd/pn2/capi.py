@@ -276,6 +276,7 @@ SIGNATURES = {
     "pn2_u8_to_tensor": [P, P, I, I, I, P, P, P],
     "pn2_input_batch_blocks": [I, I],
     "pn2_input_batch_width": [P, P, I, I, P, LL, P, LL, P, LL, P],
+    "pn2_input_batch_width_aug": [P, P, P, P, I, I, P, LL, P, LL, P, LL, P],
     "pn2_input_batch_height": [P, P, I, I, P, LL, P, LL, P, I, P, I, P, P, P],
     "pn2_clamp_adam": [P, P, P, P, LL, FL, FL, FL, FL, FL, FL, P, FL, P],
     "pn2_adam_tick": [P, FL, FL, P],

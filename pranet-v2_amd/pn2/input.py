@@ -1,8 +1,11 @@
 """Device-side input transform: what PolypDataset / test_dataset apply to every decoded image
 (binary_seg/utils/dataloader.py:104-111, 176-181): Resize((S, S)) -> ToTensor() -> Normalize(mean, std) for the image,
 Resize((S, S)) -> ToTensor() for the mask.  File decoding stays on the host (PIL); everything after the uint8 pixels runs on the GPU and is
-bit-exact with torchvision-on-PIL (the resize is Pillow's antialiased bilinear, two uint8 passes with 22-bit fixed-point taps)."""
+bit-exact with torchvision-on-PIL (the resize is Pillow's antialiased bilinear, two uint8 passes with 22-bit fixed-point taps).  The polyp loaders' augmentation
+(multiclass_seg/EMCAD/utils/dataloader.py:24-39: RandomRotation(90), RandomVerticalFlip, RandomHorizontalFlip in front of the resize) runs inside the batched
+transform: rotate_coeffs turns a draw into the integers of Pillow's nearest-neighbour rotate and the width pass reads through them."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -105,10 +108,69 @@ def batch_table(shapes, S, taps, dst=None, norm=None, gap=0):
     return rows, src, tmp
 
 
+# ------------------------------------------------------------------------------------------------ augmentation: rotation and flips as a map the width pass reads through
+# one row of the second table of pn2_input_batch_width_aug (pn2_input_aug, include/pn2.h)
+AUG = np.dtype([("a", "<i4", (6,)), ("mode", "<i4"), ("reserved", "<i4")])
+AUG_MAX_AXIS = 16384          # PN2_INPUT_AUG_MAX_AXIS (include/pn2.h)
+_NO_MAP = (0,) * 8            # a row in mode 0
+
+
+def _fix(v):
+    """Pillow's FIX (Geometry.c): floor(v * 65536 + 0.5), the int cast truncating only where the value is not negative"""
+    v = v * 65536.0 + 0.5
+    return int(v) if v >= 0.0 else int(math.floor(v))
+
+
+def rotate_coeffs(angle, flip_v, flip_h, H, W):
+    """((a0, a1, a2, a3, a4, a5), mode) for an [H][W][C] image: pixel (y, x) of
+        Image.rotate(angle, NEAREST, expand=False) -> transpose(FLIP_TOP_BOTTOM) if flip_v -> transpose(FLIP_LEFT_RIGHT) if flip_h
+    is src[(a5 + a3 * x + a4 * y) >> 16][(a2 + a0 * x + a1 * y) >> 16], or 0 when either index is outside the image - Pillow's bytes.
+    The matrix is Image.rotate's, in Python doubles (angle % 360, -radians, cos / sin rounded to 15 decimals, centre (W/2, H/2)); the integers are Geometry.c's
+    16.16 fixed point (affine_fixed); the flips are the substitutions x -> W-1-x, y -> H-1-y folded into them.  Pillow answers 0 with a copy, 180 and (on square
+    images) 90 / 270 with a transpose, and a matrix without sine terms with its scaling loop: the same integers give those bytes too (tests/test_input_aug_cpu.py).
+    mode 0 - read the source directly - for a multiple of 360 degrees without a flip, else 1."""
+    H, W = int(H), int(W)
+    a = float(angle) % 360.0
+    mode = int(a != 0.0 or bool(flip_v) or bool(flip_h))
+    r = -math.radians(a)
+    c, s = round(math.cos(r), 15), round(math.sin(r), 15)
+    m = [c, s, 0.0, -s, c, 0.0]          # (Pillow rounds -sin: round() is symmetric in sign, zeros included)
+    cx, cy = W / 2, H / 2
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    a0, a1, a3, a4 = _fix(m[0]), _fix(m[1]), _fix(m[3]), _fix(m[4])
+    a2, a5 = _fix(m[2] + m[0] * 0.5 + m[1] * 0.5), _fix(m[5] + m[3] * 0.5 + m[4] * 0.5)
+    if flip_h:          # the last transform applied: x -> W-1-x
+        a2, a5, a0, a3 = a2 + a0 * (W - 1), a5 + a3 * (W - 1), -a0, -a3
+    if flip_v:
+        a2, a5, a1, a4 = a2 + a1 * (H - 1), a5 + a4 * (H - 1), -a1, -a4
+    return (a0, a1, a2, a3, a4, a5), mode
+
+
+def aug_table(shapes, draws):
+    """The second table (dtype AUG) of a batch whose first table was built from `shapes`: draws[i] = (angle, flip_v, flip_h) or None for the slot of shapes[i]."""
+    ints = [_NO_MAP] * len(shapes)
+    done = {}          # a mask has its image's size and draw: the integers are formed once per pair
+    for i, (s, d) in enumerate(zip(shapes, draws)):
+        if s is None or d is None or int(s[0]) == 0:
+            continue
+        if max(int(s[0]), int(s[1])) > AUG_MAX_AXIS:
+            raise ValueError(f"slot {i}: rotation is built for axes up to {AUG_MAX_AXIS}, got {tuple(s)}")
+        key = (float(d[0]), bool(d[1]), bool(d[2]), int(s[0]), int(s[1]))
+        hit = done.get(key)
+        if hit is None:
+            a, mode = rotate_coeffs(*key)
+            hit = done[key] = a + (mode, 0)
+        ints[i] = hit
+    return np.array(ints, dtype=np.int32).reshape(-1).view(AUG)          # (one conversion: row-by-row stores into a structured array cost more than the arithmetic)
+
+
 class DeviceTransform:
     """t = DeviceTransform(352); x, gt = t(images_u8, masks_u8) with lists of uint8 tensors [H][W][3] / [H][W] (any sizes)
     -> x fp32 [N][3][S][S] normalised, gt fp32 [N][1][S][S] in [0, 1]: the batch PolypDataset + DataLoader would collate.
-    t.batch(images_u8, masks_u8) gives the same tensors for the whole list in two launches and one host-to-device copy."""
+    t.batch(images_u8, masks_u8) gives the same tensors for the whole list in two launches and one host-to-device copy; with draws=t.draw(n) every pair is
+    rotated and flipped first, as the polyp loaders' augmentation switch does, in the same two launches."""
 
     def __init__(self, size, mean=_MEAN, std=_STD, device=None):
         if not torch.cuda.is_available():
@@ -144,12 +206,33 @@ class DeviceTransform:
             self.tap_uploads += 1
         return self._taps_dev
 
-    def batch(self, images, masks=None, out=None):
+    @staticmethod
+    def draw(n):
+        """[(angle, flip_v, flip_h)] * n: the random decisions of n consecutive PolypDataset.__getitem__ calls with augmentation on
+        (multiclass_seg/EMCAD/utils/dataloader.py:59-68).  Per sample the loader draws seed = np.random.randint(2147483647) and seeds torch's global generator
+        with it before the image's transforms and again before the mask's, so both get the same decisions; here the seed goes to a private torch.Generator and
+        the global one (DropPath, every other consumer) is left alone.  The draws are those of torchvision 0.8 to 0.12, in the order of the Compose:
+        RandomRotation.get_params: float(torch.empty(1).uniform_(-90., 90.).item()); RandomVerticalFlip, then RandomHorizontalFlip: torch.rand(1) < 0.5.
+        torchvision is not installed where this was written: the calls and their order are taken from its source as remembered, not checked against it."""
+        out = []
+        g = torch.Generator()
+        for _ in range(int(n)):
+            g.manual_seed(int(np.random.randint(2147483647)))
+            angle = float(torch.empty(1).uniform_(-90., 90., generator=g).item())
+            flip_v = bool(torch.rand(1, generator=g) < 0.5)
+            flip_h = bool(torch.rand(1, generator=g) < 0.5)
+            out.append((angle, flip_v, flip_h))
+        return out
+
+    def batch(self, images, masks=None, out=None, draws=None):
         """__call__ for the whole list at once: the same x (and g), bit for bit, from two kernel launches (pn2_input_batch_width / _height) whatever the list's
         length.  images / masks: uint8 arrays [H][W][3] / [H][W] of any sizes - numpy arrays, CPU tensors or tensors on this device; None is an empty slot,
         whose output sample is left as it was (out=(x, g) or out=x: tensors to fill instead of new ones).  Host inputs are packed behind the table in one pinned
         staging buffer and go up in ONE copy; device inputs are gathered with device copies and only the table goes up.  Tap blocks are cached per input size
-        (self.taps), scratch is reused between calls; calls of one DeviceTransform belong on one stream."""
+        (self.taps), scratch is reused between calls; calls of one DeviceTransform belong on one stream.
+        draws: one (angle, flip_v, flip_h) or None per image (draw(n) makes them) - the image and the mask in the same position are rotated (nearest, same size,
+        fill 0) and flipped as Pillow would before the resize.  The width pass reads through the map (pn2_input_batch_width_aug): still two launches, and the
+        second table rides in the same copy as the first.  draws=None makes exactly the calls of a batch without the argument."""
         S, st = self.size, _stream()
         n_img = len(images)
         items = list(images) + (list(masks) if masks is not None else [])
@@ -180,15 +263,22 @@ class DeviceTransform:
             if t is not None and (tuple(t.shape) != (n, c, S, S) or t.dtype != torch.float32 or t.device != self.dev or not t.is_contiguous()):
                 raise ValueError(f"out: contiguous fp32 [{n}][{c}][{S}][{S}] on {self.dev}")
         n = len(items)
+        if draws is not None and len(draws) != n_img:
+            raise ValueError(f"draws: one (angle, flip_v, flip_h) or None per image, got {len(draws)} for {n_img} images")
         if n:
             rows, src_bytes, tmp_bytes = batch_table(shapes, S, self.taps, dst=[i if i < n_img else i - n_img for i in range(n)], norm=[i < n_img for i in range(n)])
-            tb = _up(n * SLOT.itemsize, 256)          # the table leads the arena: host inputs and table travel in one copy
+            aug = None
+            if draws is not None:          # a mask takes the draw of the image in its position
+                aug = aug_table(shapes, [draws[j] if j < n_img else None for j in (i if i < n_img else i - n_img for i in range(n))])
+            up = n * SLOT.itemsize + (n * AUG.itemsize if aug is not None else 0)
+            tb = _up(up, 256)          # the table (and the second one behind it) leads the arena: host inputs and tables travel in one copy
             if self._staged is not None:
                 self._staged.synchronize()            # the previous batch's copy has left the staging buffer
             stage = self._buf("stage", tb + src_bytes, pinned=True)
             host = stage.numpy()
             host[:n * SLOT.itemsize] = rows.view(np.uint8).reshape(-1)
-            up = n * SLOT.itemsize
+            if aug is not None:
+                host[n * SLOT.itemsize:up] = aug.view(np.uint8).reshape(-1)
             for r, a in zip(rows, arrs):
                 if a is not None and r["H"] > 0 and not isinstance(a, torch.Tensor):
                     lo = tb + int(r["src"])
@@ -205,7 +295,11 @@ class DeviceTransform:
                     arena[lo:lo + a.numel()].copy_(a.reshape(-1))
             taps = self._sync_taps()
             th, td, src = C.c_void_p(rows.ctypes.data), C.c_void_p(arena.data_ptr()), C.c_void_p(arena.data_ptr() + tb)
-            call.pn2_input_batch_width(th, td, n, S, src, src_bytes, _p(tmp), tmp_bytes, _p(taps), self.taps.ints, st)
+            if aug is None:
+                call.pn2_input_batch_width(th, td, n, S, src, src_bytes, _p(tmp), tmp_bytes, _p(taps), self.taps.ints, st)
+            else:
+                ah, ad = C.c_void_p(aug.ctypes.data), C.c_void_p(arena.data_ptr() + n * SLOT.itemsize)
+                call.pn2_input_batch_width_aug(th, td, ah, ad, n, S, src, src_bytes, _p(tmp), tmp_bytes, _p(taps), self.taps.ints, st)
             call.pn2_input_batch_height(th, td, n, S, _p(tmp), tmp_bytes, _p(taps), self.taps.ints, _p(x), n_img, _p(g), n - n_img, _p(self.mean), _p(self.std), st)
         return x if masks is None else (x, g)
 

@@ -54,28 +54,40 @@ def _keep_separate(items):
 
 class _DeviceBatches:
     """iterates a host DataLoader and hands every batch through the device transform: batched, the whole host batch goes to DeviceTransform.batch (one copy
-    and two launches); otherwise every array is copied and transformed on its own.  The workers only decode either way."""
+    and two launches); otherwise every array is copied and transformed on its own.  The workers only decode either way.  augmentation: every pair is rotated and
+    flipped by its own draw (DeviceTransform.draw, made here in the iterating process, in batch order) inside the batched transform; unbatched, each pair is a
+    batch of one."""
 
-    def __init__(self, loader, transform, batched=True):
-        self.loader, self.transform, self.batched = loader, transform, batched
+    def __init__(self, loader, transform, batched=True, augmentation=False):
+        self.loader, self.transform, self.batched, self.augmentation = loader, transform, batched, augmentation
 
     def __len__(self):
         return len(self.loader)
 
     def __iter__(self):
         for images, masks in self.loader:
-            if self.batched:
+            if self.augmentation:
+                draws = self.transform.draw(len(images))
+                if self.batched:
+                    yield self.transform.batch(images, masks, draws=draws)
+                else:
+                    pairs = [self.transform.batch([im], [gt], draws=[d]) for im, gt, d in zip(images, masks, draws)]
+                    yield torch.cat([p[0] for p in pairs]), torch.cat([p[1] for p in pairs])
+            elif self.batched:
                 yield self.transform.batch(images, masks)
             else:
                 yield self.transform([t.cuda(non_blocking=True) for t in images], [t.cuda(non_blocking=True) for t in masks])
 
 
-def get_loader(image_root, gt_root, batchsize, trainsize, shuffle=True, num_workers=4, pin_memory=True, batched=True):
+def get_loader(image_root, gt_root, batchsize, trainsize, shuffle=True, num_workers=4, pin_memory=True, batched=True, augmentation=False):
     """The reference's signature (and `batched`: False transforms image by image); iterating yields (images [N][3][S][S], gts [N][1][S][S]) fp32 GPU tensors,
-    the same bits either way."""
+    the same bits either way.  augmentation (True, or 'True' as the polyp training scripts pass it): RandomRotation(90), RandomVerticalFlip and
+    RandomHorizontalFlip in front of the resize, image and mask sharing every draw - the decisions come from numpy's global generator as in the reference
+    (seed it to repeat a run), the pixels are Pillow's."""
+    augmentation = augmentation is True or augmentation == 'True'
     host = DataLoader(PolypDataset(image_root, gt_root, trainsize), batch_size=batchsize, shuffle=shuffle, num_workers=num_workers,
                       pin_memory=pin_memory, collate_fn=_keep_separate)
-    return _DeviceBatches(host, DeviceTransform(trainsize), batched)
+    return _DeviceBatches(host, DeviceTransform(trainsize), batched, augmentation)
 
 
 class test_dataset:

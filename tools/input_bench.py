@@ -2,12 +2,13 @@
 against the ragged-batch path (DeviceTransform.batch on the host arrays) at S = 352, on a fixed, seeded mix of the source sizes recorded in the fixtures
 tests/golden/input_pipeline.npz and eval_full.npz.  Inputs are host arrays, so the host-to-device copies count; file decoding is not part of either path.
 
-    python tools/input_bench.py [--images 1024] [--loops 16] [--reps 7] [--batch-sizes 1,16,32] [--size 352]
+    python tools/input_bench.py [--images 1024] [--loops 16] [--reps 7] [--batch-sizes 1,16,32] [--size 352] [--aug-batch-size 32] [--aug-loops 8]
 
 Prints one JSON line per (batch size, with / without masks): images/s of both paths from the median and the fastest of `reps` timed passes, each `loops` times
 over the set (a window of 0.1 s to 1 s) and ending in a device synchronise; the two paths alternate pass by pass after a warm pass of each (which fills the tap
 caches and sizes the buffers).  Launches and host-to-device copies per batch are counted from the call sequence, and `equal` says whether the two
-paths returned the same bits."""
+paths returned the same bits.  A last line ("augmented": true) times the loaders' augmentation on the same set with masks: PIL rotate and transposes on the host
+followed by batch(), against batch(draws=...) (see augmented())."""
 import argparse
 import json
 import os
@@ -41,7 +42,9 @@ def main():
     ap.add_argument("--loops", type=int, default=16)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--size", type=int, default=352)
-    ap.add_argument("--batch-sizes", default="1,16,32")
+    ap.add_argument("--batch-sizes", default="1,16,32", help="batch sizes of the per-image / batch lines ('' for none)")
+    ap.add_argument("--aug-batch-size", type=int, default=32, help="batch size of the augmented line (0: no such line)")
+    ap.add_argument("--aug-loops", type=int, default=8)
     a = ap.parse_args()
     from pn2.input import DeviceTransform
     if not torch.cuda.is_available():
@@ -49,7 +52,7 @@ def main():
     imgs, gts = make_set(a.images)
     n = len(imgs)
     for with_masks in (True, False):
-        for bs in [int(v) for v in a.batch_sizes.split(",")]:
+        for bs in [int(v) for v in a.batch_sizes.split(",") if v]:
             t = DeviceTransform(a.size)
             chunks = [(imgs[i:i + bs], gts[i:i + bs] if with_masks else None) for i in range(0, n, bs)]
 
@@ -88,6 +91,62 @@ def main():
                 row[name] = {"images_per_s_median": n_timed / med, "images_per_s_best": n_timed / min(ts[name]), "spread": (max(ts[name]) - min(ts[name])) / med}
             row["ratio_median"] = row["batch"]["images_per_s_median"] / row["per_image"]["images_per_s_median"]
             print(json.dumps(row), flush=True)
+    if a.aug_batch_size > 0:
+        augmented(a, imgs, gts)
+
+
+def augmented(a, imgs, gts):
+    """The augmented line: pairs rotated and flipped by seeded draws.  `host_pil` is what a user of batch() without draws has to do - Image.rotate(NEAREST) and
+    the two transposes on the host for every image and mask, then DeviceTransform.batch; `device` is batch(draws=...), the same two launches reading through the
+    map.  Same set, same S, host arrays in; wrapping an array as a PIL image and reading the result back are part of the host path, as they are for that user."""
+    from PIL import Image
+    from pn2.input import DeviceTransform
+    bs, n = a.aug_batch_size, len(imgs)
+    np.random.seed(0)
+    draws = DeviceTransform.draw(n)
+    t = DeviceTransform(a.size)
+    chunks = [(imgs[i:i + bs], gts[i:i + bs], draws[i:i + bs]) for i in range(0, n, bs)]
+
+    def pil(arr, d):
+        im = Image.fromarray(arr.numpy()).rotate(d[0], Image.NEAREST, expand=False)
+        if d[1]:
+            im = im.transpose(Image.FLIP_TOP_BOTTOM)
+        if d[2]:
+            im = im.transpose(Image.FLIP_LEFT_RIGHT)
+        return np.asarray(im)
+
+    def host_pil():
+        out = None
+        for im, gt, dr in chunks * loops[0]:
+            out = t.batch([pil(x, d) for x, d in zip(im, dr)], [pil(x, d) for x, d in zip(gt, dr)])
+        return out
+
+    def device():
+        out = None
+        for im, gt, dr in chunks * loops[0]:
+            out = t.batch(im, gt, draws=dr)
+        return out
+    ts = {"host_pil": [], "device": []}
+    last = {}
+    loops = [1]
+    for rep in range(a.reps + 1):
+        for name, fn in (("host_pil", host_pil), ("device", device)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[name] = fn()
+            torch.cuda.synchronize()
+            if rep:
+                ts[name].append(time.perf_counter() - t0)
+        loops[0] = a.aug_loops
+    n_timed = n * a.aug_loops
+    row = {"augmented": True, "batch_size": bs, "masks": True, "images": n_timed, "size": a.size,
+           "equal": bool(all(torch.equal(u, v) for u, v in zip(last["host_pil"], last["device"]))), "launches_per_batch": {"host_pil": 2, "device": 2},
+           "h2d_copies_per_batch": {"host_pil": 1, "device": 1}}
+    for name in ("host_pil", "device"):
+        med = statistics.median(ts[name])
+        row[name] = {"images_per_s_median": n_timed / med, "images_per_s_best": n_timed / min(ts[name]), "spread": (max(ts[name]) - min(ts[name])) / med}
+    row["ratio_median"] = row["device"]["images_per_s_median"] / row["host_pil"]["images_per_s_median"]
+    print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":
