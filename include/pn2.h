@@ -719,6 +719,50 @@ int pn2_zoom0(int elem, const void* src, int N, int H, int W, int OH, int OW, co
 int pn2_rotate0(int elem, const void* src, int N, int H, int W, const double* m6_dev, void* out, void* stream);
 int pn2_rot_flip(int elem, const void* src, int N, int S, const int* kaxis_dev, void* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- ACDC slice pipeline: ragged batches through the spline zoom
+ * multiclass_seg/EMCAD/utils/dataset_ACDC.py:13-48 (random_rot_flip, random_rotate and RandomGenerator on slices of any, also non-square, shape) and
+ * multiclass_seg/MIST/ACDC_train_test.py:48-93 (val(): zoom in, net, order-0 zoom back to the slice's own size, one binary Dice per slice) on batches whose
+ * samples each have their own [H][W].  The same bits as the uniform entry points above; the launch count does not depend on N or on how many shapes a batch holds.
+ * pn2_ragged_plan is HOST code (no GPU needed): from one pn2_ragged_sample per sample it writes ONE blob - header, N descriptors, the two block prefix tables of the
+ *   prefilter (axis 0: 64-column tiles of the shape after the geometry, axis 1: 64-row tiles; a sample already at its output size has none) and the concatenated
+ *   per-axis tables, each (nin, nout, order) once per blob and cached in the process.  Table layout, in 8-byte units from the start of the table area: order 3 of an
+ *   axis = w[nout][4] doubles, then idx[nout][4] ints; order 0 = idx[nout] ints; an output index whose coordinate lies past the last sample has idx[..][0] = -1.
+ *   packed = 1: the samples lie back to back in one source buffer (src_off = lab_off = running sum of H * W, given values ignored); packed = 0: the offsets of the
+ *   samples are taken as given, in elements relative to the base pointer of the launch (fp32 elements for src_off, bytes for lab_off; they may be negative).
+ *   Returns -1 null pointer, -2 N outside 1 .. PN2_RAGGED_MAX_N or an axis outside 1 .. 1024, -3 a geometry that is none of the three or a k / axis outside
+ *   0..3 / -1..1, -4 blob too small (pn2_ragged_plan_bound bytes always suffice).
+ * geom: 0 none, 1 np.flip(np.rot90(a, k), axis) (axis -1: no flip; odd k swaps the shape: gh = W, gw = H), 2 ndimage.rotate(order=0, reshape=False) with m6 as in
+ *   pn2_rotate0 - dataset_ACDC.py:37-40 never applies both.  copy = 1 where (gh, gw) == (oh, ow): the reference skips zoom there (:42), so the image is the geometry
+ *   map of the source as raw bits - no prefilter, no gather (a spline zoom by 1 is not a copy) - and the label likewise.
+ * The launchers read the header from the HOST copy of the blob and hand the DEVICE copy (the same bytes) to the kernels; both pointers are required.
+ * pn2_ragged_prefilter: fp32 samples -> float64 coefficients of the shape after the geometry, sample n at work[work_off] (2 * header.work_doubles doubles in all).
+ *   4 launches (none if every sample is a copy); the first reads the source through the geometry map, so the augmentation has no launch or plane of its own.
+ * pn2_ragged_zoom3: coefficients -> fp32, sample n as [oh][ow] at out[out_off] (1 launch).  pn2_ragged_zoom0: the geometry map composed with the order-0 map,
+ *   u8 -> u8 at out[out_off] (1 launch) - the label path of a training batch, and with per-sample (oh, ow) the way back of val().
+ * pn2_ragged_dice_counts: counts [N][3] long long = { |pred != 0 and gt != 0|, |pred != 0|, |gt != 0| } of the packed u8 buffers, sample n at [out_off] (1 launch). */
+#define PN2_RAGGED_MAX_N 4096
+typedef struct { int H, W, oh, ow, geom, k, axis, pad_; long long src_off, lab_off; double m6[6]; } pn2_ragged_sample;
+typedef struct {
+    long long src_off, lab_off, work_off, out_off;   /* elements: fp32 source, u8 source, doubles in each workspace plane, output */
+    int H, W, gh, gw, oh, ow;                        /* source shape, shape after the geometry, output shape */
+    int geom, k, axis, copy;
+    int ty3, tx3, ty0, tx0;                          /* table offsets in 8-byte units (0 and unused for a copy) */
+    double zn0, zn1;                                 /* pole^(gh-1), pole^(gw-1) */
+    double m6[6];
+} pn2_ragged_desc;
+typedef struct {
+    int magic, N, blocks0, blocks1, max_out, uniform_out;
+    int desc_off, bs0_off, bs1_off, tab_off;         /* byte offsets into the blob */
+    int ntables, pad_;
+    long long bytes, work_doubles, src_elems, out_elems;   /* used bytes; doubles per workspace plane; packed source / output elements */
+} pn2_ragged_header;
+int pn2_ragged_plan_bound(int N, const pn2_ragged_sample* samples, long long* bytes);
+int pn2_ragged_plan(int N, const pn2_ragged_sample* samples, int packed, void* blob, long long blob_bytes);
+int pn2_ragged_prefilter(const float* src, const void* plan_host, const void* plan_dev, void* work, void* stream);
+int pn2_ragged_zoom3(const float* src, const void* plan_host, const void* plan_dev, const void* work, float* out, void* stream);
+int pn2_ragged_zoom0(const unsigned char* src, const void* plan_host, const void* plan_dev, unsigned char* out, void* stream);
+int pn2_ragged_dice_counts(const unsigned char* pred, const unsigned char* gt, const void* plan_host, const void* plan_dev, long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,8 +7,15 @@
 // Every float64 operation is the one ni_splines.c / ni_interpolation.c perform, in their order; scipy's build has no fused multiply-add, so contraction is off
 // for this whole file (hipcc contracts a + b*c by default).  The coordinate tables and z^(n-1) are computed on the host in double (pn2_zoom_tables,
 // pn2_zoom_pole_pow), so no device pow / floor of a product decides a bit.
+// The pn2_ragged_* half serves batches whose samples each have their own [H][W] (the ACDC slices: dataset_ACDC.py:13-48, MIST/ACDC_train_test.py:48-93) from one
+// host-built descriptor table, with the same line bodies and the same host tables, so the same bits.
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <tuple>
+#include <vector>
 #include "pn2_common.h"
 #include "../../include/pn2.h"
 
@@ -25,18 +32,15 @@ inline double filter_gain() { return 1.0 * ((1.0 - ZP) * (1.0 - 1.0 / ZP)); }
 
 // ---- prefilter, first half of one axis: gain, mirror initialisation (the whole line, serial), causal sweep.  One thread owns one line: src / dst are
 // [N][R][Cn] with the line along R and the 64 lanes of a block on consecutive columns, so every load and store of the wave is one contiguous 256 / 512 bytes.
-template <typename TS>
-__global__ __launch_bounds__(64) void spline_causal_k(const TS* __restrict__ src, double* __restrict__ dst, int R, int Cn, int nb, double z, double gain, double zn) {
-    const int n = blockIdx.x / nb, c = (blockIdx.x - n * nb) * 64 + threadIdx.x;
-    if (c >= Cn) return;
-    const TS* s = src + (size_t)n * R * Cn + c;
-    double* d = dst + (size_t)n * R * Cn + c;
-    if (R == 1) { d[0] = (double)s[0]; return; }          // scipy skips an axis of length 1 (no gain either)
-    double c0 = (double)s[0] * gain + zn * ((double)s[(size_t)(R - 1) * Cn] * gain);
+// The body of one line, shared by the uniform and the ragged kernels: at(i) is sample i of the line as a double, d its first output, Cn the output pitch.
+template <typename L>
+__device__ __forceinline__ void causal_line(L at, double* __restrict__ d, int R, int Cn, double z, double gain, double zn) {
+    if (R == 1) { d[0] = at(0); return; }          // scipy skips an axis of length 1 (no gain either)
+    double c0 = at(0) * gain + zn * (at(R - 1) * gain);
     double zi = z;
 #pragma unroll 8
     for (int i = 1; i < R - 1; ++i) {          // zi turns denormal near i = 540 and zero near 566: the loop runs on as scipy's does
-        const double a = (double)s[(size_t)i * Cn] * gain, b = (double)s[(size_t)(R - 1 - i) * Cn] * gain;
+        const double a = at(i) * gain, b = at(R - 1 - i) * gain;
         c0 = c0 + zi * (a + zn * b);
         zi = zi * z;
     }
@@ -44,9 +48,17 @@ __global__ __launch_bounds__(64) void spline_causal_k(const TS* __restrict__ src
     d[0] = c0;
 #pragma unroll 8
     for (int i = 1; i < R; ++i) {
-        c0 = (double)s[(size_t)i * Cn] * gain + z * c0;
+        c0 = at(i) * gain + z * c0;
         d[(size_t)i * Cn] = c0;
     }
+}
+
+template <typename TS>
+__global__ __launch_bounds__(64) void spline_causal_k(const TS* __restrict__ src, double* __restrict__ dst, int R, int Cn, int nb, double z, double gain, double zn) {
+    const int n = blockIdx.x / nb, c = (blockIdx.x - n * nb) * 64 + threadIdx.x;
+    if (c >= Cn) return;
+    const TS* s = src + (size_t)n * R * Cn + c;
+    causal_line([=](int i) { return (double)s[(size_t)i * Cn]; }, dst + (size_t)n * R * Cn + c, R, Cn, z, gain, zn);
 }
 
 // ---- second half: anticausal initialisation and sweep, from the last row down, written TRANSPOSED: dst is [N][Cn][R].  The next axis then runs through the
@@ -54,12 +66,12 @@ __global__ __launch_bounds__(64) void spline_causal_k(const TS* __restrict__ src
 // LDS tile of 33 doubles per line: the column-wise ds_write_b64 of the sweep then falls on banks 2 * lane mod 32 (2 lanes per bank and half wave, the rate
 // of an 8-byte store anyway; 32 doubles per line would put all 64 lanes on one bank), and the row-wise ds_read_b64 of the store takes 64 consecutive dwords
 // per half wave.  Each half wave stores 256 contiguous bytes.
-__global__ __launch_bounds__(64) void spline_anticausal_t_k(const double* __restrict__ src, double* __restrict__ dst, int R, int Cn, int nb, double z) {
-    __shared__ double tile[64][TR + 1];
-    const int tid = threadIdx.x, n = blockIdx.x / nb, cb = (blockIdx.x - n * nb) * 64, c = cb + tid;
+// The body of one block, shared by the uniform and the ragged kernels: sp / dn are the [R][Cn] source and the [Cn][R] destination plane of the block's sample, cb its
+// first column.
+__device__ __forceinline__ void anticausal_t_lines(const double* __restrict__ sp, double* __restrict__ dn, int R, int Cn, int cb, double z, double (*tile)[TR + 1]) {
+    const int tid = threadIdx.x, c = cb + tid;
     const bool live = c < Cn;
-    const double* s = src + (size_t)n * R * Cn + (live ? c : 0);
-    double* dn = dst + (size_t)n * R * Cn;
+    const double* s = sp + (live ? c : 0);
     double next = 0.0, last = 0.0;
     if (live) last = R > 1 ? (z * s[(size_t)(R - 2) * Cn] + s[(size_t)(R - 1) * Cn]) * z / (z * z - 1.0) : s[0];
     for (int k = (R - 1) / TR; k >= 0; --k) {
@@ -83,6 +95,12 @@ __global__ __launch_bounds__(64) void spline_anticausal_t_k(const double* __rest
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(64) void spline_anticausal_t_k(const double* __restrict__ src, double* __restrict__ dst, int R, int Cn, int nb, double z) {
+    __shared__ double tile[64][TR + 1];
+    const int n = blockIdx.x / nb;
+    anticausal_t_lines(src + (size_t)n * R * Cn, dst + (size_t)n * R * Cn, R, Cn, (blockIdx.x - n * nb) * 64, z, tile);
 }
 
 // ---- order 3: out[y][x] = sum_j sum_k (coef[iy_j][ix_k] * wy_j) * wx_k, j outer, k inner, from 0.0 (ni_interpolation.c:NI_ZoomShift), cast to float32
@@ -153,6 +171,130 @@ __global__ __launch_bounds__(256) void rot_flip_k(const T* __restrict__ src, int
     }
 }
 
+// ================================================================================================ ragged batches (pn2_ragged_*): every sample its own [H][W]
+// Element (i, j) of sample d AFTER its geometry (shape gh x gw), read from the source: the index map of rot_flip_k for any H x W (odd k: gh = W, gw = H), the
+// nearest-sample map of rotate0_k with 0 outside, or the element itself.  Raw bits either way, so this equals materialising the augmented plane first.
+template <typename T>
+__device__ __forceinline__ T geom_load(const T* __restrict__ s, const pn2_ragged_desc& d, int i, int j) {
+    if (d.geom == 1) {
+        if (d.axis == 0) i = d.gh - 1 - i; else if (d.axis == 1) j = d.gw - 1 - j;
+        int si = i, sj = j;                                      // rot90(a, 1)[i][j] = a[j][W-1-i], rot90(a, 3)[i][j] = a[H-1-j][i]
+        if (d.k == 1) { si = j; sj = d.W - 1 - i; }
+        else if (d.k == 2) { si = d.H - 1 - i; sj = d.W - 1 - j; }
+        else if (d.k == 3) { si = d.H - 1 - j; sj = i; }
+        return s[(size_t)si * d.W + sj];
+    }
+    if (d.geom == 2) {
+        const double cy = (d.m6[4] + (double)i * d.m6[0]) + (double)j * d.m6[1];
+        const double cx = (d.m6[5] + (double)i * d.m6[2]) + (double)j * d.m6[3];
+        if (cy >= 0.0 && cy <= (double)(d.H - 1) && cx >= 0.0 && cx <= (double)(d.W - 1))
+            return s[(size_t)floor(cy + 0.5) * d.W + (size_t)floor(cx + 0.5)];
+        return (T)0;
+    }
+    return s[(size_t)i * d.W + j];
+}
+
+// Block b of a prefilter pass -> (sample, 64-line tile) through the pass's prefix table (a sample that is a plain copy has no blocks).
+// AXIS 0: lines along gh, lanes on the gw columns, the fp32 source read through the geometry map.  AXIS 1: lines along gw of the transposed plane [gw][gh].
+template <int AXIS>
+__global__ __launch_bounds__(64) void ragged_causal_k(const float* __restrict__ src, const double* __restrict__ plane, double* __restrict__ dst,
+                                                      const pn2_ragged_desc* __restrict__ descs, const int* __restrict__ bstart, int N, double z, double gain) {
+    const int n = find_job(bstart, N, (int)blockIdx.x);
+    const pn2_ragged_desc d = descs[n];
+    const int R = AXIS == 0 ? d.gh : d.gw, Cn = AXIS == 0 ? d.gw : d.gh;
+    const int c = ((int)blockIdx.x - bstart[n]) * 64 + (int)threadIdx.x;
+    if (c >= Cn) return;
+    double* o = dst + d.work_off + c;
+    if (AXIS == 0) {
+        const float* s = src + d.src_off;
+        causal_line([&](int i) { return (double)geom_load(s, d, i, c); }, o, R, Cn, z, gain, d.zn0);
+    } else {
+        const double* s = plane + d.work_off + c;
+        causal_line([=](int i) { return s[(size_t)i * Cn]; }, o, R, Cn, z, gain, d.zn1);
+    }
+}
+
+template <int AXIS>
+__global__ __launch_bounds__(64) void ragged_anticausal_t_k(const double* __restrict__ src, double* __restrict__ dst, const pn2_ragged_desc* __restrict__ descs,
+                                                            const int* __restrict__ bstart, int N, double z) {
+    __shared__ double tile[64][TR + 1];
+    const int n = find_job(bstart, N, (int)blockIdx.x);          // uniform over the block: every thread reaches the barriers of the body
+    const pn2_ragged_desc* d = descs + n;
+    const int R = AXIS == 0 ? d->gh : d->gw, Cn = AXIS == 0 ? d->gw : d->gh;
+    anticausal_t_lines(src + d->work_off, dst + d->work_off, R, Cn, ((int)blockIdx.x - bstart[n]) * 64, z, tile);
+}
+
+// order 3 of sample blockIdx.y: the sum of zoom3_gather_k with the sample's own tables, or the geometry map alone where the sample is a copy
+__global__ __launch_bounds__(256) void ragged_zoom3_k(const float* __restrict__ src, const double* __restrict__ work, const pn2_ragged_desc* __restrict__ descs,
+                                                      const double* __restrict__ tab, float* __restrict__ out) {
+    const pn2_ragged_desc d = descs[blockIdx.y];
+    const int total = d.oh * d.ow;
+    const float* s = src + d.src_off;
+    float* o = out + d.out_off;
+    const double* p = work + d.work_off;
+    const double* wy = tab + d.ty3;
+    const double* wx = tab + d.tx3;
+    const int* iy = (const int*)(wy + 4 * d.oh);
+    const int* ix = (const int*)(wx + 4 * d.ow);
+    for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < total; i += (int)gridDim.x * 256) {
+        const int oy = i / d.ow, ox = i - oy * d.ow;
+        float r = 0.0f;
+        if (d.copy) r = geom_load(s, d, oy, ox);
+        else if (iy[oy * 4] >= 0 && ix[ox * 4] >= 0) {
+            double t = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double* row = p + (size_t)iy[oy * 4 + j] * d.gw;
+                const double wj = wy[oy * 4 + j];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) t = t + (row[ix[ox * 4 + k]] * wj) * wx[ox * 4 + k];
+            }
+            r = (float)t;
+        }
+        o[i] = r;
+    }
+}
+
+// order 0 of sample blockIdx.y, u8: out[y][x] = geometry map at (iy[y], ix[x]), 0 where either coordinate lies past the last sample
+__global__ __launch_bounds__(256) void ragged_zoom0_k(const uint8_t* __restrict__ src, const pn2_ragged_desc* __restrict__ descs, const double* __restrict__ tab,
+                                                      uint8_t* __restrict__ out) {
+    const pn2_ragged_desc d = descs[blockIdx.y];
+    const int total = d.oh * d.ow;
+    const uint8_t* s = src + d.lab_off;
+    uint8_t* o = out + d.out_off;
+    const int* iy = (const int*)(tab + d.ty0);
+    const int* ix = (const int*)(tab + d.tx0);
+    for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < total; i += (int)gridDim.x * 256) {
+        int oy = i / d.ow, ox = i - oy * d.ow;
+        bool ok = true;
+        if (!d.copy) { oy = iy[oy]; ox = ix[ox]; ok = oy >= 0 && ox >= 0; }
+        o[i] = ok ? geom_load(s, d, oy, ox) : (uint8_t)0;
+    }
+}
+
+// one block per sample: |pred != 0 and gt != 0|, |pred != 0|, |gt != 0| of its oh * ow bytes (at most 2^20: the sums fit an int)
+__global__ __launch_bounds__(256) void ragged_dice_k(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ gt, const pn2_ragged_desc* __restrict__ descs,
+                                                     long long* __restrict__ counts) {
+    __shared__ int part[4][3];
+    const pn2_ragged_desc* d = descs + blockIdx.x;
+    const int total = d->oh * d->ow;
+    const uint8_t* p = pred + d->out_off;
+    const uint8_t* g = gt + d->out_off;
+    int v[3] = {0, 0, 0};
+    for (int i = (int)threadIdx.x; i < total; i += 256) {
+        const int a = p[i] != 0, b = g[i] != 0;
+        v[0] += a & b; v[1] += a; v[2] += b;
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][q] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) counts[(size_t)blockIdx.x * 3 + threadIdx.x] = (long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
 inline bool axes_ok(int N, int H, int W) { return N >= 1 && H >= 1 && W >= 1 && H <= MAX_AXIS && W <= MAX_AXIS && (long long)N * H * W < (1ll << 40); }
 inline unsigned grid_of(size_t total) { return (unsigned)pn2_host::grid_for(total, 16384); }
 
@@ -162,6 +304,37 @@ int with_elem(int elem, F f) {
     if (elem == 4) return f(Ty<uint32_t>{});
     return -3;
 }
+
+constexpr int RAGGED_MAGIC = 0x52474431;
+// 8-byte units of one axis table in a plan: order 3 = 4 doubles + 4 ints per output index, order 0 = one int
+inline int table_units(int nout, int order) { return order == 3 ? 6 * nout : (nout + 1) / 2; }
+inline std::mutex& ragged_mutex() { static std::mutex m; return m; }
+
+// The table of one (nin, nout, order) in the plan's layout, from pn2_zoom_tables; kept for the life of the process (the caller holds ragged_mutex)
+const std::vector<double>& ragged_table(int nin, int nout, int order) {
+    static std::map<std::tuple<int, int, int>, std::vector<double>> cache;
+    const auto key = std::make_tuple(nin, nout, order);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    const int per = order == 3 ? 4 : 1;
+    std::vector<int> idx((size_t)nout * per), valid((size_t)nout);
+    std::vector<double> w((size_t)nout * 4);
+    pn2_zoom_tables(nin, nout, order, idx.data(), w.data(), valid.data());
+    std::vector<double> t((size_t)table_units(nout, order), 0.0);
+    int* ti = (int*)(t.data() + (order == 3 ? 4 * nout : 0));
+    if (order == 3) std::memcpy(t.data(), w.data(), sizeof(double) * 4 * (size_t)nout);
+    for (int o = 0; o < nout; ++o) {
+        for (int l = 0; l < per; ++l) ti[o * per + l] = idx[o * per + l];
+        if (!valid[o]) ti[o * per] = -1;
+    }
+    return cache.emplace(key, std::move(t)).first->second;
+}
+
+inline bool header_ok(const pn2_ragged_header* h) {
+    return h->magic == RAGGED_MAGIC && h->N >= 1 && h->N <= PN2_RAGGED_MAX_N && h->blocks0 >= 0 && h->blocks1 >= 0 && (h->blocks0 == 0) == (h->blocks1 == 0) &&
+           h->max_out >= 1 && h->max_out <= MAX_AXIS * MAX_AXIS && h->desc_off == (int)sizeof(pn2_ragged_header);
+}
+inline unsigned ragged_grid_x(const pn2_ragged_header* h) { const int g = (h->max_out + 255) / 256; return (unsigned)(g > 1024 ? 1024 : g); }
 
 }  // namespace
 
@@ -281,6 +454,152 @@ int pn2_rot_flip(int elem, const void* src, int N, int S, const int* kaxis_dev, 
         PN2_CHECK_LAUNCH();
         return 0;
     });
+}
+
+// ---- ragged batches: the planner (host only) and the launchers
+int pn2_ragged_plan_bound(int N, const pn2_ragged_sample* samples, long long* bytes) {
+    if (!samples || !bytes) return -1;
+    if (N < 1 || N > PN2_RAGGED_MAX_N) return -2;
+    long long b = (long long)sizeof(pn2_ragged_header) + (long long)N * sizeof(pn2_ragged_desc) + 8ll * (N + 1);
+    for (int n = 0; n < N; ++n) {
+        const pn2_ragged_sample& s = samples[n];
+        if (s.oh < 1 || s.ow < 1 || s.oh > MAX_AXIS || s.ow > MAX_AXIS) return -2;
+        b += 8ll * (table_units(s.oh, 3) + table_units(s.ow, 3) + table_units(s.oh, 0) + table_units(s.ow, 0));
+    }
+    *bytes = b;
+    return 0;
+}
+
+int pn2_ragged_plan(int N, const pn2_ragged_sample* samples, int packed, void* blob, long long blob_bytes) {
+    if (!samples || !blob) return -1;
+    if (N < 1 || N > PN2_RAGGED_MAX_N) return -2;
+    for (int n = 0; n < N; ++n) {
+        const pn2_ragged_sample& s = samples[n];
+        if (s.H < 1 || s.W < 1 || s.oh < 1 || s.ow < 1 || s.H > MAX_AXIS || s.W > MAX_AXIS || s.oh > MAX_AXIS || s.ow > MAX_AXIS) return -2;
+        if (s.geom < 0 || s.geom > 2 || (s.geom == 1 && (s.k < 0 || s.k > 3 || s.axis < -1 || s.axis > 1))) return -3;
+    }
+    pn2_ragged_header h = {};
+    h.magic = RAGGED_MAGIC;
+    h.N = N;
+    h.desc_off = (int)sizeof(pn2_ragged_header);
+    h.bs0_off = h.desc_off + N * (int)sizeof(pn2_ragged_desc);
+    h.bs1_off = h.bs0_off + 4 * (N + 1);
+    h.tab_off = h.bs1_off + 4 * (N + 1);          // 8 (N + 1) bytes of prefix tables: the table area stays 8-byte aligned
+    h.uniform_out = 1;
+    std::vector<pn2_ragged_desc> descs((size_t)N);
+    std::vector<int> bs0((size_t)N + 1, 0), bs1((size_t)N + 1, 0);
+    std::vector<double> tab;
+    std::map<std::tuple<int, int, int>, int> placed;          // (nin, nout, order) -> offset in this blob: samples of equal axes share one table
+    std::lock_guard<std::mutex> lock(ragged_mutex());
+    auto place = [&](int nin, int nout, int order) {
+        const auto key = std::make_tuple(nin, nout, order);
+        auto it = placed.find(key);
+        if (it != placed.end()) return it->second;
+        const std::vector<double>& t = ragged_table(nin, nout, order);
+        const int off = (int)tab.size();
+        tab.insert(tab.end(), t.begin(), t.end());
+        placed[key] = off;
+        return off;
+    };
+    long long src = 0, work = 0, out = 0;
+    for (int n = 0; n < N; ++n) {
+        const pn2_ragged_sample& s = samples[n];
+        pn2_ragged_desc& d = descs[n];
+        d = pn2_ragged_desc{};
+        const bool swap = s.geom == 1 && (s.k & 1);
+        d.H = s.H; d.W = s.W; d.gh = swap ? s.W : s.H; d.gw = swap ? s.H : s.W; d.oh = s.oh; d.ow = s.ow;
+        d.geom = s.geom; d.k = s.geom == 1 ? s.k : 0; d.axis = s.geom == 1 ? s.axis : -1;
+        d.copy = d.gh == d.oh && d.gw == d.ow;
+        d.src_off = packed ? src : s.src_off;
+        d.lab_off = packed ? src : s.lab_off;
+        d.out_off = out;
+        d.work_off = work;
+        d.zn0 = std::pow(ZP, (double)(d.gh - 1));
+        d.zn1 = std::pow(ZP, (double)(d.gw - 1));
+        if (s.geom == 2) for (int q = 0; q < 6; ++q) d.m6[q] = s.m6[q];
+        bs0[n + 1] = bs0[n]; bs1[n + 1] = bs1[n];
+        if (!d.copy) {
+            d.ty3 = place(d.gh, d.oh, 3); d.tx3 = place(d.gw, d.ow, 3);
+            d.ty0 = place(d.gh, d.oh, 0); d.tx0 = place(d.gw, d.ow, 0);
+            bs0[n + 1] += (d.gw + 63) / 64; bs1[n + 1] += (d.gh + 63) / 64;
+            work += (long long)d.gh * d.gw;
+        }
+        src += (long long)s.H * s.W;
+        out += (long long)s.oh * s.ow;
+        if (s.oh * s.ow > h.max_out) h.max_out = s.oh * s.ow;
+        if (s.oh != samples[0].oh || s.ow != samples[0].ow) h.uniform_out = 0;
+    }
+    h.blocks0 = bs0[N]; h.blocks1 = bs1[N];
+    h.ntables = (int)placed.size();
+    h.work_doubles = work; h.src_elems = packed ? src : 0; h.out_elems = out;
+    h.bytes = (long long)h.tab_off + 8ll * (long long)tab.size();
+    if (h.bytes > blob_bytes) return -4;
+    char* b = (char*)blob;
+    std::memcpy(b, &h, sizeof h);
+    std::memcpy(b + h.desc_off, descs.data(), (size_t)N * sizeof(pn2_ragged_desc));
+    std::memcpy(b + h.bs0_off, bs0.data(), 4 * ((size_t)N + 1));
+    std::memcpy(b + h.bs1_off, bs1.data(), 4 * ((size_t)N + 1));
+    if (!tab.empty()) std::memcpy(b + h.tab_off, tab.data(), 8 * tab.size());
+    return 0;
+}
+
+int pn2_ragged_prefilter(const float* src, const void* plan_host, const void* plan_dev, void* work, void* stream) {
+    if (!src || !plan_host || !plan_dev) return -1;
+    const pn2_ragged_header* h = (const pn2_ragged_header*)plan_host;
+    if (!header_ok(h)) return -2;
+    if (h->blocks0 == 0) return 0;          // every sample is already at its output size
+    if (!work) return -1;
+    const char* pd = (const char*)plan_dev;
+    const pn2_ragged_desc* descs = (const pn2_ragged_desc*)(pd + h->desc_off);
+    const int* bs0 = (const int*)(pd + h->bs0_off);
+    const int* bs1 = (const int*)(pd + h->bs1_off);
+    hipStream_t st = (hipStream_t)stream;
+    double* B = (double*)work;
+    double* A = B + h->work_doubles;
+    const double gain = filter_gain();
+    // the passes of pn2_zoom_prefilter, each sample on its own lines: axis 0 lands in B as [gw][gh], axis 1 restores [gh][gw]
+    hipLaunchKernelGGL(ragged_causal_k<0>, dim3((unsigned)h->blocks0), dim3(64), 0, st, src, (const double*)nullptr, A, descs, bs0, h->N, ZP, gain);
+    PN2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ragged_anticausal_t_k<0>, dim3((unsigned)h->blocks0), dim3(64), 0, st, (const double*)A, B, descs, bs0, h->N, ZP);
+    PN2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ragged_causal_k<1>, dim3((unsigned)h->blocks1), dim3(64), 0, st, (const float*)nullptr, (const double*)B, A, descs, bs1, h->N, ZP, gain);
+    PN2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ragged_anticausal_t_k<1>, dim3((unsigned)h->blocks1), dim3(64), 0, st, (const double*)A, B, descs, bs1, h->N, ZP);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+int pn2_ragged_zoom3(const float* src, const void* plan_host, const void* plan_dev, const void* work, float* out, void* stream) {
+    if (!src || !plan_host || !plan_dev || !out) return -1;
+    const pn2_ragged_header* h = (const pn2_ragged_header*)plan_host;
+    if (!header_ok(h)) return -2;
+    if (h->blocks0 != 0 && !work) return -1;
+    const char* pd = (const char*)plan_dev;
+    hipLaunchKernelGGL(ragged_zoom3_k, dim3(ragged_grid_x(h), (unsigned)h->N), dim3(256), 0, (hipStream_t)stream, src, (const double*)work,
+                       (const pn2_ragged_desc*)(pd + h->desc_off), (const double*)(pd + h->tab_off), out);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+int pn2_ragged_zoom0(const unsigned char* src, const void* plan_host, const void* plan_dev, unsigned char* out, void* stream) {
+    if (!src || !plan_host || !plan_dev || !out) return -1;
+    const pn2_ragged_header* h = (const pn2_ragged_header*)plan_host;
+    if (!header_ok(h)) return -2;
+    const char* pd = (const char*)plan_dev;
+    hipLaunchKernelGGL(ragged_zoom0_k, dim3(ragged_grid_x(h), (unsigned)h->N), dim3(256), 0, (hipStream_t)stream, src, (const pn2_ragged_desc*)(pd + h->desc_off),
+                       (const double*)(pd + h->tab_off), out);
+    PN2_CHECK_LAUNCH();
+    return 0;
+}
+
+int pn2_ragged_dice_counts(const unsigned char* pred, const unsigned char* gt, const void* plan_host, const void* plan_dev, long long* counts, void* stream) {
+    if (!pred || !gt || !plan_host || !plan_dev || !counts) return -1;
+    const pn2_ragged_header* h = (const pn2_ragged_header*)plan_host;
+    if (!header_ok(h)) return -2;
+    hipLaunchKernelGGL(ragged_dice_k, dim3((unsigned)h->N), dim3(256), 0, (hipStream_t)stream, pred, gt,
+                       (const pn2_ragged_desc*)((const char*)plan_dev + h->desc_off), counts);
+    PN2_CHECK_LAUNCH();
+    return 0;
 }
 
 }  // extern "C"

@@ -127,6 +127,22 @@ class SegUpMap(C.Structure):
     _fields_ = [("p", C.c_void_p), ("ld", C.c_int), ("H", C.c_int), ("W", C.c_int)]
 
 
+class RaggedSample(C.Structure):          # pn2_ragged_sample
+    _fields_ = [(n, C.c_int) for n in ("H", "W", "oh", "ow", "geom", "k", "axis", "pad_")] + [("src_off", C.c_longlong), ("lab_off", C.c_longlong), ("m6", C.c_double * 6)]
+
+
+class RaggedDesc(C.Structure):          # pn2_ragged_desc
+    _fields_ = [(n, C.c_longlong) for n in ("src_off", "lab_off", "work_off", "out_off")] + \
+               [(n, C.c_int) for n in ("H", "W", "gh", "gw", "oh", "ow", "geom", "k", "axis", "copy", "ty3", "tx3", "ty0", "tx0")] + \
+               [("zn0", C.c_double), ("zn1", C.c_double), ("m6", C.c_double * 6)]
+
+
+class RaggedHeader(C.Structure):          # pn2_ragged_header
+    _fields_ = [(n, C.c_int) for n in ("magic", "N", "blocks0", "blocks1", "max_out", "uniform_out", "desc_off", "bs0_off", "bs1_off", "tab_off", "ntables", "pad_")] + \
+               [(n, C.c_longlong) for n in ("bytes", "work_doubles", "src_elems", "out_elems")]
+
+
+RAGGED_MAX_N = 4096
 P, I, LL, FL = C.c_void_p, C.c_int, C.c_longlong, C.c_float
 
 # name -> argtypes ; every function returns int (0 = ok)
@@ -302,6 +318,12 @@ SIGNATURES = {
     "pn2_zoom0": [I, P, I, I, I, I, I, P, P, P, P, P, P],
     "pn2_rotate0": [I, P, I, I, I, P, P, P],
     "pn2_rot_flip": [I, P, I, I, P, P, P],
+    "pn2_ragged_plan_bound": [I, P, C.POINTER(LL)],
+    "pn2_ragged_plan": [I, P, I, P, LL],
+    "pn2_ragged_prefilter": [P, P, P, P, P],
+    "pn2_ragged_zoom3": [P, P, P, P, P, P],
+    "pn2_ragged_zoom0": [P, P, P, P, P],
+    "pn2_ragged_dice_counts": [P, P, P, P, P, P],
 }
 # entry points that return a value rather than a status
 _VALUE_FUNCS = {"pn2_copy_job_blocks", "pn2_conv_gemm_tile", "pn2_conv_gemm_job_blocks", "pn2_bn_finalize_job_blocks", "pn2_affine_job_blocks", "pn2_bn_bwd_finalize_job_blocks",

@@ -200,6 +200,54 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], use_du
     return volume_metrics(pred, label, classes)
 
 
+def val_slices(images, labels, net_or_predictor, img_size, mode, batch_size=16):
+    """The val() loop of multiclass_seg/MIST/ACDC_train_test.py:48-93 over single slices of differing sizes: images a list of fp32 [x_i][y_i] slices, labels a list
+    of uint8 label maps of the same shapes (all host arrays or all GPU tensors).  Per batch of slices: the ragged spline zoom to img_size x img_size (a slice of that
+    size is not resampled, :59), the captured eval forward and label launch of a pn2.infer.VolumePredictor in one of its MODES (the reference sums P - P_bg over the
+    map pairs for a dual model, 'sum_fg_minus_bg', and its maps otherwise, 'sum_fg'), the order-0 zoom of the labels back to every slice's own size (:82-83) and the
+    three counts of medpy's binary dc(prediction, label) (:87), which treats every non-zero label as foreground.
+    Returns (per-slice Dice 2 I / (A + B) as float64 ndarray, 0.0 where A + B = 0; their mean, val()'s `performance`).  A net is wrapped in a VolumePredictor of its
+    own; pass a VolumePredictor (patch_size (img_size, img_size)) to keep its graphs between calls."""
+    import numpy as np
+    from . import volinput as V
+    from .infer import VolumePredictor
+    if mode not in MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(MODES)}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("pn2.voleval needs a GPU (no CPU fallback)")
+    images, labels = list(images), list(labels)
+    if not images or len(images) != len(labels):
+        raise ValueError("one label map per slice, at least one slice")
+    S = int(img_size)
+    vp = net_or_predictor if isinstance(net_or_predictor, VolumePredictor) else VolumePredictor(net_or_predictor, (S, S), batch_size)
+    if vp.patch_size != (S, S):
+        raise ValueError(f"the predictor's patch size {vp.patch_size} is not {(S, S)}")
+    B = vp.batch_size
+    counts = []
+    for i in range(0, len(images), B):
+        ims, gts = images[i:i + B], labels[i:i + B]
+        sizes = [tuple(int(a) for a in im.shape) for im in ims]
+        if any(tuple(g.shape) != s for g, s in zip(gts, sizes)):
+            raise ValueError("a label map whose shape differs from its slice's")
+        xb = V.zoom_ragged(ims, (S, S), 3)
+        n = xb.shape[0]
+        if n < B:          # one graph serves every batch: zero slices fill the last one (eval-mode BatchNorm keeps the samples independent)
+            xb = torch.cat([xb, xb.new_zeros((B - n, S, S))])
+        lab = vp._labels(xb[:, None], mode)["labels"][:n]
+        pred, _, plan = V._unzoom(lab, sizes)
+        gt, _, off, _keep = V._gather_slices(gts, torch.uint8, "labels")
+        if off is not None:          # GPU tensors of their own: packed in the order of the predictions
+            gt = torch.cat([g.reshape(-1) for g in _keep])
+        counts.append(V._dice_counts_dev(pred, gt, sizes, plan))
+    cnt = torch.cat(counts).cpu().numpy()          # one copy, after the last batch is queued
+    both = cnt[:, 1] + cnt[:, 2]
+    dice = np.where(both > 0, 2.0 * cnt[:, 0] / np.maximum(both, 1).astype(np.float64), 0.0)
+    dc_sum = 0
+    for v in dice:          # :87-88: summed slice by slice, in the loader's order
+        dc_sum += float(v)
+    return dice, dc_sum / len(dice)
+
+
 def val_single_volume(image, label, net, classes, patch_size=[256, 256], use_dual=False, batch_size=16):
     """utils.py:248-301: the in-training validation -> the list of Dice values for the classes 1 .. classes-1.  Dual models are combined as
     sum of (foreground - background) over the four map pairs, others take the last map."""

@@ -10,7 +10,7 @@ import random
 import numpy as np
 import torch
 
-from .capi import call
+from .capi import call, RaggedDesc, RaggedHeader, RaggedSample, RAGGED_MAX_N
 
 MAX_AXIS = 1024
 _TABLES = {}
@@ -179,3 +179,195 @@ class SliceTransform:
             images, labels = rotate(images, angles), rotate(labels, angles)
         images, labels = zoom(images, self.output_size, 3), zoom(labels, self.output_size, 0)
         return {"image": images[:, None].contiguous(), "label": labels.long()}
+
+
+# ------------------------------------------------------------------------------------------------ ragged batches: the ACDC slices, every one its own [H][W]
+# dataset_ACDC.py:13-48 (RandomGenerator on slices of any shape, np.rot90 swapping a non-square one) and MIST/ACDC_train_test.py:48-93 (val(): zoom in, net, order-0
+# zoom back to the slice's own size, one binary Dice per slice).  One host-built plan (pn2_ragged_plan: descriptors, block tables, per-axis tables) goes to the device in
+# one copy; the launches - 4 prefilter, 1 gather, 1 label - do not depend on N or on the shapes.  The uniform entry points above are untouched.
+class RaggedPlan:
+    """The blob of pn2_ragged_plan on the host (`host`, uint8 ndarray; `header`, `descs` are views of it) and, after to(dev), on the device (`dev`)."""
+
+    def __init__(self, samples, packed=True):
+        n = len(samples)
+        if not 1 <= n <= RAGGED_MAX_N:
+            raise ValueError(f"{n} samples: a ragged batch holds 1 .. {RAGGED_MAX_N}")
+        arr = (RaggedSample * n)(*samples)
+        nbytes = C.c_longlong(0)
+        call.pn2_ragged_plan_bound(n, arr, C.byref(nbytes))
+        buf = np.zeros(int(nbytes.value), np.uint8)
+        call.pn2_ragged_plan(n, arr, 1 if packed else 0, C.c_void_p(buf.ctypes.data), buf.size)
+        self.header = RaggedHeader.from_buffer(buf)
+        self.host = buf[:int(self.header.bytes)]
+        self.descs = (RaggedDesc * n).from_buffer(buf, self.header.desc_off)
+        self.n, self.dev = n, None
+
+    def block_starts(self):
+        h = self.header
+        return tuple(np.frombuffer(self.host, np.int32, self.n + 1, off).copy() for off in (h.bs0_off, h.bs1_off))
+
+    def to(self, dev):
+        self.dev = torch.from_numpy(self.host).to(dev)          # the one descriptor + table copy of the batch
+        return self
+
+    def hp(self):
+        return C.c_void_p(self.host.ctypes.data)
+
+
+def ragged_samples(shapes, sizes, draws=None, offsets=None):
+    """One RaggedSample per slice: shapes [(H, W)], sizes [(oh, ow)] (or one size for all), draws as SliceTransform takes them, offsets [(fp32 elements, bytes)]
+    relative to the launch's base pointers when the slices do not lie back to back.  Host code: no GPU needed."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    n = len(shapes)
+    sizes = list(sizes)
+    if len(sizes) == 2 and np.isscalar(sizes[0]):
+        sizes = [sizes] * n
+    draws = [None] * n if draws is None else list(draws)
+    if len(sizes) != n or len(draws) != n or (offsets is not None and len(offsets) != n):
+        raise ValueError("one size, one draw and one offset pair per slice")
+    out = []
+    for i, ((H, W), (oh, ow), d) in enumerate(zip(shapes, sizes, draws)):
+        if not all(1 <= int(a) <= MAX_AXIS for a in (H, W, oh, ow)):
+            raise ValueError(f"slice {i}: {(H, W)} -> {(int(oh), int(ow))}: every axis must be in 1 .. {MAX_AXIS}")
+        s = RaggedSample(H=H, W=W, oh=int(oh), ow=int(ow), axis=-1)
+        if d is not None:
+            if d[0] == "rot_flip" and len(d) == 3 and d[2] in (None, 0, 1):
+                s.geom, s.k, s.axis = 1, int(d[1]) % 4, -1 if d[2] is None else int(d[2])
+            elif d[0] == "rotate" and len(d) == 2:
+                s.geom = 2
+                s.m6[:] = _rotate_matrix(float(d[1]), H, W)
+            else:
+                raise ValueError("one draw per sample: ('rot_flip', k, axis), ('rotate', angle) or None")
+        if offsets is not None:
+            s.src_off, s.lab_off = int(offsets[i][0]), int(offsets[i][1])
+        out.append(s)
+    return out
+
+
+def _gather_slices(items, dtype, what):
+    """A list of [H][W] slices, all on the host (ndarrays / CPU tensors: packed into one buffer, ONE copy to the device) or all on the device (left where they are: the plan
+    addresses them relative to the lowest one) -> (base tensor, shapes, element offsets or None when packed, whatever must stay alive until the launches are queued)."""
+    items = list(items)
+    if not items:
+        raise ValueError("an empty batch")
+    ts = [torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a for a in items]
+    if any(not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != dtype for t in ts):
+        raise ValueError(f"{what}: a list of [H][W] {dtype} slices")
+    shapes = [tuple(t.shape) for t in ts]
+    if any(min(s) < 1 or max(s) > MAX_AXIS for s in shapes):
+        raise ValueError(f"{what}: every axis must be in 1 .. {MAX_AXIS}")
+    on_dev = [t.is_cuda for t in ts]
+    if not any(on_dev):
+        if not torch.cuda.is_available():
+            raise RuntimeError("pn2.volinput needs a GPU (no CPU fallback)")
+        flat = torch.cat([t.reshape(-1) for t in ts]) if len(ts) > 1 else ts[0].reshape(-1)
+        return flat.to("cuda"), shapes, None, None
+    if not all(on_dev):
+        raise ValueError(f"{what}: all slices on the host or all on the device")
+    ts = [t.contiguous() for t in ts]
+    base = min(ts, key=lambda t: t.data_ptr())
+    es = base.element_size()
+    return base, shapes, [(t.data_ptr() - base.data_ptr()) // es for t in ts], ts
+
+
+def _ragged_batch(images, labels, size, draws):
+    """The launches of one ragged batch: images and / or labels (lists, either may be None) -> (fp32 [N][oh][ow] or None, uint8 [N][oh][ow] or None)."""
+    oh, ow = int(size[0]), int(size[1])
+    img = lab = None
+    if images is not None:
+        img, shapes, ioff, keep_i = _gather_slices(images, torch.float32, "images")
+    if labels is not None:
+        lab, lshapes, loff, keep_l = _gather_slices(labels, torch.uint8, "labels")
+        if images is not None and (lshapes != shapes or (ioff is None) != (loff is None)):
+            raise ValueError("images and labels: one shape per sample, both on the host or both on the device")
+        shapes = lshapes
+    offsets = None
+    if (img is not None and ioff is not None) or (lab is not None and loff is not None):
+        n = len(shapes)
+        offsets = list(zip(ioff if img is not None else [0] * n, loff if lab is not None else [0] * n))
+    dev = (img if img is not None else lab).device
+    plan = RaggedPlan(ragged_samples(shapes, (oh, ow), draws, offsets), packed=offsets is None).to(dev)
+    st, N = _stream(), plan.n
+    out3 = out0 = None
+    if img is not None:
+        out3 = torch.empty((N, oh, ow), dtype=torch.float32, device=dev)
+        work = torch.empty(max(1, 2 * int(plan.header.work_doubles)), dtype=torch.float64, device=dev)
+        call.pn2_ragged_prefilter(_p(img), plan.hp(), _p(plan.dev), _p(work), st)
+        call.pn2_ragged_zoom3(_p(img), plan.hp(), _p(plan.dev), _p(work), _p(out3), st)
+    if lab is not None:
+        out0 = torch.empty((N, oh, ow), dtype=torch.uint8, device=dev)
+        call.pn2_ragged_zoom0(_p(lab), plan.hp(), _p(plan.dev), _p(out0), st)
+    return out3, out0
+
+
+def zoom_ragged(slices, size, order):
+    """scipy.ndimage.zoom(s, (oh / H_i, ow / W_i), order=order) of every slice of a list of [H_i][W_i] tensors or host arrays -> [N][oh][ow] on the device; a slice
+    already at (oh, ow) is copied, as the reference skips the call (ACDC_train_test.py:58-60).  order 3: fp32.  order 0: uint8."""
+    if order not in (0, 3):
+        raise ValueError("order 3 (image) or 0 (label)")
+    out3, out0 = _ragged_batch(slices if order == 3 else None, slices if order == 0 else None, size, None)
+    return out3 if order == 3 else out0
+
+
+def _unzoom(labels, sizes):
+    """uint8 [N][h][w] on the device -> (packed uint8 buffer, its [x_i][y_i] views, the plan whose out_off address the buffer)."""
+    _need_gpu(labels)
+    if labels.dim() != 3 or labels.dtype != torch.uint8:
+        raise ValueError("labels: uint8 [N][h][w]")
+    labels = labels.contiguous()
+    N, h, w = labels.shape
+    sizes = [(int(a), int(b)) for a, b in sizes]
+    if len(sizes) != N:
+        raise ValueError(f"{len(sizes)} sizes for {N} samples")
+    plan = RaggedPlan(ragged_samples([(h, w)] * N, [(s[0], s[1]) for s in sizes])).to(labels.device)
+    packed = torch.empty(int(plan.header.out_elems), dtype=torch.uint8, device=labels.device)
+    call.pn2_ragged_zoom0(_p(labels), plan.hp(), _p(plan.dev), _p(packed), _stream())
+    views = [packed[d.out_off:d.out_off + d.oh * d.ow].view(d.oh, d.ow) for d in plan.descs]
+    return packed, views, plan
+
+
+def unzoom_labels(labels, sizes):
+    """The way back of val() (ACDC_train_test.py:82-83): scipy.ndimage.zoom(labels[i], (x_i / h, y_i / w), order=0) of uniform uint8 labels [N][h][w], every sample to
+    its own size -> a list of [x_i][y_i] views of one packed buffer (one launch).  A sample already at its size is copied."""
+    return _unzoom(labels, sizes)[1]
+
+
+def dice_counts(pred, gt, sizes, plan=None):
+    """int64 ndarray [N][3] = |pred != 0 and gt != 0|, |pred != 0|, |gt != 0| per sample of two packed uint8 buffers holding [x_i][y_i] samples back to back
+    (one launch, one copy to the host): what medpy's dc(pred_i, gt_i) needs (ACDC_train_test.py:87)."""
+    return _dice_counts_dev(pred, gt, sizes, plan).cpu().numpy()
+
+
+def _dice_counts_dev(pred, gt, sizes, plan=None):
+    _need_gpu(pred, gt)
+    if plan is None:
+        plan = RaggedPlan(ragged_samples(sizes, sizes)).to(pred.device)
+    n = int(plan.header.out_elems)
+    if pred.dtype != torch.uint8 or gt.dtype != torch.uint8 or pred.numel() != n or gt.numel() != n or not pred.is_contiguous() or not gt.is_contiguous():
+        raise ValueError(f"pred and gt: contiguous uint8 buffers of {n} elements")
+    cnt = torch.empty((plan.n, 3), dtype=torch.int64, device=pred.device)
+    call.pn2_ragged_dice_counts(_p(pred), _p(gt), plan.hp(), _p(plan.dev), _p(cnt), _stream())
+    return cnt
+
+
+class RaggedSliceTransform:
+    """t = RaggedSliceTransform((224, 224)); batch = t(images, labels) with lists of fp32 [H_i][W_i] images and uint8 labels of the same shapes, square or not, all on the
+    host (one copy of the pixels, one of the labels) or all on the device -> {'image': fp32 [N][1][oh][ow], 'label': int64 [N][oh][ow]}: the batch the ACDC
+    RandomGenerator + DataLoader would collate (dataset_ACDC.py:30-48).  draws as SliceTransform takes them, from SliceTransform.draw (the ACDC file consumes the
+    generators in the Synapse file's order, :37-40 with :14,17,24).  np.rot90 with odd k swaps a sample's shape before the zoom; a sample at the output size after
+    its geometry is not zoomed (:42)."""
+
+    draw = staticmethod(SliceTransform.draw)
+
+    def __init__(self, output_size):
+        self.output_size = (int(output_size[0]), int(output_size[1]))
+        if not all(1 <= a <= MAX_AXIS for a in self.output_size):
+            raise ValueError(f"size {self.output_size}: every axis must be in 1 .. {MAX_AXIS}")
+
+    def __call__(self, images, labels, draws=None):
+        images, labels = list(images), list(labels)
+        if len(images) != len(labels):
+            raise ValueError("one label per image")
+        draws = self.draw(len(images)) if draws is None else list(draws)
+        image, label = _ragged_batch(images, labels, self.output_size, draws)
+        return {"image": image[:, None], "label": label.long()}
