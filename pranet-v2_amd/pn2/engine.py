@@ -5,6 +5,7 @@ pn2/ops_conv.py   packing, tuners, conv + BatchNorm ops (forward and backward): 
                   orchestrator over named steps with one per-call record, the one BatchNorm path (_bn_forward, _bn_backward_plain) and weight-gradient path (_wgrad)
 pn2/ops_encoder.py  PVTv2 / EMCAD ops
 pn2/ops_spatial.py  pooling, resampling, element-wise, DSRA ops
+pn2/ops_cascade.py  the CASCADE decoders' additive attention gate
 Everything importable from pn2.engine before the split still is (the switches live in pn2.core: patch them there)."""
 import ctypes as C
 import os
@@ -19,9 +20,10 @@ from .core import _p, _stream, _job_table, _thrash, _w4, _LinearAsConv, _PERMS, 
 from .ops_conv import ConvOps
 from .ops_encoder import EncoderOps
 from .ops_spatial import SpatialOps
+from .ops_cascade import CascadeOps
 
 
-class Engine(ConvOps, EncoderOps, SpatialOps):
+class Engine(ConvOps, EncoderOps, SpatialOps, CascadeOps):
     def __init__(self, dtype=BF16, training=True, grad_provider=None, need_grad=True, pack_cache=None, tuner=None, grad_queue=None, arena=None, lock_cache=None,
                  bn_fold=None):
         self.bn_fold = bn_fold          # BnFoldCache: eval-mode BatchNorm rows kept across forwards (the caller refreshes it once per forward); None = one prepare launch per layer

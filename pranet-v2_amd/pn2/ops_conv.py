@@ -295,6 +295,8 @@ class ConvOps:
         defer_out: the caller guarantees that the output is consumed ONLY as the `residual` of one later conv_bn_act (Bottle2neck's downsample branch).  A train-mode
                   BatchNorm output without activation is then not written: the returned Act carries the raw conv output and the BatchNorm's rows (Act.deferred), and the
                   consumer's output pass normalises both operands (pn2_affine_act_dual), behind ONE finalize launch for the two BatchNorms.  Bit-identical to the two passes.
+                  defer_out="biased": the same for a biased conv whose consumer is NOT a residual add but an op that finalizes the BatchNorm itself (_bn_forward with the record's
+                  bias) and reads raw + rows (CascadeOps.attention_gate).
         """
         assert tee is None or (self.training and bn is not None and bias is None and gate is None and sum_with is None), "tee: train-mode conv + BatchNorm outputs only"
         # pool: the op is conv -> BatchNorm -> ReLU -> MaxPool2d(3, 2, 1) and returns the POOLED activation; the full-resolution BatchNorm output is never written
@@ -338,7 +340,7 @@ class ConvOps:
             s.par = par_out if par_out is not None else self.fbuf(4, s.Cp)          # rows: scale, shift, mean, invstd
             assert tuple(s.par.shape) == (4, s.Cp) and s.par.stride(1) == 1
             s.defer = bool(defer_out and core.DUAL_AFFINE and s.train_bn and not relu and residual is None and out is None and sum_with is None and tee is None and not pool
-                           and gate is None and y_C is None and bias is None and y_dt in (None, self.dt) and not s.fuse_bias and s.Cp % s.V == 0 and s.raw_ld % s.V == 0)
+                           and gate is None and y_C is None and (bias is None or defer_out == "biased") and y_dt in (None, self.dt) and not s.fuse_bias and s.Cp % s.V == 0 and s.raw_ld % s.V == 0)
             if s.defer:             # neither finalized nor written here: the consumer does both (or _materialize)
                 s.scale, s.shift, s.mean, s.invstd = s.par[0], s.par[1], s.par[2], s.par[3]
             elif s.dual is not None:
