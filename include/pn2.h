@@ -763,7 +763,7 @@ int pn2_ragged_zoom3(const float* src, const void* plan_host, const void* plan_d
 int pn2_ragged_zoom0(const unsigned char* src, const void* plan_host, const void* plan_dev, unsigned char* out, void* stream);
 int pn2_ragged_dice_counts(const unsigned char* pred, const unsigned char* gt, const void* plan_host, const void* plan_dev, long long* counts, void* stream);
 
-/* ---------------------------------------------------------------------------------------------- CASCADE additive attention gate (csrc/pn2_cascade.hip)
+/* ---------------------------------------------------------------------------------------------- CASCADE attention gate, additive and concatenating (csrc/pn2_cascade.hip)
  * g1 = BN_g(W_g g), x1 = BN_x(W_x x), psi = sigmoid(BN_psi(w_psi . relu(g1 + x1) + b_psi)), out = g + x * psi   (MIST/lib/decoders.py Attention_block + "aggregate").
  * The 1x1 convs and their statistics are pn2_conv_gemm + pn2_bn_finalize; these entry points take the RAW conv outputs [M][F_int_p] (dt storage, 16-byte rows) with
  * their fp32 (scale, shift) rows - both null: the operand already is the BatchNorm output - so relu(g1 + x1) is never stored.  w_psi: the F_int fp32 weights.
@@ -776,6 +776,10 @@ int pn2_ragged_dice_counts(const unsigned char* pred, const unsigned char* gt, c
  *   pn2_bn_bwd_finalize (mean / invstd null: eval mode, p2 = 0).
  * pn2_ag_bwd_sum: dpsi_raw = coef[0] (dz - coef[1] - xhat coef[2]) with the finalize's rows (coef null: a[0] * dz); dsum[m][c] = dpsi_raw w_psi[c] [relu(...) > 0], the
  *   gradient of BOTH BatchNorm outputs; pw[blk][F_int_p] / pb[blk]: partial rows of dw_psi / db_psi for pn2_colsum_finalize.
+ * pn2_ag_apply_cat_fwd / pn2_ag_bwd_gate_cat: the same two steps for the concatenating decoder (CASCADE_Cat: cat(x * psi, g)), behind the same pn2_ag_psi_fwd and in front of the
+ *   same pn2_ag_bwd_sum.  out / dout: rows of 2 C (ld >= 2 C).  out[m][0:C] = x * psi, out[m][C:2C] = g (bit for bit); dx (+)= dout[:, 0:C] * psi, dg (+)= dout[:, C:2C],
+ *   dz[m] = psi (1 - psi) sum_{c < C} dout x; p1 / p2 as pn2_ag_bwd_gate: pn2_ag_blocks(dt, M, C, 1) rows.  C % 8 == 0 and Cp == C (no pad lanes, the second half 16-byte
+ *   aligned in both storage types), anything else: -2 before any launch.
  * Fixed summation order, no atomics.  -1: null argument, -2: unsupported geometry (widths not padded to 8, rows not 16-byte aligned, F_int_p above 64 vectors). */
 int pn2_ag_blocks(int dt, int M, int width_p, int kind);
 int pn2_ag_psi_rows(int dt, int M, int F_int_p);
@@ -785,6 +789,10 @@ int pn2_ag_apply_fwd(int dt, const void* g, int ld_g, const void* x, int ld_x, c
                      int M, int C, int Cp, void* stream);
 int pn2_ag_bwd_gate(int dt, const void* dout, int ld_dout, const void* x, int ld_x, const float* psi_raw, const float* a, const float* b, const float* mean, const float* invstd,
                     void* dx, int ld_dx, int dx_accum, void* dg, int ld_dg, int dg_accum, float* dz, float* p1, float* p2, int M, int C, int Cp, void* stream);
+int pn2_ag_apply_cat_fwd(int dt, const void* g, int ld_g, const void* x, int ld_x, const float* psi_raw, const float* a, const float* b, void* out, int ld_out,
+                         int M, int C, int Cp, void* stream);
+int pn2_ag_bwd_gate_cat(int dt, const void* dout, int ld_dout, const void* x, int ld_x, const float* psi_raw, const float* a, const float* b, const float* mean, const float* invstd,
+                        void* dx, int ld_dx, int dx_accum, void* dg, int ld_dg, int dg_accum, float* dz, float* p1, float* p2, int M, int C, int Cp, void* stream);
 int pn2_ag_bwd_sum(int dt, const float* dz, const float* psi_raw, const float* a, const float* mean, const float* invstd, const float* coef,
                    const void* raw_g, int ld_g, const float* scale_g, const float* shift_g, const void* raw_x, int ld_x, const float* scale_x, const float* shift_x,
                    const float* w_psi, int F_int, int F_int_p, int M, void* dsum, int ld_dsum, float* pw, float* pb, void* stream);

@@ -1,10 +1,12 @@
-// pn2_cascade.hip — the additive attention gate of the CASCADE decoders (Attention_block + the "aggregate" line behind it):
-//   g1 = BN_g(W_g g)   x1 = BN_x(W_x x)   psi = sigmoid(BN_psi(w_psi . relu(g1 + x1) + b_psi))   out = g + x * psi
+// pn2_cascade.hip — the attention gate of the CASCADE decoders (Attention_block + the "aggregate" / "Concat" line behind it):
+//   g1 = BN_g(W_g g)   x1 = BN_x(W_x x)   psi = sigmoid(BN_psi(w_psi . relu(g1 + x1) + b_psi))   out = g + x * psi (CASCADE_Add*)  or  cat(x * psi, g) (CASCADE_Cat)
 // The two 1x1 convs and their BatchNorm statistics stay on the conv / pn2_bn_* kernels; what is here starts from the RAW conv outputs [M][Fp] and their
 // (scale, shift) rows, so the F_int-wide relu(g1 + x1) only ever exists in registers:
 //   ag_psi_fwd_k     psi_raw[m] = sum_c w_psi[c] * relu(fma(rg, sg, hg) + fma(rx, sx, hx)) + per-block (mean, M2) of psi_raw for pn2_bn_finalize (tile form)
 //   ag_apply_fwd_k   out = g + x * sigmoid(a * psi_raw + b)
 //   ag_bwd_gate_k    dx (+)= dout * psi, dg (+)= dout, dz[m] = psi (1 - psi) sum_c dout * x, per-block sums of dz and dz * xhat for pn2_bn_bwd_finalize
+//   ag_apply_cat_fwd_k    out[m][0:C] = x * sigmoid(a * psi_raw + b), out[m][C:2C] = g: rows of 2C from one read of g and x (C % 8 == 0: no pad lanes, both halves 16-byte aligned)
+//   ag_bwd_gate_cat_k     ag_bwd_gate_k on a dout row of 2C: dx (+)= dout[:, 0:C] * psi, dg (+)= dout[:, C:2C], dz and the block sums from the left half only
 //   ag_bwd_sum_k     dpsi_raw from dz and the finalize's coefficients; dsum[m][c] = dpsi_raw * w_psi[c] * [relu' > 0] (ONE tensor: the gradient of both BatchNorm outputs),
 //                    per-block rows of dw_psi = sum_m dpsi_raw * relu(...) and of db_psi = sum_m dpsi_raw for pn2_colsum_finalize
 // Row walks: 256 threads = CVP channel vectors x R row lanes, 16-byte loads.  Every sum runs in a fixed order (butterflies, then LDS rows in index order): no atomics,
@@ -192,6 +194,83 @@ __global__ __launch_bounds__(256) void ag_bwd_gate_k(const T* __restrict__ dout,
     if (threadIdx.x == 0) { p1[blockIdx.x] = a1; p2[blockIdx.x] = a2; }
 }
 
+// cat(x * psi, g): one thread per channel vector of the C-wide operands, two stores (C % 8 == 0: Cp == C, the right half starts on a 16-byte boundary)
+template <typename T>
+__global__ __launch_bounds__(256) void ag_apply_cat_fwd_k(const T* __restrict__ g, int ld_g, const T* __restrict__ x, int ld_x, const float* __restrict__ psi,
+                                                          const float* __restrict__ a, const float* __restrict__ b, T* __restrict__ out, int ld_o, int M, int C) {
+    constexpr int V = TT<T>::VEC;
+    const int CV = C / V;
+    const size_t total = (size_t)M * CV;
+    const float ka = a[0], kb = b[0];
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        int cv; const size_t m = divmod_idx(idx, CV, cv);
+        const int c = cv * V;
+        const uint4 gv = *reinterpret_cast<const uint4*>(g + m * ld_g + c);          // (copied as it is: the right half equals g bit for bit)
+        float xv[V], o[V];
+        ldv<T>(x + m * ld_x + c, xv);
+        const float s = sigmoidf_(fmaf(psi[m], ka, kb));
+#pragma unroll
+        for (int e = 0; e < V; ++e) o[e] = xv[e] * s;
+        stv<T>(out + m * ld_o + c, o);
+        *reinterpret_cast<uint4*>(out + m * ld_o + C + c) = gv;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ag_bwd_gate_cat_k(const T* __restrict__ dout, int ld_do, const T* __restrict__ x, int ld_x, const float* __restrict__ psi,
+                                                         const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                         T* __restrict__ dx, int ld_dx, int dx_acc, T* __restrict__ dg, int ld_dg, int dg_acc,
+                                                         float* __restrict__ dz, float* __restrict__ p1, float* __restrict__ p2, int M, int C, int rows, int CVP) {
+    constexpr int V = TT<T>::VEC;
+    __shared__ float red[4];
+    const int CV = C / V, R = 256 / CVP, cvl = threadIdx.x % CVP, rl = threadIdx.x / CVP;
+    const int r0 = blockIdx.x * rows;
+    int r1 = r0 + rows; if (r1 > M) r1 = M;
+    const float ka = a[0], kb = b[0], mu = mean ? mean[0] : 0.f, is = mean ? invstd[0] : 0.f;
+    float a1 = 0.f, a2 = 0.f;
+    for (int mb = r0; mb < r1; mb += R) {          // (uniform trip count, as in ag_psi_fwd_k)
+        const int m = mb + rl;
+        const bool valid = m < r1;
+        float pr = 0.f, s = 0.f, t = 0.f;
+        if (valid) {
+            pr = psi[m]; s = sigmoidf_(fmaf(pr, ka, kb));
+            for (int cv = cvl; cv < CV; cv += CVP) {
+                const int c = cv * V;
+                float d[V], xv[V], o[V];
+                const uint4 dr = *reinterpret_cast<const uint4*>(dout + (size_t)m * ld_do + C + c);          // the right half: g's gradient as it is
+                ldv<T>(dout + (size_t)m * ld_do + c, d); ldv<T>(x + (size_t)m * ld_x + c, xv);
+#pragma unroll
+                for (int e = 0; e < V; ++e) t = fmaf(d[e], xv[e], t);
+                if (dx) {
+                    if (dx_acc) ldv<T>(dx + (size_t)m * ld_dx + c, o);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) o[e] = dx_acc ? fmaf(d[e], s, o[e]) : d[e] * s;
+                    stv<T>(dx + (size_t)m * ld_dx + c, o);
+                }
+                if (dg) {
+                    if (dg_acc) {
+                        TT<T>::unpack(dr, d); ldv<T>(dg + (size_t)m * ld_dg + c, o);
+#pragma unroll
+                        for (int e = 0; e < V; ++e) d[e] += o[e];
+                        stv<T>(dg + (size_t)m * ld_dg + c, d);
+                    } else {
+                        *reinterpret_cast<uint4*>(dg + (size_t)m * ld_dg + c) = dr;
+                    }
+                }
+            }
+        }
+        for (int off = CVP >> 1; off > 0; off >>= 1) t += __shfl_xor(t, off);
+        if (valid && cvl == 0) {
+            const float z = t * s * (1.f - s);
+            dz[m] = z;
+            a1 += z; a2 = fmaf(z, (pr - mu) * is, a2);
+        }
+    }
+    a1 = block_sum(a1, red);
+    a2 = block_sum(a2, red);
+    if (threadIdx.x == 0) { p1[blockIdx.x] = a1; p2[blockIdx.x] = a2; }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void ag_bwd_sum_k(const float* __restrict__ dz, const float* __restrict__ psi, const float* __restrict__ a, const float* __restrict__ mean,
                                                     const float* __restrict__ invstd, const float* __restrict__ coef,
@@ -315,6 +394,32 @@ int pn2_ag_bwd_gate(int dt, const void* dout, int ld_dout, const void* x, int ld
         using T = type_of<decltype(t)>;
         return pn2_launch<ag_bwd_gate_k<T>>(dim3(p.nblk), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dout, ld_dout, (const T*)x, ld_x, psi_raw, a, b, mean, invstd,
                                             (T*)dx, ld_dx, dx_accum, (T*)dg, ld_dg, dg_accum, dz, p1, p2, M, C, Cp, p.rows, p.cvp);
+    });
+}
+
+int pn2_ag_apply_cat_fwd(int dt, const void* g, int ld_g, const void* x, int ld_x, const float* psi_raw, const float* a, const float* b, void* out, int ld_out,
+                         int M, int C, int Cp, void* stream) {
+    if (!g || !x || !psi_raw || !a || !b || !out) return -1;
+    const int V = vec_of(dt);
+    if (M < 1 || C < 8 || C % 8 || Cp != C || ld_g < C || ld_x < C || ld_out < 2 * C || ld_g % V || ld_x % V || ld_out % V || !al16(g) || !al16(x) || !al16(out)) return -2;
+    return with_storage_dtype(dt, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        return pn2_launch<ag_apply_cat_fwd_k<T>>(dim3(grid_for((size_t)M * (C / V), GRID_CAP)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)g, ld_g, (const T*)x, ld_x, psi_raw, a, b,
+                                                 (T*)out, ld_out, M, C);
+    });
+}
+
+int pn2_ag_bwd_gate_cat(int dt, const void* dout, int ld_dout, const void* x, int ld_x, const float* psi_raw, const float* a, const float* b, const float* mean, const float* invstd,
+                        void* dx, int ld_dx, int dx_accum, void* dg, int ld_dg, int dg_accum, float* dz, float* p1, float* p2, int M, int C, int Cp, void* stream) {
+    if (!dout || !x || !psi_raw || !a || !b || !dz || !p1 || !p2 || (mean == nullptr) != (invstd == nullptr)) return -1;
+    const int V = vec_of(dt);
+    if (M < 1 || C < 8 || C % 8 || Cp != C || ld_dout < 2 * C || ld_x < C || ld_dout % V || ld_x % V || !al16(dout) || !al16(x)) return -2;
+    if ((dx && (ld_dx < C || ld_dx % V || !al16(dx))) || (dg && (ld_dg < C || ld_dg % V || !al16(dg)))) return -2;
+    const AgPlan p = ag_plan_kind(dt, M, C, 1);          // (the plan of pn2_ag_bwd_gate at this width: p1 / p2 hold pn2_ag_blocks(dt, M, C, 1) rows)
+    return with_storage_dtype(dt, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        return pn2_launch<ag_bwd_gate_cat_k<T>>(dim3(p.nblk), dim3(256), 0, 0, (hipStream_t)stream, (const T*)dout, ld_dout, (const T*)x, ld_x, psi_raw, a, b, mean, invstd,
+                                                (T*)dx, ld_dx, dx_accum, (T*)dg, ld_dg, dg_accum, dz, p1, p2, M, C, p.rows, p.cvp);
     });
 }
 

@@ -1,12 +1,14 @@
-"""CASCADE decoders, plain and dual-supervised (reference: multiclass_seg/MIST/lib/decoders.py:20-119,202-431; MERIT's copy is the same text) on the gfx950 kernels.
+"""CASCADE decoders - concatenating, additive and dual-supervised (reference: multiclass_seg/MIST/lib/decoders.py:20-431; MERIT's copy is the same text) on the gfx950 kernels.
 
 Same class names, constructor signatures, parameter names (state_dict keys and order) and default initialisation as the reference; the computation is expressed in
 engine ops, as in lib/decoders.py: the biased 3x3 / 1x1 convs on the implicit-GEMM kernels with BatchNorm on pn2_bn_*, nearest x2 up-sampling, the channel and
-spatial attention of the CAM blocks on the pooling and gating kernels of csrc/pn2_emcad.hip, the DSRA fusion on pn2_dsra_fuse, and the additive attention gate
-together with the aggregation behind it on csrc/pn2_cascade.hip (Engine.attention_gate).  No PyTorch fallback: forward needs the GPU library.
+spatial attention of the CAM blocks on the pooling and gating kernels of csrc/pn2_emcad.hip, the DSRA fusion on pn2_dsra_fuse, and the attention gate together with
+the aggregation behind it on csrc/pn2_cascade.hip: g + x * psi (Engine.attention_gate) or cat(x * psi, g) (Engine.attention_gate_cat), each written by one launch.
+No PyTorch fallback: forward needs the GPU library.
 
-Built: CASCADE_Add and CASCADE_Add_dual (both use_softmax values).  Not built: CASCADE_Cat.  The reference's ChannelAttention divides its width by 16 whatever the width,
-so a stage needs at least 16 channels there; the same holds here."""
+Built: CASCADE_Cat, CASCADE_Add and CASCADE_Add_dual (both use_softmax values).  The reference's ChannelAttention divides its width by 16 whatever the width, so a stage
+needs at least 16 channels there; the same holds here.  CASCADE_Cat's gated stages need widths that are a multiple of 8 (every reference width is): the two halves of a
+concatenated row then both start on a 16-byte boundary."""
 import torch
 import torch.nn as nn
 
@@ -48,7 +50,8 @@ class up_conv(nn.Module):
 
 
 class Attention_block(nn.Module):
-    """Additive attention gate (:52-79).  _build_aggregate returns g + x * psi: the gate and the "aggregate" line that follows every one of its uses, in one op."""
+    """Additive attention gate (:52-79).  _build_aggregate returns g + x * psi, _build_concat cat(x * psi, g): the gate and the "aggregate" / "Concat" line that follows
+    every one of its uses, in one op."""
 
     def __init__(self, F_g, F_l, F_int):
         super().__init__()
@@ -57,13 +60,21 @@ class Attention_block(nn.Module):
         self.psi = nn.Sequential(nn.Conv2d(F_int, 1, kernel_size=1, stride=1, padding=0, bias=True), nn.BatchNorm2d(1), nn.Sigmoid())
         self.relu = nn.ReLU(inplace=True)
 
-    def _build_aggregate(self, eng, g, x):
+    def _check(self, g, x):
         if g.C != x.C:
             raise NotImplementedError("Attention_block with F_g != F_l is not built: the fused gate adds x * psi to g (every CASCADE decoder uses one width)")
         if self.psi[0].in_channels > 256:
             raise NotImplementedError("Attention_block with F_int above 256 is not built (the gate kernels take at most 64 fp32 channel vectors)")
+
+    def _build_aggregate(self, eng, g, x):
+        self._check(g, x)
         return eng.attention_gate(g, x, self.W_g[0], self.W_g[1], self.W_x[0], self.W_x[1], self.psi[0], self.psi[1])
 
+    def _build_concat(self, eng, g, x):
+        self._check(g, x)
+        if g.C % 8:
+            raise NotImplementedError(f"Attention_block behind a concatenation needs a width that is a multiple of 8, not {g.C} (the halves of a row are 16-byte vectors)")
+        return eng.attention_gate_cat(g, x, self.W_g[0], self.W_g[1], self.W_x[0], self.W_x[1], self.psi[0], self.psi[1])
 
     def forward(self, g, x):
         """x * psi, as the reference returns it: the fused op's g + x * psi minus g"""
@@ -120,9 +131,10 @@ class SpatialAttention(nn.Module):
 
 
 class _CascadeStages(nn.Module):
-    """What CASCADE_Add and CASCADE_Add_dual share; with a `num_class` the dual-supervised fg / bg heads are registered in the reference's order (behind each stage's ConvBlock)."""
+    """What the CASCADE decoders share; with a `num_class` the dual-supervised fg / bg heads are registered in the reference's order (behind each stage's ConvBlock).
+    `width`: how many times the stage width the CAM of a gated stage is wide (2: the gate's output is concatenated with the up-sampled map, CASCADE_Cat)."""
 
-    def _register_stages(self, channels, num_class=None):
+    def _register_stages(self, channels, num_class=None, width=1):
         c = channels
         self.Conv_1x1 = nn.Conv2d(c[0], c[0], kernel_size=1, stride=1, padding=0)
         self.ConvBlock4 = conv_block(ch_in=c[0], ch_out=c[0])
@@ -130,10 +142,10 @@ class _CascadeStages(nn.Module):
         for i, lvl in ((1, 3), (2, 2), (3, 1)):
             setattr(self, f"Up{lvl}", up_conv(ch_in=c[i - 1], ch_out=c[i]))
             setattr(self, f"AG{lvl}", Attention_block(F_g=c[i], F_l=c[i], F_int=c[i + 1] if lvl > 1 else int(c[3] / 2)))
-            setattr(self, f"ConvBlock{lvl}", conv_block(ch_in=c[i], ch_out=c[i]))
+            setattr(self, f"ConvBlock{lvl}", conv_block(ch_in=width * c[i], ch_out=c[i]))
             self._register_heads(lvl, c[i], num_class)
         for i, lvl in enumerate((4, 3, 2, 1)):
-            setattr(self, f"CA{lvl}", ChannelAttention(c[i]))
+            setattr(self, f"CA{lvl}", ChannelAttention(c[i] if lvl == 4 else width * c[i]))
         self.SA = SpatialAttention()
 
     def _register_heads(self, lvl, ch, num_class):
@@ -148,14 +160,35 @@ class _CascadeStages(nn.Module):
         d = self.SA._build_gated(eng, d)
         return getattr(self, f"ConvBlock{lvl}")._build(eng, d)
 
-    def _gated_cam(self, eng, d, lvl, skip):
-        return self._cam(eng, getattr(self, f"AG{lvl}")._build_aggregate(eng, d, skip), lvl)
+    def _gated_cam(self, eng, d, lvl, skip, concat=False):
+        ag = getattr(self, f"AG{lvl}")
+        return self._cam(eng, ag._build_concat(eng, d, skip) if concat else ag._build_aggregate(eng, d, skip), lvl)
+
+    def _build_stages(self, eng, x, skips, concat):
+        """the four CAM stages without heads -> [d4, d3, d2, d1]"""
+        d = self._cam(eng, eng.conv_bias(x, self.Conv_1x1), 4)
+        ds = [d]
+        for lvl, skip in ((3, skips[0]), (2, skips[1]), (1, skips[2])):
+            d = self._gated_cam(eng, getattr(self, f"Up{lvl}")._build(eng, d), lvl, skip, concat)
+            ds.append(d)
+        return ds
 
     def _params(self):
         return list(self.parameters())
 
     def forward(self, x, skips):
         return run_module(lambda eng, x_, *s: self._build(eng, x_, list(s)), [x, *skips], self._params(), self.training)
+
+
+class CASCADE_Cat(_CascadeStages):
+    """CASCADE decoder with concatenating aggregation (:121-199): (d4, d3, d2, d1).  cat(AG(g, x), g) feeds a CAM of twice the stage width."""
+
+    def __init__(self, channels=[512, 320, 128, 64]):
+        super().__init__()
+        self._register_stages(channels, width=2)
+
+    def _build(self, eng, x, skips):
+        return self._build_stages(eng, x, skips, True)
 
 
 class CASCADE_Add(_CascadeStages):
@@ -166,12 +199,7 @@ class CASCADE_Add(_CascadeStages):
         self._register_stages(channels)
 
     def _build(self, eng, x, skips):
-        d = self._cam(eng, eng.conv_bias(x, self.Conv_1x1), 4)
-        ds = [d]
-        for lvl, skip in ((3, skips[0]), (2, skips[1]), (1, skips[2])):
-            d = self._gated_cam(eng, getattr(self, f"Up{lvl}")._build(eng, d), lvl, skip)
-            ds.append(d)
-        return ds
+        return self._build_stages(eng, x, skips, False)
 
 
 class CASCADE_Add_dual(_CascadeStages):

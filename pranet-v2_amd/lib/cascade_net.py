@@ -1,5 +1,6 @@
 """PVT_CASCADE: EMCADNet's wrapper (lib/networks.py) around the CASCADE decoder (lib/cascade.py) - a PVTv2 encoder, CASCADE_Add_dual (dual=True: 8 K-class maps) or
-CASCADE_Add + four out_head convs (dual=False: 4 maps), bilinear up-sampling by 32 / 16 / 8 / 4.
+CASCADE_Add / CASCADE_Cat + four out_head convs (dual=False: 4 maps; aggregation='additive' / 'concatenation', the reference networks' decoder_aggregation switch), bilinear
+up-sampling by 32 / 16 / 8 / 4.  The reference has no dual-supervised concatenating decoder: every class that takes CASCADE_Cat puts plain heads behind it.
 
 The reference pairs this decoder with MaxViT encoders (MIST_CAM, MERIT_*), which are not built here; it has no class of this name.  Parity for this class is therefore
 against the composition of reference pieces (the PVTv2 encoder of multiclass_seg/EMCAD/lib/pvtv2.py, the decoder of MIST/lib/decoders.py, EMCADNet's input conv and
@@ -13,13 +14,18 @@ import torch.nn as nn
 from pn2 import F32
 from pn2.graph import run_module
 from lib import pvtv2
-from lib.cascade import CASCADE_Add, CASCADE_Add_dual
+from lib.cascade import CASCADE_Add, CASCADE_Add_dual, CASCADE_Cat
 
 
 class PVT_CASCADE(nn.Module):
-    def __init__(self, num_classes=1, encoder='pvt_v2_b2', dual=True, pretrain=True, use_softmax=True):
+    def __init__(self, num_classes=1, encoder='pvt_v2_b2', dual=True, pretrain=True, use_softmax=True, aggregation='additive'):
         super().__init__()
+        if aggregation not in ('additive', 'concatenation'):
+            raise ValueError(f"aggregation {aggregation!r}: 'additive' or 'concatenation'")
+        if aggregation == 'concatenation' and dual:
+            raise ValueError("aggregation='concatenation' needs dual=False: the concatenating decoder has no dual-supervised heads")
         self.dual = dual
+        self.aggregation = aggregation
         self.conv = nn.Sequential(nn.Conv2d(1, 3, kernel_size=1), nn.BatchNorm2d(3), nn.ReLU(inplace=True))
         if encoder not in ('pvt_v2_b0', 'pvt_v2_b1', 'pvt_v2_b2', 'pvt_v2_b3', 'pvt_v2_b4', 'pvt_v2_b5'):
             raise NotImplementedError(f"encoder {encoder}: only the PVTv2 encoders are built")
@@ -31,7 +37,10 @@ class PVT_CASCADE(nn.Module):
             model_dict = self.backbone.state_dict()
             model_dict.update({k: v for k, v in save_model.items() if k in model_dict.keys()})
             self.backbone.load_state_dict(model_dict)
-        self.decoder = CASCADE_Add_dual(channels=channels, num_class=num_classes, use_softmax=use_softmax) if dual else CASCADE_Add(channels=channels)
+        if dual:
+            self.decoder = CASCADE_Add_dual(channels=channels, num_class=num_classes, use_softmax=use_softmax)
+        else:
+            self.decoder = (CASCADE_Cat if aggregation == 'concatenation' else CASCADE_Add)(channels=channels)
         self.out_head4 = nn.Conv2d(channels[0], num_classes, 1)
         self.out_head3 = nn.Conv2d(channels[1], num_classes, 1)
         self.out_head2 = nn.Conv2d(channels[2], num_classes, 1)

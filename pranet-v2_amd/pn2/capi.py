@@ -329,6 +329,8 @@ SIGNATURES = {
     "pn2_ag_psi_fwd": [I, P, I, P, P, P, I, P, P, P, I, I, I, P, P, P, P],
     "pn2_ag_apply_fwd": [I, P, I, P, I, P, P, P, P, I, I, I, I, P],
     "pn2_ag_bwd_gate": [I, P, I, P, I, P, P, P, P, P, P, I, I, P, I, I, P, P, P, I, I, I, P],
+    "pn2_ag_apply_cat_fwd": [I, P, I, P, I, P, P, P, P, I, I, I, I, P],
+    "pn2_ag_bwd_gate_cat": [I, P, I, P, I, P, P, P, P, P, P, I, I, P, I, I, P, P, P, I, I, I, P],
     "pn2_ag_bwd_sum": [I, P, P, P, P, P, P, P, I, P, P, P, I, P, P, P, I, I, I, P, I, P, P, P],
 }
 # entry points that return a value rather than a status

@@ -5,7 +5,7 @@ pn2/ops_conv.py   packing, tuners, conv + BatchNorm ops (forward and backward): 
                   orchestrator over named steps with one per-call record, the one BatchNorm path (_bn_forward, _bn_backward_plain) and weight-gradient path (_wgrad)
 pn2/ops_encoder.py  PVTv2 / EMCAD ops
 pn2/ops_spatial.py  pooling, resampling, element-wise, DSRA ops
-pn2/ops_cascade.py  the CASCADE decoders' additive attention gate
+pn2/ops_cascade.py  the CASCADE decoders' attention gate, additive and concatenating
 Everything importable from pn2.engine before the split still is (the switches live in pn2.core: patch them there)."""
 import ctypes as C
 import os
