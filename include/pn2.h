@@ -797,6 +797,17 @@ int pn2_ag_bwd_sum(int dt, const float* dz, const float* psi_raw, const float* a
                    const void* raw_g, int ld_g, const float* scale_g, const float* shift_g, const void* raw_x, int ld_x, const float* scale_x, const float* shift_x,
                    const float* w_psi, int F_int, int F_int_p, int M, void* dsum, int ld_dsum, float* pw, float* pb, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- strided skip of the ResNet stage-opening blocks (csrc/pn2_resnet.hip)
+ * downsample = Conv2d(1x1, stride 2, pad 0) + BatchNorm (EMCAD/lib/resnet.py:141-148) as a strided gather in front of the stride-1 pointwise conv path.  NHWC, bf16 / fp32,
+ * 16-byte vectors: C and both ld multiples of the vector, ld >= C (channel slices of wider rows; the columns past C are never touched), pointers 16-byte aligned.
+ * pn2_subsample_fwd: y[n][oh][ow][:] = x[n][oh*stride][ow*stride][:], OH = (H-1)/stride + 1, OW = (W-1)/stride + 1 - what a pad-0 1x1 conv of that stride reads.
+ * pn2_subsample_bwd: the adjoint over the whole of dx [N][H][W] in one pass.  accum = 0: the strided pixels take dy, every other pixel zero; accum = 1: the strided pixels
+ *   take dx + dy (rounded once to the storage type), the others are neither read nor written.  One writer per element, no atomics: bit-identical replays.
+ * stride 2; stride 1 is forwarded to pn2_copy.  -1: null argument, -2: unsupported geometry (any other stride, widths or rows off the vector, N*H*W beyond 2^31 - 1,
+ * accum not 0 / 1), -3: unknown dtype - all decided on the host before any launch. */
+int pn2_subsample_fwd(int dt, const void* x, int ld_x, void* y, int ld_y, int N, int H, int W, int C, int stride, void* stream);
+int pn2_subsample_bwd(int dt, const void* dy, int ld_dy, void* dx, int ld_dx, int N, int H, int W, int C, int stride, int accum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

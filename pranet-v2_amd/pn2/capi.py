@@ -332,6 +332,8 @@ SIGNATURES = {
     "pn2_ag_apply_cat_fwd": [I, P, I, P, I, P, P, P, P, I, I, I, I, P],
     "pn2_ag_bwd_gate_cat": [I, P, I, P, I, P, P, P, P, P, P, I, I, P, I, I, P, P, P, I, I, I, P],
     "pn2_ag_bwd_sum": [I, P, P, P, P, P, P, P, I, P, P, P, I, P, P, P, I, I, I, P, I, P, P, P],
+    "pn2_subsample_fwd": [I, P, I, P, I, I, I, I, I, I, P],
+    "pn2_subsample_bwd": [I, P, I, P, I, I, I, I, I, I, I, P],
 }
 # entry points that return a value rather than a status
 _VALUE_FUNCS = {"pn2_copy_job_blocks", "pn2_conv_gemm_tile", "pn2_conv_gemm_job_blocks", "pn2_bn_finalize_job_blocks", "pn2_affine_job_blocks", "pn2_bn_bwd_finalize_job_blocks",

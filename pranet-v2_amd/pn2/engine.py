@@ -6,6 +6,7 @@ pn2/ops_conv.py   packing, tuners, conv + BatchNorm ops (forward and backward): 
 pn2/ops_encoder.py  PVTv2 / EMCAD ops
 pn2/ops_spatial.py  pooling, resampling, element-wise, DSRA ops
 pn2/ops_cascade.py  the CASCADE decoders' attention gate, additive and concatenating
+pn2/ops_resnet.py   the strided skip of the ResNet stage-opening blocks: subsample, strided_pointwise
 Everything importable from pn2.engine before the split still is (the switches live in pn2.core: patch them there)."""
 import ctypes as C
 import os
@@ -21,9 +22,10 @@ from .ops_conv import ConvOps
 from .ops_encoder import EncoderOps
 from .ops_spatial import SpatialOps
 from .ops_cascade import CascadeOps
+from .ops_resnet import ResNetOps
 
 
-class Engine(ConvOps, EncoderOps, SpatialOps, CascadeOps):
+class Engine(ConvOps, EncoderOps, SpatialOps, CascadeOps, ResNetOps):
     def __init__(self, dtype=BF16, training=True, grad_provider=None, need_grad=True, pack_cache=None, tuner=None, grad_queue=None, arena=None, lock_cache=None,
                  bn_fold=None):
         self.bn_fold = bn_fold          # BnFoldCache: eval-mode BatchNorm rows kept across forwards (the caller refreshes it once per forward); None = one prepare launch per layer
