@@ -184,6 +184,13 @@ int with_dtype_pair(int dt, int dt_g, F f) {
     if (dt == PN2_F32 && dt_g == PN2_F32) return f(Ty<float>{}, Ty<float>{});
     return -3;
 }
+// run-time int that takes one of a few values -> f(Int<N>{}) for the first N that equals it, for the LAST one otherwise (the `default:` rung: the callers' range
+// checks come first).  with_int<1, 2, 3, 4>(P, f) instantiates f for exactly the four listed values
+template <int N0, int... Ns, typename F>
+int with_int(int v, F f) {
+    if constexpr (sizeof...(Ns) > 0) { if (v != N0) return with_int<Ns...>(v, f); }
+    return f(Int<N0>{});
+}
 // elements per 16-byte vector of a dtype code.  An unknown code counts as bf16 (8) ON PURPOSE: the entry points test alignment (-2) before they
 // dispatch on the dtype (-3), so this answer decides which of the two a call with a bad dtype and a misaligned shape gets
 inline int vec_of(int dt) { return dt == PN2_F32 ? 4 : 8; }
@@ -201,7 +208,6 @@ inline void rows_walk_geometry(int M, int CV, int min_mult, int max_mult, int& c
     if (max_mult > 0 && rows_per_blk > max_mult * R) rows_per_blk = max_mult * R;
     nblk = (M + rows_per_blk - 1) / rows_per_blk;
 }
-// (pn2_tail.hip still has a grid_for of its own with this signature: the shared one lives in a namespace that the other files open)
 // arguments of a table-driven launch (pn2_*_multi): device job table, njobs + 1 prefix sums, counts
 inline bool table_ok(const void* jobs_dev, const int* block_start_dev, int njobs, int total_blocks) { return jobs_dev && block_start_dev && njobs >= 1 && total_blocks >= 1; }
 namespace pn2_host {

@@ -2818,39 +2818,32 @@ int pn2_pack_weight(int dtype, const float* w, void* wp, const pn2_pack_desc* p,
     if (!w || !wp || !p) return -1;
     const size_t total = (size_t)p->Rp * p->Kp;
     const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    if (dtype == PN2_BF16) hipLaunchKernelGGL(pack_weight<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)wp, *p);
-    else if (dtype == PN2_F32) hipLaunchKernelGGL(pack_weight<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (float*)wp, *p);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dtype, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<pack_weight<T>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, w, (T*)wp, *p);
+    });
 }
 
 int pn2_pack_blocks(const pn2_pack_desc* p) { return (p && p->KH * p->KW <= 225) ? pack_blocks(*p) : -1; }
 
 int pn2_pack_weights_multi(int dtype, const pn2_pack_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
     if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    if (dtype == PN2_BF16) hipLaunchKernelGGL(pack_weight_multi<bf16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else if (dtype == PN2_F32) hipLaunchKernelGGL(pack_weight_multi<float>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dtype, [&](auto ty) {
+        return pn2_launch<pack_weight_multi<type_of<decltype(ty)>>>(dim3(total_blocks), dim3(256), 0, 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
+    });
 }
 
 int pn2_wgrad_reduce(const float* slab, float* gw, const pn2_pack_desc* p, int nsplit, int accumulate, void* stream) {
     if (!slab || !gw || !p) return -1;
     const int grid = reduce_blocks(*p);
-    hipLaunchKernelGGL(wgrad_reduce_unpack, dim3(grid), dim3(256), 0, (hipStream_t)stream, slab, gw, *p, nsplit, accumulate);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<wgrad_reduce_unpack>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, slab, gw, *p, nsplit, accumulate);
 }
 
 int pn2_wgrad_reduce_blocks(const pn2_pack_desc* p) { return p ? reduce_blocks(*p) : -1; }
 
 int pn2_wgrad_reduce_multi(const pn2_reduce_job* jobs_dev, const int* block_start_dev, int njobs, int total_blocks, void* stream) {
     if (!jobs_dev || !block_start_dev || njobs < 1 || total_blocks < 1) return -1;
-    hipLaunchKernelGGL(wgrad_reduce_multi, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<wgrad_reduce_multi>(dim3(total_blocks), dim3(256), 0, 0, (hipStream_t)stream, jobs_dev, block_start_dev, njobs);
 }
 
 
@@ -2859,11 +2852,10 @@ int pn2_pack_patch_weight(int dtype, const float* w_oihw, void* wp, int Cout, in
     if (!w_oihw || !wp || Cin_p < Cin || Rp < KH * KW * Cin_p || Kp < Cout) return -1;
     const size_t total = (size_t)Rp * Kp;
     const unsigned grid = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    if (dtype == PN2_BF16) hipLaunchKernelGGL(pack_patch_k<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w_oihw, (bf16_t*)wp, Cout, Cin, KH, KW, Cin_p, Rp, Kp);
-    else if (dtype == PN2_F32) hipLaunchKernelGGL(pack_patch_k<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w_oihw, (float*)wp, Cout, Cin, KH, KW, Cin_p, Rp, Kp);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dtype, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<pack_patch_k<T>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, w_oihw, (T*)wp, Cout, Cin, KH, KW, Cin_p, Rp, Kp);
+    });
 }
 
 /* dx[n][oy*S+kh][ox*S+kw][c] (+)= t[(n,oy,ox)][(kh*S+kw)*C + c]: scatters the GEMM result of the patchify data gradient back to NHWC */
@@ -2873,11 +2865,10 @@ int pn2_depth_to_space(int dtype, const void* t, int ld_t, void* dx, int ld_dx, 
     if (C % V || ld_t % V || ld_dx % V || OH * S > H || OW * S > W) return -2;
     const size_t total = (size_t)N * H * W * (C / V);
     const unsigned grid = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
-    if (dtype == PN2_BF16) hipLaunchKernelGGL(depth_to_space_k<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)t, ld_t, (bf16_t*)dx, ld_dx, N, H, W, OH, OW, S, C, accumulate);
-    else if (dtype == PN2_F32) hipLaunchKernelGGL(depth_to_space_k<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)t, ld_t, (float*)dx, ld_dx, N, H, W, OH, OW, S, C, accumulate);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dtype, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<depth_to_space_k<T>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)t, ld_t, (T*)dx, ld_dx, N, H, W, OH, OW, S, C, accumulate);
+    });
 }
 
 
@@ -2893,13 +2884,11 @@ int pn2_conv_dgrad_small_cin(int dtype, const void* dy, int ld_dy, const float* 
     const size_t M = (size_t)N * H * W;
     const int pix = 1024;
     const unsigned grid = (unsigned)((M + pix - 1) / pix);
-    if (dtype == PN2_BF16) hipLaunchKernelGGL(dgrad_small_cin_k<bf16_t>, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dy, ld_dy, w_oihw, (bf16_t*)dx, ld_dx,
-                                              N, H, W, OH, OW, Cout, Cin, KH, KW, stride, pad, accumulate, pix);
-    else if (dtype == PN2_F32) hipLaunchKernelGGL(dgrad_small_cin_k<float>, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const float*)dy, ld_dy, w_oihw, (float*)dx, ld_dx,
-                                                  N, H, W, OH, OW, Cout, Cin, KH, KW, stride, pad, accumulate, pix);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dtype, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<dgrad_small_cin_k<T>>(dim3(grid), dim3(256), lds, 64 * 1024, (hipStream_t)stream, (const T*)dy, ld_dy, w_oihw, (T*)dx, ld_dx, N, H, W, OH, OW, Cout, Cin, KH, KW,
+                                                stride, pad, accumulate, pix);
+    });
 }
 
 
@@ -2912,11 +2901,10 @@ int pn2_conv_splitk_reduce(int dtype, const float* ws, int ksplit, int M, int Co
     int lanes = 1; while (lanes < Cout / 4 && lanes < 16) lanes <<= 1;          // <= 16 column lanes (64 channels) per workgroup -> >= 16 row lanes
     if (dtype == PN2_BF16 && ld_out % 4) return -2;
     const dim3 grid((M + 63) / 64, (Cout / 4 + lanes - 1) / lanes);
-    if (dtype == PN2_BF16) hipLaunchKernelGGL(splitk_reduce_k<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, ws, ksplit, M, Cout, (bf16_t*)out, ld_out, bias, psum, psq, accumulate, lanes);
-    else if (dtype == PN2_F32) hipLaunchKernelGGL(splitk_reduce_k<float>, grid, dim3(256), 0, (hipStream_t)stream, ws, ksplit, M, Cout, (float*)out, ld_out, bias, psum, psq, accumulate, lanes);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dtype, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<splitk_reduce_k<T>>(grid, dim3(256), 0, 0, (hipStream_t)stream, ws, ksplit, M, Cout, (T*)out, ld_out, bias, psum, psq, accumulate, lanes);
+    });
 }
 
 }  // extern "C"

@@ -266,10 +266,11 @@ __global__ __launch_bounds__(256) void wfm_sums_batch_k(const unsigned char* __r
         wfm_sums_body(pred + r.off, gt + r.off, r.H, r.W, work_d + r.off, work_d + total + r.off, K, c5, blockIdx.x, nb, part + (size_t)blockIdx.y * PN2_EVAL_WFM_MAX_BLOCKS * 2);
 }
 
+constexpr size_t EDT_LDS_CAP = 60 * 1024;          // a row of W ints in the LDS of the edt_rows kernels
 // -1: null pointer / empty size, -2: outside the built range (blockIdx.y carries the image; edt_rows keeps a row of W ints in LDS)
 int batch_check(const void* a, const void* b, const void* tab, int B, int maxH, int maxW, long long total) {
     if (!a || !b || !tab || B < 1 || maxH < 1 || maxW < 1 || total < 1) return -1;
-    if (B > 65535 || (size_t)maxW * sizeof(int) > 60 * 1024) return -2;
+    if (B > 65535 || (size_t)maxW * sizeof(int) > EDT_LDS_CAP) return -2;
     return 0;
 }
 
@@ -282,24 +283,20 @@ int pn2_eval_region_sums(const unsigned char* pred_u8, const float* gt, int H, i
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(out25, 0, 25 * sizeof(unsigned long long), st) != hipSuccess) return -4;
     const int g = region_blocks((long long)H * W);
-    hipLaunchKernelGGL(eval_centroid_k, dim3(g), dim3(256), 0, st, gt, H, W, out25);
-    hipLaunchKernelGGL(eval_quadrants_k, dim3(g), dim3(256), 0, st, pred_u8, gt, H, W, out25);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<eval_centroid_k>(dim3(g), dim3(256), 0, 0, st, gt, H, W, out25)) return rc;
+    return pn2_launch<eval_quadrants_k>(dim3(g), dim3(256), 0, 0, st, pred_u8, gt, H, W, out25);
 }
 
 int pn2_eval_wfm_blocks(int H, int W) { return wfm_blocks((long long)H * W); }
 
 int pn2_eval_wfm(const unsigned char* pred_u8, const float* gt, int H, int W, const double* K49, double c5, int* work_i, double* work_d, double* part, void* stream) {
     if (!pred_u8 || !gt || !K49 || !work_i || !work_d || !part || H < 1 || W < 1) return -1;
-    if ((size_t)W * sizeof(int) > 60 * 1024) return -2;
+    if ((size_t)W * sizeof(int) > EDT_LDS_CAP) return -2;
     hipStream_t st = (hipStream_t)stream;
     double* et = work_d; double* dst = work_d + (size_t)H * W;
-    hipLaunchKernelGGL(edt_cols_k, dim3((W + 255) / 256), dim3(256), 0, st, gt, H, W, work_i);
-    hipLaunchKernelGGL(edt_rows_k, dim3(H), dim3(256), (size_t)W * sizeof(int), st, pred_u8, gt, H, W, work_i, et, dst);
-    hipLaunchKernelGGL(wfm_sums_k, dim3(pn2_eval_wfm_blocks(H, W)), dim3(256), 0, st, pred_u8, gt, H, W, et, dst, K49, c5, part);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<edt_cols_k>(dim3((W + 255) / 256), dim3(256), 0, 0, st, gt, H, W, work_i)) return rc;
+    if (int rc = pn2_launch<edt_rows_k>(dim3(H), dim3(256), (size_t)W * sizeof(int), (int)EDT_LDS_CAP, st, pred_u8, gt, H, W, (const int*)work_i, et, dst)) return rc;
+    return pn2_launch<wfm_sums_k>(dim3(pn2_eval_wfm_blocks(H, W)), dim3(256), 0, 0, st, pred_u8, gt, H, W, (const double*)et, (const double*)dst, K49, c5, part);
 }
 
 int pn2_eval_tail_batch(const float* const* maps, int nmaps, int B, int h, int w, const pn2_eval_img* table_dev, int maxH, int maxW, long long total,
@@ -314,15 +311,11 @@ int pn2_eval_tail_batch(const float* const* maps, int nmaps, int B, int h, int w
     if (hipMemsetAsync(minmax, 0, (size_t)B * 2 * sizeof(unsigned), st) != hipSuccess) return -4;
     const long long n = (long long)maxH * maxW;
     const dim3 grid((unsigned)std::min<long long>((n + 1023) / 1024, 512), B);
-    if (nmaps == 4) {
-        hipLaunchKernelGGL(tail_minmax_batch_k<4>, grid, dim3(256), 0, st, M, h, w, table_dev, maxH, maxW, total, minmax);
-        hipLaunchKernelGGL(tail_bytes_batch_k<4>, grid, dim3(256), 0, st, M, h, w, table_dev, maxH, maxW, total, (const unsigned*)minmax, out);
-    } else {
-        hipLaunchKernelGGL(tail_minmax_batch_k<1>, grid, dim3(256), 0, st, M, h, w, table_dev, maxH, maxW, total, minmax);
-        hipLaunchKernelGGL(tail_bytes_batch_k<1>, grid, dim3(256), 0, st, M, h, w, table_dev, maxH, maxW, total, (const unsigned*)minmax, out);
-    }
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_int<4, 1>(nmaps, [&](auto nm) {
+        constexpr int NM = decltype(nm)::value;
+        if (int rc = pn2_launch<tail_minmax_batch_k<NM>>(grid, dim3(256), 0, 0, st, M, h, w, table_dev, maxH, maxW, total, minmax)) return rc;
+        return pn2_launch<tail_bytes_batch_k<NM>>(grid, dim3(256), 0, 0, st, M, h, w, table_dev, maxH, maxW, total, (const unsigned*)minmax, out);
+    });
 }
 
 int pn2_eval_counts_batch(const unsigned char* pred_u8, const float* gt, const pn2_eval_img* table_dev, int B, int maxH, int maxW, long long total,
@@ -334,10 +327,9 @@ int pn2_eval_counts_batch(const unsigned char* pred_u8, const float* gt, const p
     if (out25 && hipMemsetAsync(out25, 0, (size_t)B * 25 * sizeof(unsigned long long), st) != hipSuccess) return -4;
     const long long n = (long long)maxH * maxW;
     const int nr = region_blocks(n);
-    hipLaunchKernelGGL(counts_batch_k, dim3(std::max(hist_blocks(n), out25 ? nr : 1), B), dim3(256), 0, st, pred_u8, gt, table_dev, maxH, maxW, total, hist, out25);
-    if (out25) hipLaunchKernelGGL(quadrants_batch_k, dim3(nr, B), dim3(256), 0, st, pred_u8, gt, table_dev, maxH, maxW, total, out25);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    const int rc = pn2_launch<counts_batch_k>(dim3(std::max(hist_blocks(n), out25 ? nr : 1), B), dim3(256), 0, 0, st, pred_u8, gt, table_dev, maxH, maxW, total, hist, out25);
+    if (rc || !out25) return rc;
+    return pn2_launch<quadrants_batch_k>(dim3(nr, B), dim3(256), 0, 0, st, pred_u8, gt, table_dev, maxH, maxW, total, out25);
 }
 
 int pn2_eval_wfm_batch(const unsigned char* pred_u8, const float* gt, const pn2_eval_img* table_dev, int B, int maxH, int maxW, long long total,
@@ -345,11 +337,10 @@ int pn2_eval_wfm_batch(const unsigned char* pred_u8, const float* gt, const pn2_
     if (!K49 || !work_i || !work_d || !part) return -1;
     if (int rc = batch_check(pred_u8, gt, table_dev, B, maxH, maxW, total)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(edt_cols_batch_k, dim3((maxW + 63) / 64, B), dim3(64), 0, st, gt, table_dev, maxH, maxW, total, work_i);
-    hipLaunchKernelGGL(edt_rows_batch_k, dim3(maxH, B), dim3(256), (size_t)maxW * sizeof(int), st, pred_u8, gt, table_dev, maxH, maxW, total, (const int*)work_i, work_d);
-    hipLaunchKernelGGL(wfm_sums_batch_k, dim3(wfm_blocks((long long)maxH * maxW), B), dim3(256), 0, st, pred_u8, gt, table_dev, maxH, maxW, total, (const double*)work_d, K49, c5, part);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<edt_cols_batch_k>(dim3((maxW + 63) / 64, B), dim3(64), 0, 0, st, gt, table_dev, maxH, maxW, total, work_i)) return rc;
+    if (int rc = pn2_launch<edt_rows_batch_k>(dim3(maxH, B), dim3(256), (size_t)maxW * sizeof(int), (int)EDT_LDS_CAP, st, pred_u8, gt, table_dev, maxH, maxW, total, (const int*)work_i, work_d))
+        return rc;
+    return pn2_launch<wfm_sums_batch_k>(dim3(wfm_blocks((long long)maxH * maxW), B), dim3(256), 0, 0, st, pred_u8, gt, table_dev, maxH, maxW, total, (const double*)work_d, K49, c5, part);
 }
 
 }  // extern "C"

@@ -37,8 +37,6 @@ __global__ __launch_bounds__(256) void to_tensor_k(const unsigned char* __restri
     }
 }
 
-inline unsigned grid_of(size_t total) { const size_t g = (total + 255) / 256; return (unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
-
 // ------------------------------------------------------------------------------------------------ ragged batch
 // Both passes give a thread PN2_INPUT_PX adjacent output pixels of one row (4 or 12 bytes); the index arithmetic inside a slot is 32-bit (the entries refuse a
 // slot of 2^31 bytes).  `wide`: out_size is a multiple of 4 and every base is aligned, so a thread's run of the [.][S][C] scratch image starts on a dword.
@@ -271,6 +269,20 @@ int check_aug(const pn2_input_slot* t, const pn2_input_aug* g, int n) {
     return 0;
 }
 
+// the width pass behind both entry points (their null checks are done); AUG: every slot reads its source through its row of the second table
+template <bool AUG>
+int input_batch_width(Bool<AUG>, const pn2_input_slot* table_host, const pn2_input_slot* table_dev, const pn2_input_aug* aug_host, const pn2_input_aug* aug_dev, int n,
+                      int out_size, const unsigned char* src, long long src_bytes, unsigned char* tmp, long long tmp_bytes, const int* taps, long long tap_ints, void* stream) {
+    if (n == 0) return 0;
+    long long blocks = 0;
+    bool aligned4 = false;
+    if constexpr (AUG) if (int rc = check_aug(table_host, aug_host, n)) return rc;
+    if (int rc = check_table(table_host, n, out_size, src_bytes, tmp_bytes, tap_ints, 0, 0, false, &blocks, &aligned4)) return rc;
+    if (blocks == 0) return 0;          // every slot is empty
+    const int wide = out_size % 4 == 0 && aligned4 && ((uintptr_t)tmp & 3) == 0;
+    return pn2_launch<input_batch_width_k<AUG>>(dim3((unsigned)blocks), dim3(256), 0, 0, (hipStream_t)stream, table_dev, aug_dev, n, out_size, src, tmp, taps, wide);
+}
+
 }  // namespace
 
 extern "C" {
@@ -318,17 +330,13 @@ int pn2_resize_u8_pass(const unsigned char* src, unsigned char* dst, int H, int 
                        const int* kk_dev, int ksize, void* stream) {
     if (!src || !dst || !xmin_dev || !count_dev || !kk_dev || H < 1 || W < 1 || C < 1 || out_size < 1 || (axis != 0 && axis != 1)) return -1;
     const size_t total = (size_t)(axis == 0 ? out_size : H) * (axis == 1 ? out_size : W) * C;
-    hipLaunchKernelGGL(resize_pass_k, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, src, dst, H, W, C, out_size, axis, xmin_dev, count_dev, kk_dev, ksize);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<resize_pass_k>(dim3(pn2_host::grid_for(total, 8192)), dim3(256), 0, 0, (hipStream_t)stream, src, dst, H, W, C, out_size, axis, xmin_dev, count_dev, kk_dev, ksize);
 }
 
 /* transforms.ToTensor() [+ transforms.Normalize(mean, std) when mean != NULL]: uint8 [H][W][C] -> fp32 [C][H][W] (one sample of the NCHW batch) */
 int pn2_u8_to_tensor(const unsigned char* src, float* dst, int H, int W, int C, const float* mean_dev, const float* std_dev, void* stream) {
     if (!src || !dst || H < 1 || W < 1 || C < 1 || ((mean_dev == nullptr) != (std_dev == nullptr))) return -1;
-    hipLaunchKernelGGL(to_tensor_k, dim3(grid_of((size_t)H * W * C)), dim3(256), 0, (hipStream_t)stream, src, dst, H, W, C, mean_dev, std_dev);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<to_tensor_k>(dim3(pn2_host::grid_for((size_t)H * W * C, 8192)), dim3(256), 0, 0, (hipStream_t)stream, src, dst, H, W, C, mean_dev, std_dev);
 }
 
 int pn2_input_batch_blocks(int rows, int out_size) {
@@ -341,17 +349,7 @@ int pn2_input_batch_blocks(int rows, int out_size) {
 int pn2_input_batch_width(const pn2_input_slot* table_host, const pn2_input_slot* table_dev, int n, int out_size, const unsigned char* src, long long src_bytes,
                           unsigned char* tmp, long long tmp_bytes, const int* taps, long long tap_ints, void* stream) {
     if (!table_host || !table_dev || !src || !tmp || !taps || n < 0 || out_size < 1 || src_bytes < 0 || tmp_bytes < 0 || tap_ints < 0) return -1;
-    if (n == 0) return 0;
-    long long blocks = 0;
-    bool aligned4 = false;
-    const int rc = check_table(table_host, n, out_size, src_bytes, tmp_bytes, tap_ints, 0, 0, false, &blocks, &aligned4);
-    if (rc) return rc;
-    if (blocks == 0) return 0;          // every slot is empty
-    const int wide = out_size % 4 == 0 && aligned4 && ((uintptr_t)tmp & 3) == 0;
-    hipLaunchKernelGGL(input_batch_width_k<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table_dev, (const pn2_input_aug*)nullptr, n, out_size, src,
-                       tmp, taps, wide);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return input_batch_width(Bool<false>{}, table_host, table_dev, nullptr, nullptr, n, out_size, src, src_bytes, tmp, tmp_bytes, taps, tap_ints, stream);
 }
 
 /* the same launch with every source pixel of a mode-1 slot read through the slot's map: rotation and flips never materialise */
@@ -359,18 +357,7 @@ int pn2_input_batch_width_aug(const pn2_input_slot* table_host, const pn2_input_
                               int out_size, const unsigned char* src, long long src_bytes, unsigned char* tmp, long long tmp_bytes, const int* taps,
                               long long tap_ints, void* stream) {
     if (!table_host || !table_dev || !aug_host || !aug_dev || !src || !tmp || !taps || n < 0 || out_size < 1 || src_bytes < 0 || tmp_bytes < 0 || tap_ints < 0) return -1;
-    if (n == 0) return 0;
-    long long blocks = 0;
-    bool aligned4 = false;
-    int rc = check_aug(table_host, aug_host, n);
-    if (rc) return rc;
-    rc = check_table(table_host, n, out_size, src_bytes, tmp_bytes, tap_ints, 0, 0, false, &blocks, &aligned4);
-    if (rc) return rc;
-    if (blocks == 0) return 0;
-    const int wide = out_size % 4 == 0 && aligned4 && ((uintptr_t)tmp & 3) == 0;
-    hipLaunchKernelGGL(input_batch_width_k<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table_dev, aug_dev, n, out_size, src, tmp, taps, wide);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return input_batch_width(Bool<true>{}, table_host, table_dev, aug_host, aug_dev, n, out_size, src, src_bytes, tmp, tmp_bytes, taps, tap_ints, stream);
 }
 
 /* height pass + ToTensor + Normalize of a ragged batch: ONE launch, scratch arena -> out_rgb [n_rgb][3][S][S] / out_mask [n_mask][1][S][S] fp32 */
@@ -389,14 +376,10 @@ int pn2_input_batch_height(const pn2_input_slot* table_host, const pn2_input_slo
     const long long bps = slot_blocks(out_size, out_size);
     if (bps * n > INT_MAX) return -2;
     const bool wide = out_size % 4 == 0 && aligned4 && ((uintptr_t)tmp & 3) == 0 && ((uintptr_t)out_rgb & 15) == 0 && ((uintptr_t)out_mask & 15) == 0;
-    if (wide)
-        hipLaunchKernelGGL(input_batch_height_k<true>, dim3((unsigned)(bps * n)), dim3(256), 0, (hipStream_t)stream, table_dev, out_size, (int)bps, tmp, taps, out_rgb, out_mask,
-                           mean_dev, std_dev);
-    else
-        hipLaunchKernelGGL(input_batch_height_k<false>, dim3((unsigned)(bps * n)), dim3(256), 0, (hipStream_t)stream, table_dev, out_size, (int)bps, tmp, taps, out_rgb, out_mask,
-                           mean_dev, std_dev);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_int<1, 0>(wide, [&](auto wd) {
+        return pn2_launch<input_batch_height_k<decltype(wd)::value != 0>>(dim3((unsigned)(bps * n)), dim3(256), 0, 0, (hipStream_t)stream, table_dev, out_size, (int)bps, tmp, taps, out_rgb,
+                                                                          out_mask, mean_dev, std_dev);
+    });
 }
 
 }  // extern "C"

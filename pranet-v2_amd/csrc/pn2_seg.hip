@@ -289,11 +289,7 @@ int pn2_seg_labels(const float* const* maps, int nmaps, int mode, int N, int K, 
     const long long HW = (long long)H * W;
     const dim3 g(pn2_host::grid_for((size_t)N * HW, 65536));
     hipStream_t st = (hipStream_t)stream;
-    if (mode == 0) hipLaunchKernelGGL(seg_labels_k<0>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
-    else if (mode == 1) hipLaunchKernelGGL(seg_labels_k<1>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
-    else hipLaunchKernelGGL(seg_labels_k<2>, g, dim3(256), 0, st, m, nmaps, N, K, HW, out);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_int<0, 1, 2>(mode, [&](auto mo) { return pn2_launch<seg_labels_k<decltype(mo)::value>>(g, dim3(256), 0, 0, st, m, nmaps, N, K, HW, out); });
 }
 
 int pn2_seg_labels_up(const pn2_seg_up_map* maps, int nmaps, int mode, int N, int K, int OH, int OW, unsigned char* out, void* stream) {
@@ -311,16 +307,9 @@ int pn2_seg_labels_up(const pn2_seg_up_map* maps, int nmaps, int mode, int N, in
     }
     const dim3 g((OW + 63) / 64, (OH + 3) / 4, N);
     hipStream_t st = (hipStream_t)stream;
-    auto launch = [&](auto mo, auto kv, auto ve) {
-        hipLaunchKernelGGL((seg_labels_up_k<decltype(mo)::value, decltype(kv)::value, decltype(ve)::value>), g, dim3(256), 0, st, m, nmaps, K, OH, OW, out);
-    };
-    auto with_kv = [&](auto mo, auto ve) {
-        switch ((K + 3) / 4) { case 1: launch(mo, Int<1>{}, ve); break; case 2: launch(mo, Int<2>{}, ve); break; case 3: launch(mo, Int<3>{}, ve); break; default: launch(mo, Int<4>{}, ve); }
-    };
-    auto with_vec = [&](auto mo) { if (vec) with_kv(mo, Bool<true>{}); else with_kv(mo, Bool<false>{}); };
-    if (mode == 0) with_vec(Int<0>{}); else if (mode == 1) with_vec(Int<1>{}); else with_vec(Int<2>{});
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_int<0, 1, 2>(mode, [&](auto mo) { return with_int<1, 2, 3, 4>((K + 3) / 4, [&](auto kv) { return with_int<1, 0>(vec, [&](auto ve) {
+        return pn2_launch<seg_labels_up_k<decltype(mo)::value, decltype(kv)::value, decltype(ve)::value != 0>>(g, dim3(256), 0, 0, st, m, nmaps, K, OH, OW, out);
+    }); }); });
 }
 
 int pn2_seg_counts(const unsigned char* pred, const unsigned char* gt, long long n, int K, unsigned long long* counts, void* stream) {
@@ -328,9 +317,7 @@ int pn2_seg_counts(const unsigned char* pred, const unsigned char* gt, long long
     if (K < 1 || K > 256) return -2;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(counts, 0, (size_t)K * 3 * sizeof(unsigned long long), st) != hipSuccess) return -4;
-    hipLaunchKernelGGL(seg_counts_k, dim3(pn2_host::grid_for((size_t)((n + 15) / 16), 2048)), dim3(256), 0, st, pred, gt, n, K, counts);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<seg_counts_k>(dim3(pn2_host::grid_for((size_t)((n + 15) / 16), 2048)), dim3(256), 0, 0, st, pred, gt, n, K, counts);
 }
 
 int pn2_seg_surface_workspace(int D, int H, int W, int ndim, long long* bytes) {
@@ -355,13 +342,11 @@ int pn2_seg_surface_hist(const unsigned char* A, const unsigned char* B, int D, 
     int* f1 = meta + 16;
     int* f2 = f1 + n;
     if (hipMemsetAsync(hist, 0, (size_t)nhist * sizeof(unsigned), st) != hipSuccess || hipMemsetAsync(counts2, 0, 2 * sizeof(unsigned), st) != hipSuccess) return -4;
-    hipLaunchKernelGGL(seg_meta_init_k, dim3(1), dim3(64), 0, st, meta);
-    hipLaunchKernelGGL(seg_bbox_k, dim3(pn2_host::grid_for((n + 15) / 16, 2048)), dim3(256), 0, st, A, B, D, H, W, cls, meta);
-    hipLaunchKernelGGL(seg_rows_k, dim3(H, D), dim3(256), 0, st, B, D, H, W, cls, ndim, meta, f1, counts2);
-    hipLaunchKernelGGL(seg_cols_k, dim3((W + 63) / 64, (H + 63) / 64, D), dim3(256), 0, st, H, W, meta, f1, f2);
-    hipLaunchKernelGGL(seg_hist_k, dim3(pn2_host::grid_for((n + 3) / 4, 8192)), dim3(256), 0, st, A, D, H, W, cls, ndim, meta, f2, hist, nhist, counts2);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<seg_meta_init_k>(dim3(1), dim3(64), 0, 0, st, meta)) return rc;
+    if (int rc = pn2_launch<seg_bbox_k>(dim3(pn2_host::grid_for((n + 15) / 16, 2048)), dim3(256), 0, 0, st, A, B, D, H, W, cls, meta)) return rc;
+    if (int rc = pn2_launch<seg_rows_k>(dim3(H, D), dim3(256), 0, 0, st, B, D, H, W, cls, ndim, (const int*)meta, f1, counts2)) return rc;
+    if (int rc = pn2_launch<seg_cols_k>(dim3((W + 63) / 64, (H + 63) / 64, D), dim3(256), 0, 0, st, H, W, (const int*)meta, (const int*)f1, f2)) return rc;
+    return pn2_launch<seg_hist_k>(dim3(pn2_host::grid_for((n + 3) / 4, 8192)), dim3(256), 0, 0, st, A, D, H, W, cls, ndim, (const int*)meta, (const int*)f2, hist, nhist, counts2);
 }
 
 }  // extern "C"

@@ -15,7 +15,6 @@
 namespace {
 
 constexpr int MAXK = 32;
-inline int grid_for(size_t total, int cap = 16384) { size_t g = (total + 255) / 256; return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g)); }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(256) void ra_gate_bwd_k(const T* __restrict__ x, in
 // subtracts the leaving sample (2 LDS reads per output instead of ks); same for (column, 8-row segment) lanes on the row sums.  {0,1} masks
 // sum exactly.  Odd LDS row strides keep both walks bank-conflict free.  (The 32x32-tile / full-window version took 55 us at 32x352x352.)
 constexpr int LTY = 32, LTX = 64, LSX = 16, LSY = 8;
-__global__ __launch_bounds__(256) void loss_weights_k(const float* __restrict__ mask, float* __restrict__ weit, int H, int W, int ks, long long* __restrict__ clr = nullptr, int nclr = 0) {
+__global__ __launch_bounds__(256) void loss_weights_k(const float* __restrict__ mask, float* __restrict__ weit, int H, int W, int ks, long long* __restrict__ clr, int nclr) {
     extern __shared__ float sh[];                  // tile TSY x TSX, then row sums TSY x HSX
     if (clr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)          // pn2_loss_weights_clear: the image-sum accumulators of the one-pass tail, zeroed by the launch in front of it
         for (int i = threadIdx.x; i < nclr; i += 256) clr[i] = 0;
@@ -251,7 +250,7 @@ __global__ void loss_finalize_k(const float* __restrict__ partial, int P, int N,
 
 __global__ __launch_bounds__(256) void loss_bwd_k(const float* __restrict__ preds, float* __restrict__ dpreds, long long map_stride, int P,
                                                   const float* __restrict__ mask, const float* __restrict__ weit, const float* __restrict__ wsum,
-                                                  const float* __restrict__ sums, float gscale, int N, int HW, long long dmap_stride = -1, const float* __restrict__ gdev = nullptr) {
+                                                  const float* __restrict__ sums, float gscale, int N, int HW, long long dmap_stride, const float* __restrict__ gdev) {
     const int p = blockIdx.z, n = blockIdx.y;
     if (dmap_stride < 0) dmap_stride = map_stride;
     const size_t of = (size_t)p * map_stride + (size_t)n * HW, ob = (size_t)(P + p) * map_stride + (size_t)n * HW;
@@ -1262,49 +1261,39 @@ extern "C" {
 int pn2_dsra_fuse_fwd(const float* fg, const float* cf, const float* cb, float* out, int M, int K, int sm, void* stream) {
     if (!fg || !cf || !cb || !out) return -1;
     if (K > MAXK) return -2;
-    hipLaunchKernelGGL(dsra_fwd_k, dim3(grid_for(M)), dim3(256), 0, (hipStream_t)stream, fg, cf, cb, out, M, K, sm);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<dsra_fwd_k>(dim3(pn2_host::grid_for(M, 16384)), dim3(256), 0, 0, (hipStream_t)stream, fg, cf, cb, out, M, K, sm);
 }
 int pn2_dsra_fuse_bwd(const float* fg, const float* cf, const float* cb, const float* dout, float* dfg, float* dcf, float* dcb, int M, int K, int sm, void* stream) {
     if (!fg || !cf || !cb || !dout || !dfg || !dcf || !dcb) return -1;
     if (K > MAXK) return -2;
-    hipLaunchKernelGGL(dsra_bwd_k, dim3(grid_for(M)), dim3(256), 0, (hipStream_t)stream, fg, cf, cb, dout, dfg, dcf, dcb, M, K, sm);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<dsra_bwd_k>(dim3(pn2_host::grid_for(M, 16384)), dim3(256), 0, 0, (hipStream_t)stream, fg, cf, cb, dout, dfg, dcf, dcb, M, K, sm);
 }
 
 int pn2_ra_gate_fwd(int dt, const void* x, int ld_x, const float* crop, void* out, int ld_out, int M, int C, void* stream) {
     if (!x || !crop || !out) return -1;
     if (C % 8 || ld_x % 8 || ld_out % 8) return -2;
-    hipStream_t st = (hipStream_t)stream;
-    if (dt == PN2_BF16) hipLaunchKernelGGL(ra_gate_fwd_k<bf16_t>, dim3(grid_for((size_t)M * C / 8)), dim3(256), 0, st, (const bf16_t*)x, ld_x, crop, (bf16_t*)out, ld_out, M, C);
-    else if (dt == PN2_F32) hipLaunchKernelGGL(ra_gate_fwd_k<float>, dim3(grid_for((size_t)M * C / 4)), dim3(256), 0, st, (const float*)x, ld_x, crop, (float*)out, ld_out, M, C);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<ra_gate_fwd_k<T>>(dim3(pn2_host::grid_for((size_t)M * C / TT<T>::VEC, 16384)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, ld_x, crop, (T*)out, ld_out, M, C);
+    });
 }
 int pn2_ra_gate_bwd(int dt, const void* x, int ld_x, const float* crop, const void* dout, int ld_dout, void* dx, int ld_dx, int dx_accum, float* dcrop, int M, int C, void* stream) {
     if (!x || !crop || !dout || !dx || !dcrop) return -1;
     if (C % 8 || ld_x % 8 || ld_dout % 8 || ld_dx % 8) return -2;
-    hipStream_t st = (hipStream_t)stream;
     const int grid = (M + 3) / 4 > 8192 ? 8192 : (M + 3) / 4;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((ra_gate_bwd_k<bf16_t, false>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, ld_x, crop, (const bf16_t*)dout, ld_dout, (bf16_t*)dx, ld_dx, dx_accum, dcrop, M, C);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((ra_gate_bwd_k<float, false>), dim3(grid), dim3(256), 0, st, (const float*)x, ld_x, crop, (const float*)dout, ld_dout, (float*)dx, ld_dx, dx_accum, dcrop, M, C);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<ra_gate_bwd_k<T, false>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)x, ld_x, crop, (const T*)dout, ld_dout, (T*)dx, ld_dx, dx_accum, dcrop, M, C);
+    });
 }
 int pn2_ra_gate_post_bwd(int dt, const void* raw, int ld_raw, const float* crop, const void* dz, int ld_dz, void* dzg, int ld_dzg, float* dcrop, int M, int C, void* stream) {
     if (!raw || !crop || !dz || !dzg || !dcrop) return -1;
     if (C % 8 || ld_raw % 8 || ld_dz % 8 || ld_dzg % 8) return -2;
-    hipStream_t st = (hipStream_t)stream;
     const int grid = (M + 3) / 4 > 8192 ? 8192 : (M + 3) / 4;
-    if (dt == PN2_BF16) hipLaunchKernelGGL((ra_gate_bwd_k<bf16_t, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)raw, ld_raw, crop, (const bf16_t*)dz, ld_dz, (bf16_t*)dzg, ld_dzg, 0, dcrop, M, C);
-    else if (dt == PN2_F32) hipLaunchKernelGGL((ra_gate_bwd_k<float, true>), dim3(grid), dim3(256), 0, st, (const float*)raw, ld_raw, crop, (const float*)dz, ld_dz, (float*)dzg, ld_dzg, 0, dcrop, M, C);
-    else return -3;
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return with_storage_dtype(dt, [&](auto ty) {
+        using T = type_of<decltype(ty)>;
+        return pn2_launch<ra_gate_bwd_k<T, true>>(dim3(grid), dim3(256), 0, 0, (hipStream_t)stream, (const T*)raw, ld_raw, crop, (const T*)dz, ld_dz, (T*)dzg, ld_dzg, 0, dcrop, M, C);
+    });
 }
 
 // tile + row sums of loss_weights_k in bytes: 38.8 KiB at ks = 31, above the default 64 KiB of dynamic LDS from ks = 59 on (70.5 KiB at 63), hence the opt-in
@@ -1328,59 +1317,55 @@ int pn2_structure_loss_fwd(const float* preds, long long map_stride, int P, cons
     if (!preds || !mask || !weit || !partial || !sums || !wsum || !loss) return -1;
     if (P * N > 512 || P > 8) return -2;
     const int nb = pn2_loss_blocks(HW);
-    hipLaunchKernelGGL(loss_fwd_k, dim3(nb, N, P), dim3(256), 0, (hipStream_t)stream, preds, map_stride, P, mask, weit, partial, N, HW);
-    hipLaunchKernelGGL(loss_finalize_k, dim3(1), dim3(1024), 0, (hipStream_t)stream, partial, P, N, nb, sums, wsum, loss);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<loss_fwd_k>(dim3(nb, N, P), dim3(256), 0, 0, (hipStream_t)stream, preds, map_stride, P, mask, weit, partial, N, HW)) return rc;
+    return pn2_launch<loss_finalize_k>(dim3(1), dim3(1024), 0, 0, (hipStream_t)stream, (const float*)partial, P, N, nb, sums, wsum, loss);
+}
+
+// the one launch of both backward entry points; dmap_stride < 0: the gradient maps lie at map_stride, gscale_dev == NULL: the host's gscale
+static int loss_bwd_launch(const float* preds, float* dpreds, long long map_stride, long long dmap_stride, int P, const float* mask, const float* weit, const float* wsum,
+                           const float* sums, const float* gscale_dev, float gscale, int N, int HW, void* stream) {
+    int nb = (HW + 1023) / 1024; if (nb > 256) nb = 256;
+    return pn2_launch<loss_bwd_k>(dim3(nb, N, P), dim3(256), 0, 0, (hipStream_t)stream, preds, dpreds, map_stride, P, mask, weit, wsum, sums, gscale, N, HW, dmap_stride, gscale_dev);
 }
 
 int pn2_structure_loss_bwd(const float* preds, float* dpreds, long long map_stride, int P, const float* mask, const float* weit, const float* wsum,
                            const float* sums, float gscale, int N, int HW, void* stream) {
     if (!preds || !dpreds || !mask || !weit || !wsum || !sums) return -1;
-    int nb = (HW + 1023) / 1024; if (nb > 256) nb = 256;
-    hipLaunchKernelGGL(loss_bwd_k, dim3(nb, N, P), dim3(256), 0, (hipStream_t)stream, preds, dpreds, map_stride, P, mask, weit, wsum, sums, gscale, N, HW);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return loss_bwd_launch(preds, dpreds, map_stride, -1, P, mask, weit, wsum, sums, nullptr, gscale, N, HW, stream);
 }
 
 int pn2_structure_loss_bwd_dev(const float* preds, float* dpreds, long long map_stride, long long dmap_stride, int P, const float* mask, const float* weit, const float* wsum,
                                const float* sums, const float* gscale_dev, float gscale, int N, int HW, void* stream) {
     if (!preds || !dpreds || !mask || !weit || !wsum || !sums) return -1;
     if (map_stride < 0 || dmap_stride < 0) return -2;
-    int nb = (HW + 1023) / 1024; if (nb > 256) nb = 256;
-    hipLaunchKernelGGL(loss_bwd_k, dim3(nb, N, P), dim3(256), 0, (hipStream_t)stream, preds, dpreds, map_stride, P, mask, weit, wsum, sums, gscale, N, HW, dmap_stride, gscale_dev);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return loss_bwd_launch(preds, dpreds, map_stride, dmap_stride, P, mask, weit, wsum, sums, gscale_dev, gscale, N, HW, stream);
 }
 
 int pn2_adam_tick(float* bc, float beta1, float beta2, void* stream) {
     if (!bc) return -1;
-    hipLaunchKernelGGL(adam_tick_k, dim3(1), dim3(1), 0, (hipStream_t)stream, bc, beta1, beta2);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<adam_tick_k>(dim3(1), dim3(1), 0, 0, (hipStream_t)stream, bc, beta1, beta2);
 }
 
 int pn2_clamp_adam(float* param, float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr, float beta1, float beta2,
                    float eps, float clip, float grad_scale, const float* bias_corr, float weight_decay, void* stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !bias_corr) return -1;
     if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return -2;
-    hipLaunchKernelGGL(clamp_adam_k, dim3(grid_for((size_t)(n / 4 + 1), 4096)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, clip, grad_scale, bias_corr, weight_decay);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<clamp_adam_k>(dim3(pn2_host::grid_for((size_t)(n / 4 + 1), 4096)), dim3(256), 0, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, clip, grad_scale,
+                                    bias_corr, weight_decay);
 }
 
 int pn2_eval_tail(const float* res, unsigned char* out, float* minmax, long long n, void* stream) {
     if (!res || !out || !minmax) return -1;
-    const int nb = grid_for((size_t)n, 512);
+    const int nb = pn2_host::grid_for((size_t)n, 512);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(minmax_k, dim3(nb), dim3(256), 0, st, res, n, minmax);
-    hipLaunchKernelGGL(minmax_final_k, dim3(1), dim3(64), 0, st, minmax, nb);
-    hipLaunchKernelGGL(eval_u8_k, dim3(grid_for((size_t)n)), dim3(256), 0, st, res, out, minmax, n);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<minmax_k>(dim3(nb), dim3(256), 0, 0, st, res, n, minmax)) return rc;
+    if (int rc = pn2_launch<minmax_final_k>(dim3(1), dim3(64), 0, 0, st, minmax, nb)) return rc;
+    return pn2_launch<eval_u8_k>(dim3(pn2_host::grid_for((size_t)n, 16384)), dim3(256), 0, 0, st, res, out, (const float*)minmax, n);
 }
 
 int pn2_dsra_tail_blocks(int OH) { return (OH + TRB - 1) / TRB; }
+
+constexpr int TAIL_LDS_CAP = 60 * 1024;          // dynamic LDS the tail entry points accept: below the 64 KiB that need no opt-in
 
 static int tail_check(const pn2_tail_desc* d) {
     if (!d || d->P < 1 || d->P > 4 || (d->OW & 3) || d->OW > 1024 || d->N < 1 || d->P * d->N > 512) return -2;
@@ -1431,14 +1416,30 @@ static bool tail_band_ok(const pn2_tail_desc* d) {
     return true;
 }
 
-static void tail_band_geometry(const pn2_tail_desc* d, const tail_groups& G, tail_band_aux& A, int& threads, int& blocks, size_t& lds_f, size_t& lds_b) {
-    const int LV = d->OW >> 2;
+// row lanes of the band and one-pass kernels: R rows of a band, OW / 4 threads each, in whole waves of at most 256 threads
+static int tail_row_lanes(int OW, int& threads) {
+    const int LV = OW >> 2;
     int R = 1; while (R * 2 * LV <= 256 && R * 2 <= TRB) R <<= 1;
-    A.R = R; threads = (R * LV + 63) & ~63;
-    A.nbn = pn2_dsra_tail_blocks(d->OH) * d->N;
-    blocks = G.ng * ((A.nbn + 7) & ~7);
+    threads = (R * LV + 63) & ~63;
+    return R;
+}
+// the band backward's partials of one (band, image): 3 low-res rows of every map
+static void tail_band_slots(const pn2_tail_desc* d, tail_band_aux& A) {
     A.ptot = 0;
     for (int j = 0; j < 2 * d->P; ++j) { A.poff[j] = A.ptot; A.ptot += 3 * d->maps[j].w; }
+}
+// elements of the largest low-res map over the batch: the x extent of the gradient-finishing grids
+static int tail_max_elems(const pn2_tail_desc* d) {
+    int emax = 0;
+    for (int j = 0; j < 2 * d->P; ++j) emax = std::max(emax, d->N * d->maps[j].h * d->maps[j].w);
+    return emax;
+}
+
+static void tail_band_geometry(const pn2_tail_desc* d, const tail_groups& G, tail_band_aux& A, int& threads, int& blocks, size_t& lds_f, size_t& lds_b) {
+    A.R = tail_row_lanes(d->OW, threads);
+    A.nbn = pn2_dsra_tail_blocks(d->OH) * d->N;
+    blocks = G.ng * ((A.nbn + 7) & ~7);
+    tail_band_slots(d, A);
     lds_f = lds_b = 0;
     for (int g = 0; g < G.ng; ++g) {
         const size_t v = (((size_t)TBM * TRB * (d->maps[G.idx[g][0]].w + 1) + 3) & ~(size_t)3) * 4;
@@ -1452,10 +1453,8 @@ static void tail_band_geometry(const pn2_tail_desc* d, const tail_groups& G, tai
 // geometry, <= 4 rows per thread, maps of >= 5 pixels (tail_one_fin_k's image window)
 static bool tail_one_geometry(const pn2_tail_desc* d, tail_one_aux& A, int& threads, size_t& lds) {
     if (tail_mode() != 2 || d->align_corners || d->OW > 512 || (long long)d->N * pn2_dsra_tail_blocks(d->OH) > 0x7fffffffLL) return false;
-    const int LV = d->OW >> 2;
-    int R = 1; while (R * 2 * LV <= 256 && R * 2 <= TRB) R <<= 1;
-    if (TRB / R > 4) return false;
-    A.R = R; threads = (R * LV + 63) & ~63;
+    A.R = tail_row_lanes(d->OW, threads);
+    if (TRB / A.R > 4) return false;
     A.nb = pn2_dsra_tail_blocks(d->OH);
     A.ptot = 0; A.vtot = 0;
     for (int p = 0; p < d->P; ++p) {
@@ -1470,15 +1469,15 @@ static bool tail_one_geometry(const pn2_tail_desc* d, tail_one_aux& A, int& thre
     }
     for (int j = 0; j < 2 * d->P; ++j) { A.voff[j] = A.vtot; A.vtot += 3 * (d->maps[j].w + 1); }
     A.vtot = (A.vtot + 3) & ~3;
-    lds = ((size_t)A.vtot + (size_t)R * TNK * LV * 2) * 4;
-    return lds <= 60 * 1024;
+    lds = ((size_t)A.vtot + (size_t)A.R * TNK * (d->OW >> 2) * 2) * 4;
+    return lds <= TAIL_LDS_CAP;
 }
 
 int pn2_dsra_tail_scratch(const pn2_tail_desc* d) {
     if (tail_check(d) || !tail_band_ok(d)) return 0;
-    long long ptot = 0;
-    for (int j = 0; j < 2 * d->P; ++j) ptot += 3 * d->maps[j].w;
-    const long long need = (long long)d->N * pn2_dsra_tail_blocks(d->OH) * ptot;
+    tail_band_aux A;
+    tail_band_slots(d, A);
+    const long long need = (long long)d->N * pn2_dsra_tail_blocks(d->OH) * A.ptot;
     return need > 0x7fffffffLL ? 0 : (int)need;          // (never reached with tail_check's limits: N*P <= 512, OW <= 1024)
 }
 
@@ -1493,24 +1492,19 @@ int pn2_dsra_tail_fwd(const pn2_tail_desc* d, float* lat, const float* mask, con
         tail_groups G; tail_band_aux A; int threads, blocks; size_t lds_f, lds_b;
         tail_make_groups(d, G, TBM);
         tail_band_geometry(d, G, A, threads, blocks, lds_f, lds_b);
-        if (lds_f <= 60 * 1024) hipLaunchKernelGGL(tail_band_fwd_k, dim3(blocks), dim3(threads), lds_f, st, *d, G, A, lat, mask, weit, partial);
-        else band = false;
+        if (lds_f > TAIL_LDS_CAP) band = false;
+        else if (int rc = pn2_launch<tail_band_fwd_k>(dim3(blocks), dim3(threads), lds_f, TAIL_LDS_CAP, st, *d, G, A, lat, mask, weit, partial)) return rc;
     }
     if (!band) {
         size_t lds = 0;
         for (int j = 0; j < 2 * d->P; ++j) lds += (size_t)((int)(TRB * d->maps[j].rh) + 3) * d->maps[j].w * 4;
-        if (lds > 60 * 1024) return -2;
-        dim3 grid(nb, d->N);
-        switch (d->P) {
-            case 1: hipLaunchKernelGGL(tail_fwd_k<1>, grid, dim3(256), lds, st, *d, lat, mask, weit, partial); break;
-            case 2: hipLaunchKernelGGL(tail_fwd_k<2>, grid, dim3(256), lds, st, *d, lat, mask, weit, partial); break;
-            case 3: hipLaunchKernelGGL(tail_fwd_k<3>, grid, dim3(256), lds, st, *d, lat, mask, weit, partial); break;
-            default: hipLaunchKernelGGL(tail_fwd_k<4>, grid, dim3(256), lds, st, *d, lat, mask, weit, partial); break;
-        }
+        if (lds > TAIL_LDS_CAP) return -2;
+        const int rc = with_int<1, 2, 3, 4>(d->P, [&](auto p) {
+            return pn2_launch<tail_fwd_k<decltype(p)::value>>(dim3(nb, d->N), dim3(256), lds, TAIL_LDS_CAP, st, *d, lat, mask, weit, partial);
+        });
+        if (rc) return rc;
     }
-    hipLaunchKernelGGL(loss_finalize_k, dim3(1), dim3(1024), 0, st, partial, d->P, d->N, nb, sums, wsum, loss);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<loss_finalize_k>(dim3(1), dim3(1024), 0, 0, st, (const float*)partial, d->P, d->N, nb, sums, wsum, loss);
 }
 
 int pn2_dsra_tail_bwd(const pn2_tail_desc* d, const float* mask, const float* weit, const float* wsum, const float* sums,
@@ -1525,21 +1519,14 @@ int pn2_dsra_tail_bwd(const pn2_tail_desc* d, const float* mask, const float* we
         tail_band_aux A; int threads, blocks; size_t lds_f, lds_b;
         tail_make_groups(d, G, TBM);
         tail_band_geometry(d, G, A, threads, blocks, lds_f, lds_b);
-        if (lds_b <= 60 * 1024) {
-            const int nb = pn2_dsra_tail_blocks(d->OH);
-            hipLaunchKernelGGL(tail_band_bwd_k, dim3(blocks), dim3(threads), lds_b, st, *d, G, A, mask, weit, wsum, sums, gscale, scratch);
-            int emax = 0;
-            for (int j = 0; j < 2 * d->P; ++j) emax = std::max(emax, d->N * d->maps[j].h * d->maps[j].w);
-            hipLaunchKernelGGL(tail_band_fin_k, dim3((emax + 255) / 256, 2 * d->P), dim3(256), 0, st, *d, A, scratch, nb);
-            PN2_CHECK_LAUNCH();
-            return 0;
+        if (lds_b <= TAIL_LDS_CAP) {
+            if (int rc = pn2_launch<tail_band_bwd_k>(dim3(blocks), dim3(threads), lds_b, TAIL_LDS_CAP, st, *d, G, A, mask, weit, wsum, sums, gscale, scratch)) return rc;
+            return pn2_launch<tail_band_fin_k>(dim3((tail_max_elems(d) + 255) / 256, 2 * d->P), dim3(256), 0, 0, st, *d, A, (const float*)scratch, pn2_dsra_tail_blocks(d->OH));
         }
     }
     const size_t lds = tail_make_groups(d, G);
-    if (lds > 60 * 1024) return -2;
-    hipLaunchKernelGGL(tail_bwd_k, dim3(G.start[G.ng]), dim3(256), lds, st, *d, G, mask, weit, wsum, sums, gscale);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (lds > TAIL_LDS_CAP) return -2;
+    return pn2_launch<tail_bwd_k>(dim3(G.start[G.ng]), dim3(256), lds, TAIL_LDS_CAP, st, *d, G, mask, weit, wsum, sums, gscale);
 }
 
 int pn2_dsra_tail_fused_ok(const pn2_tail_desc* d) {
@@ -1566,19 +1553,14 @@ int pn2_dsra_tail_fwd_bwd(const pn2_tail_desc* d, float* lat, const float* mask,
     if (scratch_floats < (long long)d->N * A.nb * A.ptot) return -2;
     if (isum && (d->P * d->N > TLB_MAXPN || d->P > 8)) return -2;          // (P * N * 5 two-word fixed-point sums, ZERO on entry: pn2_loss_weights_clear; NULL: two more passes, see pn2.h)
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(A.nb * d->N), blk(threads);
-    switch (d->P) {
-        case 1: hipLaunchKernelGGL(tail_one_k<1>, grid, blk, lds, st, *d, A, lat, mask, weit, partial, scratch, isum); break;
-        case 2: hipLaunchKernelGGL(tail_one_k<2>, grid, blk, lds, st, *d, A, lat, mask, weit, partial, scratch, isum); break;
-        case 3: hipLaunchKernelGGL(tail_one_k<3>, grid, blk, lds, st, *d, A, lat, mask, weit, partial, scratch, isum); break;
-        default: hipLaunchKernelGGL(tail_one_k<4>, grid, blk, lds, st, *d, A, lat, mask, weit, partial, scratch, isum); break;
-    }
-    int emax = 0;
-    for (int j = 0; j < 2 * d->P; ++j) emax = std::max(emax, d->N * d->maps[j].h * d->maps[j].w);
-    hipLaunchKernelGGL(tail_one_fin_k, dim3((emax + 255) / 256, 2 * d->P + (isum ? 1 : 0)), dim3(256), 0, st, *d, A, scratch, partial, gscale, sums, wsum, per, loss, (const long long*)isum);
-    if (!isum) hipLaunchKernelGGL(loss_total_k, dim3(1), dim3(64), 0, st, per, d->P, d->N, loss);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    int rc = with_int<1, 2, 3, 4>(d->P, [&](auto p) {
+        return pn2_launch<tail_one_k<decltype(p)::value>>(dim3(A.nb * d->N), dim3(threads), lds, TAIL_LDS_CAP, st, *d, A, lat, mask, weit, partial, scratch, isum);
+    });
+    if (rc) return rc;
+    rc = pn2_launch<tail_one_fin_k>(dim3((tail_max_elems(d) + 255) / 256, 2 * d->P + (isum ? 1 : 0)), dim3(256), 0, 0, st, *d, A, (const float*)scratch, (const float*)partial, gscale, sums, wsum,
+                                    per, loss, (const long long*)isum);
+    if (rc || isum) return rc;
+    return pn2_launch<loss_total_k>(dim3(1), dim3(64), 0, 0, st, (const float*)per, d->P, d->N, loss);
 }
 
 int pn2_eval_hist(const unsigned char* pred_u8, const float* gt, long long n, unsigned* hist, void* stream) {
@@ -1586,9 +1568,7 @@ int pn2_eval_hist(const unsigned char* pred_u8, const float* gt, long long n, un
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(hist, 0, 512 * sizeof(unsigned), st) != hipSuccess) return -4;
     long long g = (n + 256 * 16 - 1) / (256 * 16);
-    hipLaunchKernelGGL(eval_hist_k, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, st, pred_u8, gt, n, hist);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<eval_hist_k>(dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, 0, st, pred_u8, gt, n, hist);
 }
 
 }  // extern "C"

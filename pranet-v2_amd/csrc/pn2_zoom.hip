@@ -296,7 +296,6 @@ __global__ __launch_bounds__(256) void ragged_dice_k(const uint8_t* __restrict__
 }
 
 inline bool axes_ok(int N, int H, int W) { return N >= 1 && H >= 1 && W >= 1 && H <= MAX_AXIS && W <= MAX_AXIS && (long long)N * H * W < (1ll << 40); }
-inline unsigned grid_of(size_t total) { return (unsigned)pn2_host::grid_for(total, 16384); }
 
 template <typename F>
 int with_elem(int elem, F f) {
@@ -397,16 +396,11 @@ int pn2_zoom_prefilter(const float* src, int N, int H, int W, void* work, void* 
     const long long b0 = (long long)N * ((W + 63) / 64), b1 = (long long)N * ((H + 63) / 64);
     if (b0 > 0x7fffffffll || b1 > 0x7fffffffll) return -2;
     // axis 0: lines along H, lanes on x; the result lands in B as [N][W][H]
-    hipLaunchKernelGGL(spline_causal_k<float>, dim3((unsigned)b0), dim3(64), 0, st, src, A, H, W, (W + 63) / 64, ZP, gain, std::pow(ZP, (double)(H - 1)));
-    PN2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(spline_anticausal_t_k, dim3((unsigned)b0), dim3(64), 0, st, (const double*)A, B, H, W, (W + 63) / 64, ZP);
-    PN2_CHECK_LAUNCH();
+    if (int rc = pn2_launch<spline_causal_k<float>>(dim3((unsigned)b0), dim3(64), 0, 0, st, src, A, H, W, (W + 63) / 64, ZP, gain, std::pow(ZP, (double)(H - 1)))) return rc;
+    if (int rc = pn2_launch<spline_anticausal_t_k>(dim3((unsigned)b0), dim3(64), 0, 0, st, (const double*)A, B, H, W, (W + 63) / 64, ZP)) return rc;
     // axis 1: lines along W of the transposed planes, lanes on y; the transposed store gives [N][H][W] back
-    hipLaunchKernelGGL(spline_causal_k<double>, dim3((unsigned)b1), dim3(64), 0, st, (const double*)B, A, W, H, (H + 63) / 64, ZP, gain, std::pow(ZP, (double)(W - 1)));
-    PN2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(spline_anticausal_t_k, dim3((unsigned)b1), dim3(64), 0, st, (const double*)A, B, W, H, (H + 63) / 64, ZP);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<spline_causal_k<double>>(dim3((unsigned)b1), dim3(64), 0, 0, st, (const double*)B, A, W, H, (H + 63) / 64, ZP, gain, std::pow(ZP, (double)(W - 1)))) return rc;
+    return pn2_launch<spline_anticausal_t_k>(dim3((unsigned)b1), dim3(64), 0, 0, st, (const double*)A, B, W, H, (H + 63) / 64, ZP);
 }
 
 int pn2_zoom3_gather(const double* coef, int N, int H, int W, int OH, int OW, const int* iy_dev, const double* wy_dev, const int* vy_dev, const int* ix_dev,
@@ -414,9 +408,7 @@ int pn2_zoom3_gather(const double* coef, int N, int H, int W, int OH, int OW, co
     if (!coef || !iy_dev || !wy_dev || !vy_dev || !ix_dev || !wx_dev || !vx_dev || !out) return -1;
     if (!axes_ok(N, H, W) || !axes_ok(N, OH, OW)) return -2;
     const size_t total = (size_t)N * OH * OW;
-    hipLaunchKernelGGL(zoom3_gather_k, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, coef, H, W, OH, OW, iy_dev, wy_dev, vy_dev, ix_dev, wx_dev, vx_dev, out, total);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<zoom3_gather_k>(dim3(pn2_host::grid_for(total, 16384)), dim3(256), 0, 0, (hipStream_t)stream, coef, H, W, OH, OW, iy_dev, wy_dev, vy_dev, ix_dev, wx_dev, vx_dev, out, total);
 }
 
 int pn2_zoom0(int elem, const void* src, int N, int H, int W, int OH, int OW, const int* iy_dev, const int* vy_dev, const int* ix_dev, const int* vx_dev, void* out,
@@ -426,9 +418,7 @@ int pn2_zoom0(int elem, const void* src, int N, int H, int W, int OH, int OW, co
     const size_t total = (size_t)N * OH * OW;
     return with_elem(elem, [&](auto t) {
         using T = type_of<decltype(t)>;
-        hipLaunchKernelGGL(zoom0_k<T>, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, (const T*)src, H, W, OH, OW, iy_dev, vy_dev, ix_dev, vx_dev, (T*)out, total);
-        PN2_CHECK_LAUNCH();
-        return 0;
+        return pn2_launch<zoom0_k<T>>(dim3(pn2_host::grid_for(total, 16384)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)src, H, W, OH, OW, iy_dev, vy_dev, ix_dev, vx_dev, (T*)out, total);
     });
 }
 
@@ -438,9 +428,7 @@ int pn2_rotate0(int elem, const void* src, int N, int H, int W, const double* m6
     const size_t total = (size_t)N * H * W;
     return with_elem(elem, [&](auto t) {
         using T = type_of<decltype(t)>;
-        hipLaunchKernelGGL(rotate0_k<T>, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, (const T*)src, H, W, m6_dev, (T*)out, total);
-        PN2_CHECK_LAUNCH();
-        return 0;
+        return pn2_launch<rotate0_k<T>>(dim3(pn2_host::grid_for(total, 16384)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)src, H, W, m6_dev, (T*)out, total);
     });
 }
 
@@ -450,9 +438,7 @@ int pn2_rot_flip(int elem, const void* src, int N, int S, const int* kaxis_dev, 
     const size_t total = (size_t)N * S * S;
     return with_elem(elem, [&](auto t) {
         using T = type_of<decltype(t)>;
-        hipLaunchKernelGGL(rot_flip_k<T>, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, (const T*)src, S, kaxis_dev, (T*)out, total);
-        PN2_CHECK_LAUNCH();
-        return 0;
+        return pn2_launch<rot_flip_k<T>>(dim3(pn2_host::grid_for(total, 16384)), dim3(256), 0, 0, (hipStream_t)stream, (const T*)src, S, kaxis_dev, (T*)out, total);
     });
 }
 
@@ -558,15 +544,10 @@ int pn2_ragged_prefilter(const float* src, const void* plan_host, const void* pl
     double* A = B + h->work_doubles;
     const double gain = filter_gain();
     // the passes of pn2_zoom_prefilter, each sample on its own lines: axis 0 lands in B as [gw][gh], axis 1 restores [gh][gw]
-    hipLaunchKernelGGL(ragged_causal_k<0>, dim3((unsigned)h->blocks0), dim3(64), 0, st, src, (const double*)nullptr, A, descs, bs0, h->N, ZP, gain);
-    PN2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ragged_anticausal_t_k<0>, dim3((unsigned)h->blocks0), dim3(64), 0, st, (const double*)A, B, descs, bs0, h->N, ZP);
-    PN2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ragged_causal_k<1>, dim3((unsigned)h->blocks1), dim3(64), 0, st, (const float*)nullptr, (const double*)B, A, descs, bs1, h->N, ZP, gain);
-    PN2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ragged_anticausal_t_k<1>, dim3((unsigned)h->blocks1), dim3(64), 0, st, (const double*)A, B, descs, bs1, h->N, ZP);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    if (int rc = pn2_launch<ragged_causal_k<0>>(dim3((unsigned)h->blocks0), dim3(64), 0, 0, st, src, (const double*)nullptr, A, descs, bs0, h->N, ZP, gain)) return rc;
+    if (int rc = pn2_launch<ragged_anticausal_t_k<0>>(dim3((unsigned)h->blocks0), dim3(64), 0, 0, st, (const double*)A, B, descs, bs0, h->N, ZP)) return rc;
+    if (int rc = pn2_launch<ragged_causal_k<1>>(dim3((unsigned)h->blocks1), dim3(64), 0, 0, st, (const float*)nullptr, (const double*)B, A, descs, bs1, h->N, ZP, gain)) return rc;
+    return pn2_launch<ragged_anticausal_t_k<1>>(dim3((unsigned)h->blocks1), dim3(64), 0, 0, st, (const double*)A, B, descs, bs1, h->N, ZP);
 }
 
 int pn2_ragged_zoom3(const float* src, const void* plan_host, const void* plan_dev, const void* work, float* out, void* stream) {
@@ -575,10 +556,8 @@ int pn2_ragged_zoom3(const float* src, const void* plan_host, const void* plan_d
     if (!header_ok(h)) return -2;
     if (h->blocks0 != 0 && !work) return -1;
     const char* pd = (const char*)plan_dev;
-    hipLaunchKernelGGL(ragged_zoom3_k, dim3(ragged_grid_x(h), (unsigned)h->N), dim3(256), 0, (hipStream_t)stream, src, (const double*)work,
-                       (const pn2_ragged_desc*)(pd + h->desc_off), (const double*)(pd + h->tab_off), out);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<ragged_zoom3_k>(dim3(ragged_grid_x(h), (unsigned)h->N), dim3(256), 0, 0, (hipStream_t)stream, src, (const double*)work,
+                                      (const pn2_ragged_desc*)(pd + h->desc_off), (const double*)(pd + h->tab_off), out);
 }
 
 int pn2_ragged_zoom0(const unsigned char* src, const void* plan_host, const void* plan_dev, unsigned char* out, void* stream) {
@@ -586,20 +565,15 @@ int pn2_ragged_zoom0(const unsigned char* src, const void* plan_host, const void
     const pn2_ragged_header* h = (const pn2_ragged_header*)plan_host;
     if (!header_ok(h)) return -2;
     const char* pd = (const char*)plan_dev;
-    hipLaunchKernelGGL(ragged_zoom0_k, dim3(ragged_grid_x(h), (unsigned)h->N), dim3(256), 0, (hipStream_t)stream, src, (const pn2_ragged_desc*)(pd + h->desc_off),
-                       (const double*)(pd + h->tab_off), out);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<ragged_zoom0_k>(dim3(ragged_grid_x(h), (unsigned)h->N), dim3(256), 0, 0, (hipStream_t)stream, src, (const pn2_ragged_desc*)(pd + h->desc_off),
+                                      (const double*)(pd + h->tab_off), out);
 }
 
 int pn2_ragged_dice_counts(const unsigned char* pred, const unsigned char* gt, const void* plan_host, const void* plan_dev, long long* counts, void* stream) {
     if (!pred || !gt || !plan_host || !plan_dev || !counts) return -1;
     const pn2_ragged_header* h = (const pn2_ragged_header*)plan_host;
     if (!header_ok(h)) return -2;
-    hipLaunchKernelGGL(ragged_dice_k, dim3((unsigned)h->N), dim3(256), 0, (hipStream_t)stream, pred, gt,
-                       (const pn2_ragged_desc*)((const char*)plan_dev + h->desc_off), counts);
-    PN2_CHECK_LAUNCH();
-    return 0;
+    return pn2_launch<ragged_dice_k>(dim3((unsigned)h->N), dim3(256), 0, 0, (hipStream_t)stream, pred, gt, (const pn2_ragged_desc*)((const char*)plan_dev + h->desc_off), counts);
 }
 
 }  // extern "C"
