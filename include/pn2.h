@@ -640,6 +640,20 @@ int pn2_seg_labels(const float* const* maps, int nmaps, int mode, int N, int K, 
  *   when every ld is a multiple of 4 and every base 16-byte aligned, as scalars otherwise: the same bits either way. */
 typedef struct { const float* p; int ld; int H, W; } pn2_seg_up_map;   /* NHWC fp32: channel k of pixel (n,y,x) at p[((n*H + y)*W + x)*ld + k], ld >= K */
 int pn2_seg_labels_up(const pn2_seg_up_map* maps, int nmaps, int mode, int N, int K, int OH, int OW, unsigned char* out /* [N][OH][OW] */, void* stream);
+/* pn2_seg_labels_up_tta: pn2_seg_labels_up under flip test-time augmentation (tta_model, utils.py:303-325), still one launch.  The maps hold V * N samples: view v
+ *   of sample n is sample v * N + n.  `views` is a HOST array of V view codes, 1 <= V <= 4, each once: 0 identity, 1 horizontal flip (x mirrored), 2 vertical flip
+ *   (y mirrored), 3 both.  For output pixel (n, oy, ox) view v contributes the combined logits of `mode` (as pn2_seg_labels_up forms them, the same bits) at the
+ *   mirrored pixel (OH-1-oy and / or OW-1-ox) of its sample: the value that up-sampling the view's maps and flipping the result back gives.  average 0 "logit":
+ *   the views' combined logits are added in fp32 in view order; average 1 "prob": per view softmax over the K channels (exp(l - max l) / sum, fp32), the
+ *   probabilities added in view order.  The reference divides by V; the argmax does not see it, so the SUM is what is compared.  Argmax, ties and NaN as
+ *   pn2_seg_labels (a NaN logit makes all probabilities of its view NaN, as torch.softmax does: label 0).  V = 1, code 0, average 0 is pn2_seg_labels_up byte
+ *   for byte.  -2 besides pn2_seg_labels_up's cases: V outside 1..4, an unknown or repeated view code, an unknown average.  Rows that are not 16-byte aligned
+ *   or not a multiple of 4 wide are read as scalars, as in pn2_seg_labels_up.
+ * pn2_flip_views: out [V * N][H][W] fp32 = the V mirrored copies of src [N][H][W] (view codes as above; raw bits), one launch: what the forward of the V * N
+ *   samples reads.  16-byte loads and stores when W % 4 == 0 and both bases are 16-byte aligned, scalars otherwise. */
+int pn2_seg_labels_up_tta(const pn2_seg_up_map* maps, int nmaps, int mode, const int* views, int V, int average, int N, int K, int OH, int OW,
+                          unsigned char* out /* [N][OH][OW] */, void* stream);
+int pn2_flip_views(const float* src, int N, int H, int W, const int* views, int V, float* out, void* stream);
 int pn2_seg_counts(const unsigned char* pred, const unsigned char* gt, long long n, int K, unsigned long long* counts, void* stream);
 int pn2_seg_surface_workspace(int D, int H, int W, int ndim, long long* bytes);
 int pn2_seg_surface_hist_len(int D, int H, int W);          /* value; -1 outside the range */

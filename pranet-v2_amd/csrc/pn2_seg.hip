@@ -127,6 +127,90 @@ __global__ __launch_bounds__(256) void seg_labels_up_k(SegUpMaps maps, int nmaps
     out[((size_t)n * OH + oy) * OW + ox] = (u8)bk;
 }
 
+// ---- flip test-time augmentation (tta_model, utils.py:303-325): the maps hold V * N samples, view v of sample n at v * N + n; view code bit 0 = x mirrored,
+// bit 1 = y mirrored.  Up-sampling a view's map and flipping the result back is reading the up-sampled map at the mirrored output pixel: the same seg_up_combined,
+// the same bits.  The views are then added in their order, as combined logits (AVG 0) or as max-subtracted softmax probabilities (AVG 1), before the argmax.
+// The reference divides the sum by V; the argmax does not see a positive factor, so the sum is left undivided.
+// (seg_labels_up_k keeps its own copy of the combination: routed through seg_up_combined the compiler schedules it differently, and its device code is pinned.)
+struct SegViews { int code[4]; };
+
+// the combined logits of seg_labels_up_k at pixel (oy, ox) of sample n: the same expressions in the same order
+template <int MODE, int KV, bool VEC>
+__device__ __forceinline__ void seg_up_combined(const SegUpMaps& maps, int nmaps, int n, int oy, int ox, int K, float* acc) {
+    if (MODE == 0) seg_up_pixel<KV, VEC>(maps, nmaps - 1, n, oy, ox, K, acc);
+    else {
+#pragma unroll
+        for (int k = 0; k < 4 * KV; ++k) acc[k] = 0.0f;
+        const int h = nmaps / 2;
+        for (int m = 0; m < (MODE == 1 ? nmaps : h); ++m) {
+            float f[4 * KV], g[4 * KV];
+            seg_up_pixel<KV, VEC>(maps, m, n, oy, ox, K, f);
+            if (MODE == 2) seg_up_pixel<KV, VEC>(maps, h + m, n, oy, ox, K, g);
+            {
+#pragma clang fp contract(off)
+#pragma unroll
+                for (int k = 0; k < 4 * KV; ++k) { if (MODE == 1) acc[k] += f[k]; else acc[k] += (f[k] - g[k]); }
+            }
+        }
+    }
+}
+
+template <int MODE, int KV, bool VEC, int AVG>
+__global__ __launch_bounds__(256) void seg_labels_up_tta_k(SegUpMaps maps, int nmaps, int K, int OH, int OW, int N, SegViews views, int V, u8* __restrict__ out) {
+    const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6), n = blockIdx.z;
+    if (ox >= OW || oy >= OH) return;
+    float tot[4 * KV];
+    for (int v = 0; v < V; ++v) {
+        const int code = views.code[v];
+        float lg[4 * KV];
+        seg_up_combined<MODE, KV, VEC>(maps, nmaps, v * N + n, (code & 2) ? OH - 1 - oy : oy, (code & 1) ? OW - 1 - ox : ox, K, lg);
+        if (AVG == 1) {          // softmax over the channels below K; a NaN logit makes every probability of the view NaN, as torch.softmax does
+#pragma clang fp contract(off)
+            float mx = lg[0];
+#pragma unroll
+            for (int k = 1; k < 4 * KV; ++k) if (k < K) mx = fmaxf(mx, lg[k]);
+            float s = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4 * KV; ++k) { lg[k] = k < K ? expf(lg[k] - mx) : 0.0f; s += lg[k]; }
+            const float rs = 1.0f / s;          // s >= 1: the largest logit contributes exp(0)
+#pragma unroll
+            for (int k = 0; k < 4 * KV; ++k) lg[k] *= rs;
+        }
+        {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int k = 0; k < 4 * KV; ++k) tot[k] = v == 0 ? lg[k] : tot[k] + lg[k];
+        }
+    }
+    float best = 0.f; int bk = 0;
+#pragma unroll
+    for (int k = 0; k < 4 * KV; ++k) {
+        const float t = tot[k];
+        if (k < K && (k == 0 || t > best || (t != t && best == best))) { best = t; bk = k; }
+    }
+    out[((size_t)n * OH + oy) * OW + ox] = (u8)bk;
+}
+
+// out[v * N + n][y][x] = src[n][y'][x'] with (y', x') the pixel mirrored by view v's code: raw bits.  VEC: four x per thread, one 16-byte load (of the mirrored
+// quad, reversed in registers) and one 16-byte store; W % 4 == 0 keeps both aligned
+template <bool VEC>
+__global__ __launch_bounds__(256) void flip_views_k(const float* __restrict__ src, int N, int H, int W, SegViews views, float* __restrict__ out, size_t total) {
+    const int Wq = VEC ? W / 4 : W;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const int q = (int)(idx % Wq);
+        size_t r = idx / Wq;
+        const int y = (int)(r % H); r /= H;
+        const int n = (int)(r % N), v = (int)(r / N);
+        const int code = views.code[v];
+        const float* row = src + ((size_t)n * H + ((code & 2) ? H - 1 - y : y)) * W;
+        if (VEC) {
+            f32x4_t t = ((const f32x4_t*)row)[(code & 1) ? Wq - 1 - q : q];
+            if (code & 1) t = f32x4_t{t[3], t[2], t[1], t[0]};
+            ((f32x4_t*)out)[idx] = t;
+        } else out[idx] = row[(code & 1) ? W - 1 - q : q];
+    }
+}
+
 // cnt[c][0..2] += |pred = c|, |gt = c|, |pred = c and gt = c|: LDS counters per block, then one atomic per non-zero counter
 __global__ __launch_bounds__(256) void seg_counts_k(const u8* __restrict__ pred, const u8* __restrict__ gt, long long n, int K, u64* __restrict__ cnt) {
     __shared__ unsigned sh[256 * 3];
@@ -277,6 +361,32 @@ bool seg_dims_ok(int D, int H, int W, int ndim) {
     return D >= 1 && H >= 1 && W >= 1 && D <= SEG_MAX_AXIS && H <= SEG_MAX_AXIS && W <= SEG_MAX_AXIS && (ndim == 3 || (ndim == 2 && D == 1));
 }
 
+// the map table of pn2_seg_labels_up / _tta: every row checked, r = 1 / s, vec = all rows readable as 16-byte vectors
+int seg_up_table(const pn2_seg_up_map* maps, int nmaps, int K, int OH, int OW, SegUpMaps& m, bool& vec) {
+    vec = true;
+    for (int i = 0; i < nmaps; ++i) {
+        const pn2_seg_up_map& s = maps[i];
+        if (!s.p) return -1;
+        if (s.ld < K || s.H < 1 || s.W < 1 || OH % s.H || OW % s.W || OH / s.H != OW / s.W) return -2;
+        m.p[i] = s.p; m.ld[i] = s.ld; m.H[i] = s.H; m.W[i] = s.W;
+        m.r[i] = (float)(1.0 / (double)(OH / s.H));
+        vec = vec && s.ld % 4 == 0 && ((uintptr_t)s.p & 15) == 0;
+    }
+    return 0;
+}
+
+// 1..4 view codes 0..3, none twice
+bool seg_views_ok(const int* views, int V, SegViews& sv) {
+    if (V < 1 || V > 4) return false;
+    unsigned seen = 0;
+    for (int v = 0; v < V; ++v) {
+        if (views[v] < 0 || views[v] > 3 || (seen >> views[v] & 1)) return false;
+        seen |= 1u << views[v];
+        sv.code[v] = views[v];
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -292,11 +402,9 @@ int pn2_seg_labels(const float* const* maps, int nmaps, int mode, int N, int K, 
     return with_int<0, 1, 2>(mode, [&](auto mo) { return pn2_launch<seg_labels_k<decltype(mo)::value>>(g, dim3(256), 0, 0, st, m, nmaps, N, K, HW, out); });
 }
 
-int pn2_seg_labels_up(const pn2_seg_up_map* maps, int nmaps, int mode, int N, int K, int OH, int OW, unsigned char* out, void* stream) {
-    if (!maps || !out || N < 1 || OH < 1 || OW < 1) return -1;
-    if (K < 2 || K > 16 || nmaps < 1 || nmaps > 8 || mode < 0 || mode > 2 || (mode == 2 && (nmaps & 1)) || N > 65535 || (OH + 3) / 4 > 65535) return -2;
-    SegUpMaps m = {};
-    bool vec = true;
+// the map table of pn2_seg_labels_up / _tta: every row checked, r = 1 / s, vec = all rows readable as 16-byte vectors
+static int seg_up_table(const pn2_seg_up_map* maps, int nmaps, int K, int OH, int OW, SegUpMaps& m, bool& vec) {
+    vec = true;
     for (int i = 0; i < nmaps; ++i) {
         const pn2_seg_up_map& s = maps[i];
         if (!s.p) return -1;
@@ -305,11 +413,65 @@ int pn2_seg_labels_up(const pn2_seg_up_map* maps, int nmaps, int mode, int N, in
         m.r[i] = (float)(1.0 / (double)(OH / s.H));
         vec = vec && s.ld % 4 == 0 && ((uintptr_t)s.p & 15) == 0;
     }
+    return 0;
+}
+
+// 1..4 view codes 0..3, none twice
+static bool seg_views_ok(const int* views, int V, SegViews& sv) {
+    if (V < 1 || V > 4) return false;
+    unsigned seen = 0;
+    for (int v = 0; v < V; ++v) {
+        if (views[v] < 0 || views[v] > 3 || (seen >> views[v] & 1)) return false;
+        seen |= 1u << views[v];
+        sv.code[v] = views[v];
+    }
+    return true;
+}
+
+int pn2_seg_labels_up(const pn2_seg_up_map* maps, int nmaps, int mode, int N, int K, int OH, int OW, unsigned char* out, void* stream) {
+    if (!maps || !out || N < 1 || OH < 1 || OW < 1) return -1;
+    if (K < 2 || K > 16 || nmaps < 1 || nmaps > 8 || mode < 0 || mode > 2 || (mode == 2 && (nmaps & 1)) || N > 65535 || (OH + 3) / 4 > 65535) return -2;
+    SegUpMaps m = {};
+    bool vec;
+    if (int rc = ::seg_up_table(maps, nmaps, K, OH, OW, m, vec)) return rc;
     const dim3 g((OW + 63) / 64, (OH + 3) / 4, N);
     hipStream_t st = (hipStream_t)stream;
     return with_int<0, 1, 2>(mode, [&](auto mo) { return with_int<1, 2, 3, 4>((K + 3) / 4, [&](auto kv) { return with_int<1, 0>(vec, [&](auto ve) {
         return pn2_launch<seg_labels_up_k<decltype(mo)::value, decltype(kv)::value, decltype(ve)::value != 0>>(g, dim3(256), 0, 0, st, m, nmaps, K, OH, OW, out);
     }); }); });
+}
+
+int pn2_seg_labels_up_tta(const pn2_seg_up_map* maps, int nmaps, int mode, const int* views, int V, int average, int N, int K, int OH, int OW, unsigned char* out,
+                          void* stream) {
+    if (!maps || !views || !out || N < 1 || OH < 1 || OW < 1) return -1;
+    if (K < 2 || K > 16 || nmaps < 1 || nmaps > 8 || mode < 0 || mode > 2 || (mode == 2 && (nmaps & 1)) || N > 65535 || (OH + 3) / 4 > 65535) return -2;
+    SegViews sv = {};
+    // the kernel forms the sample index v * N + n as an int: already implied by N <= 65535 and V <= 4 above, stated here (with room to spare) for the day N's limit moves
+    if (average < 0 || average > 1 || !::seg_views_ok(views, V, sv) || (long long)V * N > 0x7fffffffLL / 4) return -2;
+    SegUpMaps m = {};
+    bool vec;
+    if (int rc = ::seg_up_table(maps, nmaps, K, OH, OW, m, vec)) return rc;
+    const dim3 g((OW + 63) / 64, (OH + 3) / 4, N);
+    hipStream_t st = (hipStream_t)stream;
+    return with_int<0, 1, 2>(mode, [&](auto mo) { return with_int<1, 2, 3, 4>((K + 3) / 4, [&](auto kv) { return with_int<1, 0>(vec, [&](auto ve) {
+        return with_int<0, 1>(average, [&](auto av) {
+            return pn2_launch<seg_labels_up_tta_k<decltype(mo)::value, decltype(kv)::value, decltype(ve)::value != 0, decltype(av)::value>>(
+                g, dim3(256), 0, 0, st, m, nmaps, K, OH, OW, N, sv, V, out);
+        });
+    }); }); });
+}
+
+int pn2_flip_views(const float* src, int N, int H, int W, const int* views, int V, float* out, void* stream) {
+    if (!src || !views || !out || N < 1 || H < 1 || W < 1) return -1;
+    SegViews sv = {};
+    // flip_views_k splits a size_t index into int (v, n, y, q): the number of output samples has to fit an int (N has no other limit here)
+    if (!::seg_views_ok(views, V, sv) || (long long)V * N > 0x7fffffffLL) return -2;
+    const bool vec = W % 4 == 0 && (((uintptr_t)src | (uintptr_t)out) & 15) == 0;
+    const size_t total = (size_t)V * N * H * (vec ? W / 4 : W);
+    const dim3 g(pn2_host::grid_for(total, 16384));
+    return with_int<1, 0>(vec, [&](auto ve) {
+        return pn2_launch<flip_views_k<decltype(ve)::value != 0>>(g, dim3(256), 0, 0, (hipStream_t)stream, src, N, H, W, sv, out, total);
+    });
 }
 
 int pn2_seg_counts(const unsigned char* pred, const unsigned char* gt, long long n, int K, unsigned long long* counts, void* stream) {

@@ -306,6 +306,8 @@ SIGNATURES = {
     "pn2_eval_wfm_batch": [P, P, P, I, I, I, LL, P, C.c_double, P, P, P, P],
     "pn2_seg_labels": [P, I, I, I, I, I, I, P, P],
     "pn2_seg_labels_up": [C.POINTER(SegUpMap), I, I, I, I, I, I, P, P],
+    "pn2_seg_labels_up_tta": [C.POINTER(SegUpMap), I, I, C.POINTER(I), I, I, I, I, I, I, P, P],
+    "pn2_flip_views": [P, I, I, I, C.POINTER(I), I, P, P],
     "pn2_seg_counts": [P, P, LL, I, P, P],
     "pn2_seg_surface_workspace": [I, I, I, I, C.POINTER(LL)],
     "pn2_seg_surface_hist_len": [I, I, I],

@@ -11,7 +11,7 @@ from .capi import call, F32
 from .engine import Act, BnFoldCache, Engine, PackCache, StepArena, TUNER, _p, _stream
 from .graph import get_compute_dtype
 from .volinput import zoom
-from .voleval import MODES, predict_labels_up, volume_dice, volume_metrics
+from .voleval import AVERAGES, MODES, flip_views, parse_tta, predict_labels_up, predict_labels_up_tta, volume_dice, volume_metrics
 
 
 class Predictor:
@@ -175,9 +175,12 @@ class VolumePredictor(Predictor):
            vp.val_single_volume(image, label, classes, use_dual=True)   # -> [dice]                       as pn2.voleval.val_single_volume
     One graph per (batch, patch height, patch width, mode) holds the eval forward up to the low-resolution head maps (model._build_lowres) and ONE launch
     that turns them into the uint8 labels of the batch (pn2_seg_labels_up): the full-resolution K-class maps never exist.  The spline zoom going in, the order-0
-    zoom coming out and the metric kernels stay outside (volume sizes vary; their tables are cached on the host, pn2/volinput.py)."""
+    zoom coming out and the metric kernels stay outside (volume sizes vary; their tables are cached on the host, pn2/volinput.py).
+    tta: flip test-time augmentation (the reference's tta_model, utils.py:303-325) - None, "flips" (= ("id", "h", "v"), the reference's three views) or a tuple of
+    views from "id", "h" (x mirrored), "v" (y mirrored), "hv" without repeats.  tta_average "prob" adds the views' softmax probabilities (the reference's mean of
+    predicted masks), "logit" their combined logits; the sum is not divided by the number of views (the argmax does not see it).  See _labels_tta."""
 
-    def __init__(self, model, patch_size=(224, 224), batch_size=16, dtype=None):
+    def __init__(self, model, patch_size=(224, 224), batch_size=16, dtype=None, tta=None, tta_average="prob"):
         super().__init__(model, dtype)
         if not hasattr(model, "_build_lowres"):
             raise TypeError("VolumePredictor needs a model with K-class head maps (lib.networks.EMCADNet)")
@@ -185,6 +188,10 @@ class VolumePredictor(Predictor):
         self.batch_size = int(batch_size)
         if self.batch_size < 1:
             raise ValueError("batch_size >= 1")
+        self.views = parse_tta(tta)          # None: no test-time augmentation
+        if tta_average not in AVERAGES:
+            raise ValueError(f"tta_average {tta_average!r}: one of {sorted(AVERAGES)}")
+        self.tta_average = tta_average
 
     @staticmethod
     def _pick(lows, scales, mode):
@@ -203,6 +210,8 @@ class VolumePredictor(Predictor):
         if self.model.training:          # on every call: a replay would go on serving the eval-mode graph
             raise RuntimeError("VolumePredictor runs eval-mode BatchNorm: call model.eval() first")
         B, _, h, w = xb.shape
+        if self.views is not None:
+            return self._labels_tta(xb, mode)
 
         def run(st):
             eng, (lows, scales) = self._forward(st, st["x"], self.model._build_lowres)
@@ -214,8 +223,29 @@ class VolumePredictor(Predictor):
         st["graph"].replay()
         return st
 
+    def _labels_tta(self, xb, mode):
+        """_labels under flip test-time augmentation (tta_model, utils.py:303-325): the graph of key (B, h, w, mode, views, average) holds pn2_flip_views (the
+        V * B mirrored samples, view v of sample n at v * B + n), ONE eval forward over them (eval-mode BatchNorm keeps them independent) and one
+        pn2_seg_labels_up_tta launch that reads every view at the mirrored pixel and adds the views: neither a flipped nor a full-resolution K-class map exists."""
+        B, _, h, w = xb.shape
+        V = len(self.views)
+
+        def run(st):
+            flip_views(st["x"], self.views, out=st["xv"])
+            eng, (lows, scales) = self._forward(st, st["xv"], self.model._build_lowres)
+            st["lows"] = lows
+            maps, sc = self._pick([a.t[..., :a.C] for a in lows], list(scales), mode)
+            return predict_labels_up_tta(maps, sc, mode, self.views, self.tta_average, out=st["labels"])
+        st = self._captured((B, h, w, mode, self.views, self.tta_average), xb, run,
+                            lambda: {"labels": torch.empty((B, h, w), dtype=torch.uint8, device=xb.device), "lows": None,
+                                     "xv": torch.empty((V * B, 1, h, w), dtype=torch.float32, device=xb.device)})
+        st["x"].copy_(xb, non_blocking=True)
+        st["graph"].replay()
+        return st
+
     def lowres(self, xb, mode="last"):
-        """Debugging / tests: clones of the low-resolution head maps of one batch xb [B][1][h][w], NCHW fp32, as the graph of `mode` leaves them."""
+        """Debugging / tests: clones of the low-resolution head maps of one batch xb [B][1][h][w], NCHW fp32, as the graph of `mode` leaves them (with test-time
+        augmentation: of the V * B mirrored samples)."""
         st = self._labels(xb.float(), mode)
         return [a.t[..., :a.C].permute(0, 3, 1, 2).clone() for a in st["lows"]]
 

@@ -11,6 +11,8 @@ from .core import _p, _stream
 from .volinput import zoom
 
 MODES = {"last": 0, "sum_fg": 1, "sum_fg_minus_bg": 2}
+VIEWS = {"id": 0, "h": 1, "v": 2, "hv": 3}          # view codes of pn2_seg_labels_up_tta / pn2_flip_views: bit 0 = x mirrored, bit 1 = y mirrored
+AVERAGES = {"logit": 0, "prob": 1}
 MAX_AXIS = 1024
 
 
@@ -46,6 +48,14 @@ def predict_labels_up(maps, scales, mode, out=None):
     """predict_labels of the maps up-sampled bilinearly (align_corners=False) by their integer `scales`, in one launch and without the full-resolution maps
     (pn2_seg_labels_up): maps are 1..8 NHWC fp32 tensors [N][h][w][K], 2 <= K <= 16, each of its own size with h * scale, w * scale the same for all.  The last
     axis may be a slice of a wider, channel-padded one (t[..., :K]): only its stride has to be 1.  Returns uint8 [N][h * scale][w * scale] (written into `out` if given)."""
+    descs, N, K, OH, OW, dev = _up_descs(maps, scales, mode)
+    out = _labels_out(out, (N, OH, OW), dev)
+    call.pn2_seg_labels_up(descs, len(descs), MODES[mode], N, K, OH, OW, _p(out), _stream())
+    return out
+
+
+def _up_descs(maps, scales, mode):
+    """The checked descriptor table of predict_labels_up / predict_labels_up_tta -> (table, samples in the maps, K, OH, OW, device)."""
     if mode not in MODES:
         raise ValueError(f"mode {mode!r}: one of {sorted(MODES)}")
     maps, scales = [m.detach() for m in maps], [int(s) for s in scales]
@@ -62,11 +72,71 @@ def predict_labels_up(maps, scales, mode, out=None):
         if m.stride(3) != 1 or ld < K or m.stride(1) != m.shape[2] * ld or m.stride(0) != m.shape[1] * m.shape[2] * ld:
             raise ValueError("maps must be dense NHWC up to a padded channel axis")
         d.p, d.ld, d.H, d.W = m.data_ptr(), ld, m.shape[1], m.shape[2]
+    return descs, N, K, OH, OW, maps[0].device
+
+
+def _labels_out(out, shape, device):
     if out is None:
-        out = torch.empty((N, OH, OW), dtype=torch.uint8, device=maps[0].device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, OH, OW) or not out.is_contiguous() or not out.is_cuda:
-        raise ValueError(f"out must be a contiguous uint8 GPU tensor {(N, OH, OW)}")
-    call.pn2_seg_labels_up(descs, len(maps), MODES[mode], N, K, OH, OW, _p(out), _stream())
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous uint8 GPU tensor {shape}")
+    return out
+
+
+def parse_tta(tta):
+    """The `tta` argument of pn2.infer.VolumePredictor -> None or the tuple of view names: None; "flips" = ("id", "h", "v"), the three views of the reference's
+    tta_model (utils.py:311-325); or a non-empty tuple / list of names from VIEWS without repeats.  Anything else raises ValueError."""
+    if tta is None:
+        return None
+    if isinstance(tta, str):
+        if tta != "flips":
+            raise ValueError(f"tta {tta!r}: None, 'flips' or a tuple of views from {sorted(VIEWS)}")
+        return ("id", "h", "v")
+    if not isinstance(tta, (tuple, list)) or not 1 <= len(tta) <= len(VIEWS) or any(not isinstance(v, str) or v not in VIEWS for v in tta):
+        raise ValueError(f"tta {tta!r}: None, 'flips' or a tuple of views from {sorted(VIEWS)}")
+    if len(set(tta)) != len(tta):
+        raise ValueError(f"tta {tta!r}: a view is listed twice")
+    return tuple(tta)
+
+
+def _view_codes(views):
+    views = parse_tta(views)
+    if views is None:
+        raise ValueError("views: 'flips' or a tuple of views, not None")
+    return views, (C.c_int * len(views))(*[VIEWS[v] for v in views])
+
+
+def flip_views(x, views, out=None):
+    """x: fp32 [N][h][w] (or [N][1][h][w]) on the GPU -> [V * N] samples of the same trailing shape: view v of sample n at v * N + n, mirrored as its name in
+    VIEWS says (pn2_flip_views: one launch, raw bits)."""
+    views, codes = _view_codes(views)
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[1] != 1) or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("x must be a contiguous non-empty fp32 [N][h][w] or [N][1][h][w] tensor")
+    shape = (len(views) * x.shape[0],) + tuple(x.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous fp32 GPU tensor {shape}")
+    call.pn2_flip_views(_p(x), x.shape[0], x.shape[-2], x.shape[-1], codes, len(views), _p(out), _stream())
+    return out
+
+
+def predict_labels_up_tta(maps, scales, mode, views, average="prob", out=None):
+    """predict_labels_up under flip test-time augmentation, still one launch (pn2_seg_labels_up_tta).  The maps hold V * N samples, view v of sample n at v * N + n
+    (the layout flip_views writes); `views` are names from VIEWS ("id", "h": x mirrored, "v": y mirrored, "hv": both), each at most once.  Every view's combined
+    logits are read at the mirrored output pixel - the value that up-sampling the view's maps and flipping back gives - and the views are added in their order:
+    average="logit" adds the combined logits, average="prob" their softmax over K (the reference's mean of predicted masks).  The sum is not divided by V: the
+    argmax does not see it.  Returns uint8 [N][h * scale][w * scale]."""
+    if average not in AVERAGES:
+        raise ValueError(f"average {average!r}: one of {sorted(AVERAGES)}")
+    views, codes = _view_codes(views)
+    descs, VN, K, OH, OW, dev = _up_descs(maps, scales, mode)
+    if VN % len(views):
+        raise ValueError(f"{VN} samples in the maps are not a multiple of the {len(views)} views")
+    N = VN // len(views)
+    out = _labels_out(out, (N, OH, OW), dev)
+    call.pn2_seg_labels_up_tta(descs, len(descs), MODES[mode], codes, len(views), AVERAGES[average], N, K, OH, OW, _p(out), _stream())
     return out
 
 
@@ -200,14 +270,15 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], use_du
     return volume_metrics(pred, label, classes)
 
 
-def val_slices(images, labels, net_or_predictor, img_size, mode, batch_size=16):
+def val_slices(images, labels, net_or_predictor, img_size, mode, batch_size=16, tta=None, tta_average="prob"):
     """The val() loop of multiclass_seg/MIST/ACDC_train_test.py:48-93 over single slices of differing sizes: images a list of fp32 [x_i][y_i] slices, labels a list
     of uint8 label maps of the same shapes (all host arrays or all GPU tensors).  Per batch of slices: the ragged spline zoom to img_size x img_size (a slice of that
     size is not resampled, :59), the captured eval forward and label launch of a pn2.infer.VolumePredictor in one of its MODES (the reference sums P - P_bg over the
     map pairs for a dual model, 'sum_fg_minus_bg', and its maps otherwise, 'sum_fg'), the order-0 zoom of the labels back to every slice's own size (:82-83) and the
     three counts of medpy's binary dc(prediction, label) (:87), which treats every non-zero label as foreground.
     Returns (per-slice Dice 2 I / (A + B) as float64 ndarray, 0.0 where A + B = 0; their mean, val()'s `performance`).  A net is wrapped in a VolumePredictor of its
-    own; pass a VolumePredictor (patch_size (img_size, img_size)) to keep its graphs between calls."""
+    own (with flip test-time augmentation if `tta` is given: VolumePredictor's arguments); pass a VolumePredictor (patch_size (img_size, img_size)) to keep its
+    graphs between calls - its own tta setting then holds."""
     import numpy as np
     from . import volinput as V
     from .infer import VolumePredictor
@@ -219,7 +290,7 @@ def val_slices(images, labels, net_or_predictor, img_size, mode, batch_size=16):
     if not images or len(images) != len(labels):
         raise ValueError("one label map per slice, at least one slice")
     S = int(img_size)
-    vp = net_or_predictor if isinstance(net_or_predictor, VolumePredictor) else VolumePredictor(net_or_predictor, (S, S), batch_size)
+    vp = net_or_predictor if isinstance(net_or_predictor, VolumePredictor) else VolumePredictor(net_or_predictor, (S, S), batch_size, tta=tta, tta_average=tta_average)
     if vp.patch_size != (S, S):
         raise ValueError(f"the predictor's patch size {vp.patch_size} is not {(S, S)}")
     B = vp.batch_size
